@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """WT-PSE training throughput on MI355X (BASELINE.json metric: training images/sec at 256x256; WT-loss GB/s).
 
-    python bench.py --gpus 1 --steps 5 --warmup 2
+    python bench.py --gpus 1 --steps 5 --warmup 2          (the headline alone: set-up, warm-up, timed steps, the line)
+    python bench.py --gpus 1 --full                        (+ degenerate-ROI rate, kernel rooflines, configs[1], CPU baseline)
+    python bench.py --gpus 1 --dump-outputs DIR            (+ what the last timed step computed, as DIR/<name>.npy)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench.py --gpus N --steps K --warmup W
     python bench.py --gpus N ...        (WORLD_SIZE unset: starts those N ranks itself as a child `torch.distributed.run`,
@@ -82,6 +84,12 @@ def parse():
     ap.add_argument("--no-kernel-roofline", action="store_true")
     ap.add_argument("--kernels-only", action="store_true",
                     help="run only the per-kernel roofline launches (used under rocprofv3 --pmc to measure HBM traffic)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: the degenerate-ROI rate, the per-kernel rooflines, configs[1] (seg-only, fp32 / "
+                         "bf16) and the CPU baseline (each still off with its --no-* option).  Without it a run sets up, warms up, "
+                         "times --steps steps and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (see dump_outputs)")
     return ap.parse_args()
 
 
@@ -778,6 +786,38 @@ def step_hbm_traffic(ms_per_step, copy_gbs):
             "source": "committed %s (rocprofv3 --pmc, separate FETCH_SIZE / WRITE_SIZE passes over whole steps), not this run" % os.path.relpath(files[-1], ROOT)}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def _sample(t, n, seed):
+    """t as a float32 numpy array; above n values a fixed seeded sample of n of them (flattened, the same indices in every run)."""
+    import numpy as np
+    if t.numel() <= n:
+        return t.detach().float().cpu().numpy()
+    idx = np.sort(np.random.default_rng(seed).choice(t.numel(), n, replace=False))
+    return t.detach().reshape(-1)[torch.from_numpy(idx).to(t.device)].float().cpu().numpy()
+
+
+def dump_outputs(d, losses, ts, nets):
+    """What the last timed step hands its caller, as d/<name>.npy: every loss it returns (`loss_<key>`, float64 holding the fp32
+    value), the optic-disc mask its ROI was cut with (`od_pred`, [B,1,H,W]) and the weights its Adam steps left
+    (`weights_<net>`: the network's state_dict, floating-point entries concatenated in order; a fixed seeded sample of 2^21 values
+    where it holds more)."""
+    import numpy as np
+    out = {"loss_" + k: np.asarray(v, dtype=np.float64) for k, v in losses.items()}
+    out["od_pred"] = _sample(ts.last_od_pred, 1 << 22, seed=0)
+    for name, net in zip(("model_od", "shape_od", "model_oc", "shape_oc"), nets):
+        if net is not None:
+            flat = torch.cat([v.detach().reshape(-1).float() for v in net.state_dict().values() if v.is_floating_point()])
+            out["weights_" + name] = _sample(flat, 1 << 21, seed=1)
+    total = sum(a.nbytes for a in out.values())
+    assert total <= DUMP_LIMIT_BYTES, "outputs of %d bytes" % total
+    os.makedirs(d, exist_ok=True)
+    for k, a in out.items():
+        np.save(os.path.join(d, k + ".npy"), a)
+    log("outputs of the last timed step: %d arrays, %.1f MB in %s" % (len(out), total / 1e6, d))
+
+
 def rccl_version():
     """Version of the collective library behind the `nccl` backend (RCCL on ROCm), as torch reports it; None if it cannot say."""
     try:
@@ -934,9 +974,15 @@ def main():
     frac = od_fraction()
     presteps = 0
     if args.roi_presteps != 0 and full and not (0.02 <= frac <= 0.6):
-        dt0, _, _ = timed(min(args.steps, 10))
-        degenerate = {"value": world * B * min(args.steps, 10) / dt0, "unit": "images/s", "od_pred_fraction": frac,
-                      "note": "same step, ROI of calls C/D empty (initial weights): constant operands in half of the step"}
+        if args.full:
+            dt0, _, _ = timed(min(args.steps, 10))
+            degenerate = {"value": world * B * min(args.steps, 10) / dt0, "unit": "images/s", "od_pred_fraction": frac,
+                          "note": "same step, ROI of calls C/D empty (initial weights): constant operands in half of the step"}
+        else:
+            # the same steps untimed: the nets then train through the same states with and without --full, and the
+            # headline is timed on the same weights either way
+            for _ in range(min(args.steps, 10)):
+                ts.step(image, target_od, target_oc)
         limit = args.roi_presteps if args.roi_presteps > 0 else 400
         while presteps < limit:
             for _ in range(10):
@@ -953,6 +999,8 @@ def main():
     dt, t_host, losses = timed(args.steps)
     log("timed region: %.3f s for %d steps (host enqueue %.3f s)" % (dt, args.steps, t_host))
     assert all(v == v for v in losses.values()), "NaN loss: %s" % losses
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, losses, ts, nets)
 
     if rank == 0:
         ips = world * B * args.steps / dt
@@ -983,7 +1031,7 @@ def main():
         }
         if degenerate is not None:
             line["degenerate_roi"] = degenerate
-        if world == 1 and not args.no_kernel_roofline:
+        if args.full and world == 1 and not args.no_kernel_roofline:
             log("kernel rooflines")
             kr = kernel_rooflines(B, H, dev)
             tr, tr_note = measured_traffic() if (B, H) == (32, 256) else ({}, "traffic is measured at B=32, 256x256 only")
@@ -1068,11 +1116,11 @@ def main():
                                      "achieved_level_sum": w["gbs"], "bytes_level_sum": w["bytes_per_launch"],
                                      "note": "stand-alone micro-benchmark: the reference has no wavelet transform — not part of WT-PSE, "
                                              "parity unpinned (SURVEY.md 8f-4)"} for w in kr["dwt"]]
-        if world == 1 and full and args.dtype == "f32" and not args.no_kernel_roofline and (B, H) == (32, 256):
+        if args.full and world == 1 and full and args.dtype == "f32" and not args.no_kernel_roofline and (B, H) == (32, 256):
             # BASELINE.json configs[1] beside the headline (configs[2]): the segmentation net alone, fp32 results and the bf16 mode
             log("configs[1] (seg-net only): fp32 results, bf16 mode")
             line["configs1_seg_only"] = aux_seg_only(B, H, dev, args.steps, args.warmup)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             log("cpu baseline")
             line["cpu_baseline"] = cpu_baseline(H, full, args.cpu_baseline_full, args.cpu_threads)
             log("done")

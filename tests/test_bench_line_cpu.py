@@ -68,3 +68,38 @@ def test_bare_multi_gpu_invocation_starts_its_own_ranks(tmp_path):
     b = _bench()
     cmd = b.self_launch_command(["--gpus", "4"], 4, port=29511)
     assert cmd[:3] == [sys.executable, "-m", "torch.distributed.run"] and "--nproc-per-node" in cmd and cmd[cmd.index("--nproc-per-node") + 1] == "4"
+
+
+def test_plain_run_options_and_output_dump(tmp_path, monkeypatch):
+    """A plain run leaves the extra measurements to --full; --dump-outputs writes the last step's losses, ROI mask and a fixed
+    sample of the trained weights, within 64 MB, the same arrays from the same inputs."""
+    import sys
+    import types
+    import numpy as np
+    import torch
+    b = _bench()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "4", "--warmup", "1"])
+    a = b.parse()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (4, 1, False, None)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", str(tmp_path)])
+    a = b.parse()
+    assert a.full and a.dump_outputs == str(tmp_path)
+    from wtpse_hip.synth import default_hparams
+    nets = b.build_nets(default_hparams(True), 2, "cpu")
+    ts = types.SimpleNamespace(last_od_pred=(torch.rand(6, 1, 32, 32, generator=torch.Generator().manual_seed(0)) > 0.5).float())
+    for d in ("a", "b"):
+        b.dump_outputs(str(tmp_path / d), {"seg_od": 0.75, "kd_oc": 0.125}, ts, nets)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b")) == ["loss_kd_oc.npy", "loss_seg_od.npy", "od_pred.npy", "weights_model_oc.npy",
+                                                           "weights_model_od.npy", "weights_shape_oc.npy", "weights_shape_od.npy"]
+    total = 0
+    for n in names:
+        x, y = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert x.dtype in (np.float32, np.float64) and np.array_equal(x, y), n
+        total += x.nbytes
+    assert total <= b.DUMP_LIMIT_BYTES
+    assert float(np.load(tmp_path / "a" / "loss_seg_od.npy")) == 0.75
+    assert np.load(tmp_path / "a" / "od_pred.npy").shape == (6, 1, 32, 32)
+    w = np.load(tmp_path / "a" / "weights_model_od.npy")
+    sd = torch.cat([v.reshape(-1).float() for v in nets[0].state_dict().values() if v.is_floating_point()])
+    assert w.shape == (1 << 21,) and sd.numel() > (1 << 21) and np.isin(w[:64], sd.numpy()).all()
