@@ -415,6 +415,21 @@ int wtpse_resample_u8(const unsigned char* in, unsigned char* out, const int* bo
 int wtpse_input_finish(const unsigned char* img, const unsigned char* od, const int* xidx, const int* yidx, float* image,
                        float* od_out, float* oc_out, int N, int S, void* stream);
 
+/* ---- validation back half (csrc/postprocess.hip) --------------------------------------------------- */
+/* utils.postprocessing (utils.py:267-329) bit for bit: logit [B][h][w] fp32 -> out [B][h][w] uint8 = the largest 8-connected
+ * component of sigmoid(logit) > threshold (ties: the first in raster order), holes (background not 4-connected to the border)
+ * filled.  ws: wtpse_postprocess_ws(B, h, w) 4-byte words, 8-byte aligned.  1 <= h, w <= 4096. */
+int wtpse_postprocess_ws(int B, int h, int w);
+int wtpse_postprocess(const float* logit, unsigned char* out, void* ws, float threshold, int B, int h, int w, void* stream);
+/* Per-image Dice / ASD / HD95 ingredients of a mask A (uint8, nonzero = object) against a label B (fp32, nonzero = object), both
+ * [B][h][w]: rec [B][8] int64 = {|A & B|, |A|, |B|, surface pixels of A, of B, d2_lo, d2_hi, ASD sum}.  Surface = object XOR its
+ * erosion by the 4-neighbour cross (outside the image = background); d2 = exact squared Euclidean distance of a surface pixel to
+ * the other mask's surface; d2_lo / d2_hi = the two order statistics of the pooled d2 of both directions that numpy.percentile(.,
+ * 95) interpolates between (0 when a surface is empty); slot 7 holds the fp64 bits of sum(sqrt(d2)) over A's surface, folded in a
+ * fixed order.  ws: wtpse_seg_metrics_ws(B, h, w) 4-byte words, 8-byte aligned.  1 <= h, w <= 4096. */
+int wtpse_seg_metrics_ws(int B, int h, int w);
+int wtpse_seg_metrics(const unsigned char* mask, const float* label, long long* rec, void* ws, int B, int h, int w, void* stream);
+
 /* ---- small utilities ------------------------------------------------------------------------------------------- */
 int wtpse_relu_mask(const float* dz, const float* ref, float* dy, int accumulate, long long n, void* stream);
 int wtpse_axpy(float* dst, const float* src, float alpha, long long n, void* stream);

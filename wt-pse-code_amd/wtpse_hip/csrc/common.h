@@ -40,6 +40,9 @@ __device__ __forceinline__ float wave_xor_sum(float v, int mask_hi) {
 
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 
+// The logistic function as the reference's od_pred / post-processing thresholds see it (roi_k, postprocess.hip).
+__device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
+
 // Raw buffer resource (stride 0) over `bytes` bytes at `p`: loads whose per-lane byte offset is >= bytes return 0
 // in hardware, so zero padding / ragged tiles need no per-element branch; the per-channel plane offset rides in
 // the scalar `soffset` operand (measured on gfx950 with tools/probe/bufload.hip: a lane is out of range when

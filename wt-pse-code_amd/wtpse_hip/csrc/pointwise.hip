@@ -9,7 +9,6 @@ __device__ __forceinline__ float act_in(float v, const float* pro, int c, int re
   if (pro) v = fmaf(v, pro[2 * c], pro[2 * c + 1]);
   return relu ? fmaxf(v, 0.f) : v;
 }
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
 
 __device__ __forceinline__ float block_sum(float v, float* sh4) {  // 256 threads
   v = wave_xor_sum(v, 32);

@@ -866,3 +866,46 @@ def adam_step(p, g, m, v, lr, beta1, beta2, eps, step, step_dev=None):
     """Step number t = step + *step_dev (step_dev: device int32 count of completed steps, or None)."""
     lib().call("wtpse_adam", ptr(p), ptr(g), ptr(m), ptr(v), p.numel(), float(lr), float(beta1), float(beta2), float(eps),
                int(step), ptr(step_dev), stream_ptr())
+
+
+# ----------------------------------------------------------------------------------------------- validation back half
+def _chk_dev(t, name, dtype):
+    if not (t.is_cuda and t.dtype == dtype and t.is_contiguous() and t.dim() == 4 and t.shape[1] == 1):
+        raise ValueError("%s must be a contiguous [B,1,h,w] %s tensor in device memory (got %s, %s, %s)"
+                         % (name, dtype, tuple(t.shape), t.device, t.dtype))
+
+
+def postprocess_masks(logits, threshold=0.75):
+    """utils.postprocessing on the device: [B,1,h,w] fp32 logits -> uint8 [B,1,h,w] = largest 8-connected component of
+    sigmoid > threshold, holes filled (bit for bit validate.postprocess)."""
+    _chk_dev(logits, "logits", torch.float32)
+    B, _, h, w = logits.shape
+    L = lib()
+    words = L.query("wtpse_postprocess_ws", B, h, w)
+    if words <= 0:
+        raise ValueError("postprocess_masks: unsupported size %s (1 <= h, w <= 4096)" % (tuple(logits.shape),))
+    out = torch.empty((B, 1, h, w), dtype=torch.uint8, device=logits.device)
+    ws = workspace("postprocess", words, logits.device)
+    L.call("wtpse_postprocess", ptr(logits), ptr(out), ptr(ws), float(threshold), B, h, w, stream_ptr())
+    return out
+
+
+SEG_FIELDS = ("inter", "n_pred", "n_label", "surf_pred", "surf_label", "d2_lo", "d2_hi", "asd_sum")
+
+
+def seg_metrics(mask, label):
+    """Raw per-image records [B,8] int64 (fields SEG_FIELDS; the last one holds float64 bits) of a uint8 mask against an fp32
+    label (nonzero = object), both [B,1,h,w] on the device.  validate.device_metrics finishes them."""
+    _chk_dev(mask, "mask", torch.uint8)
+    _chk_dev(label, "label", torch.float32)
+    if mask.shape != label.shape or mask.device != label.device:
+        raise ValueError("mask %s and label %s differ in shape or device" % (tuple(mask.shape), tuple(label.shape)))
+    B, _, h, w = mask.shape
+    L = lib()
+    words = L.query("wtpse_seg_metrics_ws", B, h, w)
+    if words <= 0:
+        raise ValueError("seg_metrics: unsupported size %s (1 <= h, w <= 4096)" % (tuple(mask.shape),))
+    rec = torch.empty((B, 8), dtype=torch.int64, device=mask.device)
+    ws = workspace("seg_metrics", words, mask.device)
+    L.call("wtpse_seg_metrics", ptr(mask), ptr(label), ptr(rec), ptr(ws), B, h, w, stream_ptr())
+    return rec

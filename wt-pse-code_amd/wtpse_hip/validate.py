@@ -12,6 +12,12 @@ connectivity-1 structuring element, distances = Euclidean distance transform of 
 this surface; asd = their mean (result -> reference, ONE direction, as medpy's `asd`; its `assd` is the symmetric one), hd95 = the
 95th percentile of both directions' distances pooled.  **Parity unpinned** (no medpy run to compare with); pinned instead to an
 independent brute-force surface-distance oracle on small masks (oracle/metrics_cpu.py, tests/test_validate_cpu.py).
+
+`metrics="device"` (validate_epoch / validate / Validator) runs that host back half on the GPU instead (csrc/postprocess.hip):
+ops.postprocess_masks is `postprocess` bit for bit, ops.seg_metrics leaves per image the Dice counts, the two order statistics of
+the squared surface distances HD95 interpolates between and the ASD sum, and `device_metrics` finishes them in float64 as `dice` /
+`hd95` / `asd` do: Dice and HD95 are bitwise the host path's, ASD agrees within 1e-12 relative (a fixed-order fp64 sum where
+numpy's mean sums pairwise).  One device -> host copy per batch; both classes in one set of launches.  The default stays "host".
 """
 import numpy as np
 import torch
@@ -96,10 +102,94 @@ def surface_metrics(pred_mask, label):
     return hd95(p, r), asd(p, r)
 
 
-def validate_epoch(model, model_shape, model_oc, model_shape_oc, batches):
+# ---- the back half on the device ---------------------------------------------------------------------------------------
+_EMPTY_LABEL = "The second supplied array does not contain any binary object."
+
+
+def _check_metrics(metrics):
+    if metrics not in ("host", "device"):
+        raise ValueError("metrics must be 'host' or 'device', got %r" % (metrics,))
+
+
+def percentile95_position(n):
+    """numpy.percentile(a, 95) of n sorted float64 values restated (numpy/lib/_function_base_impl.py: q = 95 / float64(100); the
+    linear method's virtual index (n - 1) * q — _QuantileMethods["linear"], not the generic _compute_virtual_index, whose other
+    operation order rounds differently; then _get_indexes / _get_gamma): -> (rank_lo, rank_hi, gamma).  The device's
+    percentile_ranks computes the same ranks."""
+    q = np.true_divide(95, np.float64(100))
+    vi = (n - 1) * q
+    if vi >= n - 1:
+        prev, lo, hi = -1, n - 1, n - 1
+    elif vi < 0:
+        prev, lo, hi = 0, 0, 0
+    else:
+        prev = int(np.floor(vi))
+        lo, hi = prev, prev + 1
+    return lo, hi, vi - np.intp(prev)
+
+
+def hd95_from_order_stats(n, d2_lo, d2_hi):
+    """np.percentile(distances, 95) from the two order statistics of the n pooled squared distances: numpy's _lerp on
+    sqrt(d2) (what distance_transform_edt returns)."""
+    _, _, t = percentile95_position(n)
+    a, b = np.sqrt(np.float64(d2_lo)), np.sqrt(np.float64(d2_hi))
+    diff_b_a = b - a
+    r = a + diff_b_a * t
+    if t >= 0.5:
+        r = b - diff_b_a * (1 - t)
+    return float(r)
+
+
+def _finish_surface(r):
+    """(hd95, asd) from one record, with surface_metrics' conventions."""
+    if r[1] == 0:
+        return 100.0, 100.0
+    if r[2] == 0:
+        raise RuntimeError(_EMPTY_LABEL)
+    hd = hd95_from_order_stats(int(r[3] + r[4]), int(r[5]), int(r[6]))
+    asd_sum = np.int64(r[7]).view(np.float64)
+    return hd, float(asd_sum / np.float64(r[3]))
+
+
+def _finish_dice(r):
+    return (2 * float(r[0]) + 1.0) / (1.0 + float(r[1]) + float(r[2]))
+
+
+def _device_records(pred, pred_oc, label_od, label_oc, threshold=0.75):
+    """ops.seg_metrics of both classes in one set of launches -> host int64 [2B, 8]: disc images first, then cup."""
+    ts = (pred, pred_oc, label_od, label_oc)
+    if not torch.cuda.is_available() or not all(isinstance(t, torch.Tensor) and t.is_cuda for t in ts):
+        raise RuntimeError("metrics='device' needs the GPU and device tensors (predictions and labels); there is no CPU fallback")
+    masks = ops.postprocess_masks(torch.cat((pred, pred_oc), 0).contiguous(), threshold)
+    labels = torch.cat((label_od, label_oc), 0).to(torch.float32).contiguous()
+    return ops.seg_metrics(masks, labels).cpu().numpy()         # the one device -> host copy
+
+
+def device_metrics(pred, pred_oc, label_od, label_oc, threshold=0.75):
+    """Per-image {disc_dice, cup_dice, disc_hd, disc_asd, cup_hd, cup_asd} (lists, batch order) of one validation batch computed
+    on the GPU: pred / pred_oc [B,1,h,w] logits, label_od / label_oc [B,1,h,w] labels (nonzero = object), all device tensors.
+    Raises the host path's RuntimeError for an empty label under a non-empty prediction (cup before disc, image by image)."""
+    B = pred.shape[0]
+    rec = _device_records(pred, pred_oc, label_od, label_oc, threshold)
+    out = {k: [] for k in ("disc_dice", "cup_dice", "disc_hd", "disc_asd", "cup_hd", "cup_asd")}
+    for i in range(B):
+        out["disc_dice"].append(_finish_dice(rec[i]))
+        out["cup_dice"].append(_finish_dice(rec[B + i]))
+        hd, a = _finish_surface(rec[B + i])
+        out["cup_hd"].append(hd)
+        out["cup_asd"].append(a)
+        hd, a = _finish_surface(rec[i])
+        out["disc_hd"].append(hd)
+        out["disc_asd"].append(a)
+    return out
+
+
+def validate_epoch(model, model_shape, model_oc, model_shape_oc, batches, metrics="host"):
     """One pass of Trainer.validate's loop (Trainer.py:152-249) -> per-image means
     {cup_dice, disc_dice, cup_hd, disc_hd, cup_asd, disc_asd, n}.  batches: iterable of (image [B,3,H,W] device,
-    label_od [B,1,h,w], label_oc [B,1,h,w]).  Eval mode for the duration, the previous modes restored (Trainer.py:138-141,289-311)."""
+    label_od [B,1,h,w], label_oc [B,1,h,w]).  Eval mode for the duration, the previous modes restored (Trainer.py:138-141,289-311).
+    metrics="device": post-processing and metrics on the GPU (device_metrics; the labels must be device tensors)."""
+    _check_metrics(metrics)
     nets = [model, model_shape, model_oc, model_shape_oc]
     modes = [n.training for n in nets]
     for n in nets:
@@ -109,6 +199,13 @@ def validate_epoch(model, model_shape, model_oc, model_shape_oc, batches):
     try:
         for image, label_od, label_oc in batches:
             pred, pred_oc = predict_pair(model, model_shape, model_oc, model_shape_oc, image, label_od.shape[2:])
+            if metrics == "device":
+                m = device_metrics(pred, pred_oc, label_od, label_oc)
+                for i in range(pred.shape[0]):
+                    for k in ("disc_dice", "cup_dice", "cup_hd", "cup_asd", "disc_hd", "disc_asd"):
+                        acc[k] += m[k][i]
+                    total += 1
+                continue
             lod, loc = label_od.cpu().numpy(), label_oc.cpu().numpy()
             for i in range(pred.shape[0]):
                 post, post_oc = postprocess(pred[i])[0], postprocess(pred_oc[i])[0]
@@ -140,14 +237,18 @@ class Validator:
     Dice, anything else their mean), best_mean_dice / best_epoch, and on a new best the four-state_dict checkpoint (returned; saved
     with torch.save when `out_dir` is given, as checkpoint_<best_epoch>.pth.tar, with the score line appended to score.txt)."""
 
-    def __init__(self, objective="OD_OC", out_dir=None):
-        self.objective, self.out_dir = objective, out_dir
+    def __init__(self, objective="OD_OC", out_dir=None, metrics="host"):
+        _check_metrics(metrics)
+        self.objective, self.out_dir, self.metrics = objective, out_dir, metrics
         self.best_mean_dice, self.best_epoch = 0.0, -1
 
     def __call__(self, epoch, model, model_shape, model_oc, model_shape_oc, batches):
         """-> (is_best, cup_dice, cup_hd, cup_asd, disc_dice, disc_hd, disc_asd) on a new best, (0, 0, 0, 0, 0, 0, 0) otherwise —
         Trainer.validate's return values — plus `self.last` = the epoch's means and `self.checkpoint` = the dict just built."""
-        m = validate_epoch(model, model_shape, model_oc, model_shape_oc, batches)
+        if self.metrics == "host":
+            m = validate_epoch(model, model_shape, model_oc, model_shape_oc, batches)
+        else:
+            m = validate_epoch(model, model_shape, model_oc, model_shape_oc, batches, self.metrics)
         self.last = m
         mean_dice = m["disc_dice"] if self.objective == "OD" else m["cup_dice"] if self.objective == "OC" else \
             (m["cup_dice"] + m["disc_dice"]) / 2
@@ -164,9 +265,11 @@ class Validator:
         return 1, m["cup_dice"], m["cup_hd"], m["cup_asd"], m["disc_dice"], m["disc_hd"], m["disc_asd"]
 
 
-def validate(model, model_shape, model_oc, model_shape_oc, batches):
+def validate(model, model_shape, model_oc, model_shape_oc, batches, metrics="host"):
     """batches: iterable of (image [B,3,H,W] device, label_od [B,1,h,w], label_oc [B,1,h,w]) -> (mean cup Dice, mean disc Dice).
-    Puts the four networks in eval mode for the duration (Trainer.py:138-141) and restores the previous mode."""
+    Puts the four networks in eval mode for the duration (Trainer.py:138-141) and restores the previous mode.
+    metrics="device": post-processing and Dice on the GPU (the labels must be device tensors)."""
+    _check_metrics(metrics)
     nets = [model, model_shape, model_oc, model_shape_oc]
     modes = [n.training for n in nets]
     for n in nets:
@@ -175,6 +278,14 @@ def validate(model, model_shape, model_oc, model_shape_oc, batches):
     try:
         for image, label_od, label_oc in batches:
             pred, pred_oc = predict_pair(model, model_shape, model_oc, model_shape_oc, image, label_od.shape[2:])
+            if metrics == "device":
+                B = pred.shape[0]
+                rec = _device_records(pred, pred_oc, label_od, label_oc)
+                for i in range(B):
+                    disc += _finish_dice(rec[i])
+                    cup += _finish_dice(rec[B + i])
+                    total += 1
+                continue
             lod, loc = label_od.cpu().numpy(), label_oc.cpu().numpy()
             for i in range(pred.shape[0]):
                 disc += dice(postprocess(pred[i])[0], lod[i, 0])
