@@ -3,7 +3,8 @@
  * The reference (tonyckc/WT-PSE-code) has no FFI of its own: its boundary is the Python class surface of
  * algorithms.py / shape_networks.py, which wt-pse-code_amd/{algorithms,shape_networks}.py mirror.
  * This library sits directly below that surface.  Each entry point replaces the stock ATen dispatches the
- * reference reaches from the cited lines.
+ * reference reaches from the cited lines.  The library itself is compiled against this file: a definition that disagrees
+ * with its declaration here does not build.
  *
  * Conventions
  *   - extern "C", plain pointers and sizes; every pointer is DEVICE memory unless stated; tensors are NCHW fp32,

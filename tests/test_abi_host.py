@@ -1,15 +1,20 @@
-"""CPU-side checks of the boundary: the C-ABI library builds/loads and exports every symbol include/wtpse_hip.h
-declares (no compute call is made without a GPU); the drop-in modules expose the reference's names, signatures and
+"""CPU-side checks of the boundary: the C-ABI library builds/loads and exports exactly the symbols include/wtpse_hip.h
+declares, and a definition that drifts from its declaration does not compile (no compute call is made without a GPU); the drop-in modules expose the reference's names, signatures and
 state_dict keys; the product path fails loudly instead of falling back to the CPU."""
 import ctypes
 import inspect
 import os
+import re
+import shutil
+import subprocess
 
 import pytest
 import torch
 
 from test_oracle_golden import main_template, shape_template
 from oracle.wtpse_cpu import DEFAULT_HPARAMS as HP
+
+READELF = "/opt/rocm/lib/llvm/bin/llvm-readelf"
 
 
 def test_library_exports_every_declared_symbol():
@@ -22,6 +27,17 @@ def test_library_exports_every_declared_symbol():
     for name in protos:
         assert hasattr(dll, name), name
     assert set(lib().protos) == set(protos)
+    # both directions: what the library exports under the ABI's prefix is what the header declares (any return type), nothing else
+    text = re.sub(r"/\*.*?\*/", "", open(build.HEADER).read(), flags=re.S)
+    declared = set(re.findall(r"\b(wtpse_\w+)\s*\(", text))
+    assert set(protos) <= declared and len(declared) >= len(protos)
+    syms = subprocess.run([READELF, "--dyn-syms", "--wide", LIB_PATH], capture_output=True, text=True, check=True).stdout
+    exported = set()
+    for line in syms.splitlines():
+        f = line.split()
+        if len(f) == 8 and f[6] != "UND" and f[4] in ("GLOBAL", "WEAK") and f[7].startswith("wtpse_"):
+            exported.add(f[7].split("@")[0])
+    assert exported == declared, (sorted(exported - declared), sorted(declared - exported))
     fn = dll.wtpse_source_hash
     fn.restype = ctypes.c_char_p
     assert fn().decode() == build.source_hash() == build.built_hash()
@@ -47,6 +63,25 @@ def test_library_exports_every_declared_symbol():
     assert L.query("wtpse_wgrad_r_slabs", 32, 16, 16, 256, 256) >= 1
     # argument validation happens before any launch
     assert L.raw("wtpse_conv_fwd")(0, 16, 0, 0, 0, 0, 0, 0, 0, 0, 0, 16, 0, 1, 8, 8, 16, 3, 0, 0, 0, 0) == -1
+
+
+def test_drifted_declaration_does_not_compile(tmp_path):
+    """Every translation unit is compiled against include/wtpse_hip.h, so a definition and a declaration that disagree are a
+    compile error: here the header's copy declares wtpse_source_hash as returning int and abi.hip, which defines it, is checked
+    against that copy (the unchanged header passes the same command)."""
+    from wtpse_hip import build
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    cmd = [hipcc, "--offload-arch=gfx950", "-std=c++17", "-fsyntax-only", "-I", str(tmp_path), "-I", build.CSRC,
+           "-I", os.path.dirname(build.HEADER), os.path.join(build.CSRC, "abi.hip")]
+    text = open(build.HEADER).read()
+    (tmp_path / "wtpse_hip.h").write_text(text)
+    res = subprocess.run(cmd, capture_output=True, text=True)
+    assert res.returncode == 0, res.stderr
+    assert text.count("const char* wtpse_source_hash(void);") == 1
+    (tmp_path / "wtpse_hip.h").write_text(text.replace("const char* wtpse_source_hash(void);", "int wtpse_source_hash(void);"))
+    res = subprocess.run(cmd, capture_output=True, text=True)
+    assert res.returncode != 0
+    assert "wtpse_source_hash" in res.stderr
 
 
 def test_stale_library_is_refused(monkeypatch):

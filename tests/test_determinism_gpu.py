@@ -105,7 +105,7 @@ def test_eager_work_between_plan_replays():
             n.seed_noise(4321)
         ts = TrainStep(*nets, hp, dp=None, graph=graph)
         side = TrainStep(*other, hp, dp=None, graph=False)
-        ring0 = ops._TICKETS[dev][1] if dev in ops._TICKETS else 0
+        ring0 = ops._TICKETS[dev].next if dev in ops._TICKETS else 0
         preds = []
         for k in range(3):
             image, od, oc = make_batch(B, 64, 64, dev, seed=20 + k)
@@ -119,9 +119,9 @@ def test_eager_work_between_plan_replays():
             side.step(image, od, oc)
         torch.cuda.synchronize()
         if graph:
-            assert ts._ticket_scope.buf.data_ptr() != ops._TICKETS[dev][0].data_ptr()
+            assert ts._ticket_scope.buf.data_ptr() != ops._TICKETS[dev].buf.data_ptr()
             assert not bool(ts._ticket_scope.buf.any()), "a recorded launch left its tickets non-zero"
-        assert not bool(ops._TICKETS[dev][0].any()), "an eager launch left its tickets non-zero"
+        assert not bool(ops._TICKETS[dev].buf.any()), "an eager launch left its tickets non-zero"
         return [n.flat_params().clone() for n in nets], preds, ring0
 
     pe, qe, _ = run(False)

@@ -1,4 +1,5 @@
 // Build fingerprint of libwtpse_hip.so (see wtpse_hip/build.py::source_hash and include/wtpse_hip.h).
+#include "wtpse_hip.h"
 #ifndef WTPSE_SRC_HASH
 #define WTPSE_SRC_HASH "unstamped"
 #endif

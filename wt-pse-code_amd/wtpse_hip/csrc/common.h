@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <math.h>
+#include "wtpse_hip.h"   // the C ABI: every definition in csrc/ is compiled against its declaration
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -475,34 +476,4 @@ static inline BnfTail bnf_tail_none() {
 static inline void bnf_tail_geometry(BnfTail& t, int ntiles, int Cout, double count) {
   t.ntiles = ntiles; t.ngroups = bnb_tail_groups(ntiles); t.ctot = bnb_tail_ctot(Cout); t.t2_off = bnb_tail_t2off(ntiles, Cout);
   t.count = count;
-}
-
-// Folding the statistics inside the launch makes every workgroup live ~2.5 us longer (its partials must be visible before it takes
-// its ticket: store acknowledgement + one L2 atomic round trip).  Measured on the step (back to back, profiles/r03_*): with the
-// fold in every launch the convolutions took 2.4 ms more per step than the 346 finalize launches it replaced took (2.2 ms).  A CU
-// slot sees nWG / (256 x 2..3) workgroups in a row, so the hand-off wins where that is about one or less; beyond the threshold the
-// entry points launch the stand-alone finalize kernel themselves.
-#include <cstdlib>
-// (Round 6: with the fold's loads all in flight at once — tail_fold — the hand-off is cheaper than the stand-alone kernel up to the
-// 8192-workgroup launches of the step as well: 41.54 vs 41.66 ms per step, three alternations on one box; the threshold moves there.)
-static inline bool tail_in_launch(long long workgroups) {
-  static const long long max_wgs = [] { const char* e = getenv("WTPSE_TAIL_MAX_WGS"); return e ? atoll(e) : 8192ll; }();
-  return workgroups <= max_wgs;
-}
-extern "C" int wtpse_bn_finalize(const float* stats_partial, int nblk, int C, long long count, const float* gamma, const float* beta,
-                                 float* running_mean, float* running_var, long long* num_batches, float momentum, float eps,
-                                 float* scale_shift, float* save_mean, float* save_invstd, unsigned* act_amax, void* stream);
-extern "C" int wtpse_bn_bwd_finalize_coef(const float* stats_partial, int nblk, int C, long long count, const float* gamma,
-                                          const float* save_mean, const float* save_invstd, float* coef, float* dgamma,
-                                          float* dbeta, int accumulate, void* stream);
-// after a launch whose tails were switched off for size: the same results from the stand-alone kernels
-static inline int tail_after_launch(const BnbTail& tl, const BnfTail& fl, float* stats, int nblk, int Cout, int bn_c0, int bn_c1,
-                                    const float* bn_mean, long long count, void* stream) {
-  if (tl.tickets)
-    return wtpse_bn_bwd_finalize_coef(stats, nblk, bn_c1 - bn_c0, count, tl.gamma, bn_mean, tl.invstd, tl.coef, tl.dgamma, tl.dbeta,
-                                      tl.accumulate, stream);
-  if (fl.tickets)
-    return wtpse_bn_finalize(stats, nblk, Cout, count, fl.gamma, fl.beta, fl.rmean, fl.rvar, fl.nbt, fl.momentum, fl.eps,
-                             fl.scale_shift, fl.save_mean, fl.save_invstd, fl.act_amax, stream);
-  return 0;
 }

@@ -24,7 +24,7 @@
 //   epilogue : + bias, ReLU, per-channel (sum, sum of squares) partials for train-mode BatchNorm statistics,
 //              channel split of the result into two tensors (data gradient of a concat)
 // The data gradient is the same kernel run on dY with tap-flipped, transposed weights (see pack kernel).
-#include "common.h"
+#include "internal.h"
 
 // Input channels per LDS chunk on the 16-cout path.  These layers (16 -> 16 at full resolution, the 1x1 heads) are bound by
 // load latency, not by the matrix pipe: small chunks (4 channels for 3x3, 8 for 1x1 instead of 16) cut LDS and staging
@@ -694,27 +694,36 @@ static int launch_fwd(const ConvArgs& a, hipStream_t st) {
   return rc;
 }
 
-static int fwd_tiles(int B, int H, int W) {
-  const int TW = W <= 16 ? 16 : 32, TH = 256 / TW;
-  return B * ceil_div(W, TW) * ceil_div(H, TH);
-}
-
 extern "C" int wtpse_conv_stats_blocks(int B, int H, int W) {
   const int TW = W <= 16 ? 16 : 32, TH = 256 / TW;
   return B * ceil_div(W, TW) * ceil_div(H, TH);
 }
 
-struct BnbArgs {   // EPI 2 parameters of conv_fwd_impl (all null / 0: none)
+struct BnbArgs {   // EPI 2 parameters (all null / 0: none); conv16_x3_impl covers all output channels and ignores c0, c1
   const float* ss;
   const float* mean;
   int relu, c0, c1;
 };
 
+struct ConvExtras {   // what only some entry points pass to conv_fwd_impl / conv16_x3_impl; the defaults mean "none"
+  BnbArgs bn = {nullptr, nullptr, 0, 0, 0};
+  BnbTail tail = bnb_tail_none();
+  BnfTail ftail = bnf_tail_none();
+  unsigned* out_amax = nullptr;
+};
+
+// preconditions of the in-launch tails, shared by both implementations
+static bool tails_ok(const BnbTail& tail, const BnfTail& ftail, bool bnb, const float* stats, const float* gram) {
+  return (!tail.tickets || (bnb && tail.partial2 && tail.gamma && tail.invstd && tail.coef && tail.dgamma && tail.dbeta)) &&
+         (!ftail.tickets || (!bnb && stats && !gram && ftail.partial2 && ftail.gamma && ftail.beta && ftail.scale_shift &&
+                             ftail.save_mean && ftail.save_invstd && (ftail.rmean == nullptr) == (ftail.rvar == nullptr)));
+}
+
 static int conv_fwd_impl(const float* in0, int C0, const float* in1, int C1, const float* wpacked, const float* bias,
                          const float* pro0, const float* pro1, int pro_relu, float* out0, float* out1, int Csplit, float* stats,
                          int B, int H, int W, int Cout, int ksize, int relu_out, const float* mask_ref, float* gram,
-                         void* stream, BnbArgs bn = BnbArgs{nullptr, nullptr, 0, 0, 0}, BnbTail tail = bnb_tail_none(),
-                         BnfTail ftail = bnf_tail_none(), unsigned* out_amax = nullptr) {
+                         void* stream, const ConvExtras& ex = ConvExtras()) {
+  const BnbArgs& bn = ex.bn; unsigned* const out_amax = ex.out_amax;
   WTPSE_REQUIRE(in0 && wpacked && out0 && B > 0 && H > 0 && W > 0 && C0 > 0 && C1 >= 0 && Cout > 0);
   WTPSE_REQUIRE(ksize == 1 || ksize == 3);
   WTPSE_REQUIRE((C1 == 0) == (in1 == nullptr));
@@ -728,12 +737,10 @@ static int conv_fwd_impl(const float* in0, int C0, const float* in1, int C1, con
                          bn.c0 % 16 == 0 && (bn.c1 % 16 == 0 || bn.c1 == Cout)));
   WTPSE_REQUIRE(C1 == 0 || C0 % 16 == 0);   // a channel chunk must not straddle the two inputs
   WTPSE_REQUIRE(!(out_amax && (mask_ref || bnb)));
-  WTPSE_REQUIRE(!tail.tickets || (bnb && tail.partial2 && tail.gamma && tail.invstd && tail.coef && tail.dgamma && tail.dbeta));
-  WTPSE_REQUIRE(!ftail.tickets || (!bnb && stats && !gram && ftail.partial2 && ftail.gamma && ftail.beta && ftail.scale_shift &&
-                                   ftail.save_mean && ftail.save_invstd && (ftail.rmean == nullptr) == (ftail.rvar == nullptr)));
+  WTPSE_REQUIRE(tails_ok(ex.tail, ex.ftail, bnb, stats, gram));
   ConvArgs a;
-  a.tail = tail;
-  a.ftail = ftail;
+  a.tail = ex.tail;
+  a.ftail = ex.ftail;
   a.bn_ss = bn.ss; a.bn_mean = bn.mean; a.bn_relu = bn.relu; a.bn_c0 = bnb ? bn.c0 : 0; a.bn_c1 = bnb ? bn.c1 : 0;
   a.in0 = in0; a.in1 = in1; a.wp = wpacked; a.bias = bias; a.pro0 = pro0; a.pro1 = pro1; a.out0 = out0; a.out1 = out1; a.stats = stats; a.mask = mask_ref; a.gram = gram;
   a.in_amax = nullptr; a.in_scale = 1.f; a.out_amax = out_amax;
@@ -744,7 +751,7 @@ static int conv_fwd_impl(const float* in0, int C0, const float* in1, int C1, con
   int mode = Cout <= 16 ? 0 : (Cout % 64 == 0 ? 2 : 1);  // ragged channel counts run on the 32-wide path
   // Grids that cannot give every CU ~3 workgroups (the 16x16 / 32x32 levels): halve the cout block to double the
   // workgroup count, and overlap each workgroup's own loads with its MFMAs (register double-buffering)
-  const int tiles = fwd_tiles(B, H, W);
+  const int tiles = wtpse_conv_stats_blocks(B, H, W);
   if (mode == 2 && tiles * (a.CoutP / 64) < 512) mode = 1;
   if (mode == 1 && tiles * ceil_div(a.CoutP, 32) < 384) mode = 0;   // still under two workgroups per CU: 16-cout blocks
   const int cb = mode == 0 ? 16 : 32 * mode;
@@ -768,8 +775,9 @@ extern "C" int wtpse_conv_fwd(const float* in0, int C0, const float* in1, int C1
                               const float* bias, const float* pro0, const float* pro1, int pro_relu, float* out0, float* out1,
                               int Csplit, float* stats, int B, int H, int W, int Cout, int ksize, int relu_out,
                               const float* mask_ref, unsigned* out_amax, void* stream) {
+  ConvExtras ex; ex.out_amax = out_amax;
   return conv_fwd_impl(in0, C0, in1, C1, wpacked, bias, pro0, pro1, pro_relu, out0, out1, Csplit, stats, B, H, W, Cout, ksize,
-                       relu_out, mask_ref, nullptr, stream, BnbArgs{nullptr, nullptr, 0, 0, 0}, bnb_tail_none(), bnf_tail_none(), out_amax);
+                       relu_out, mask_ref, nullptr, stream, ex);
 }
 
 // Data gradient that also performs the first half of the BatchNorm backward of the layer it flows into (include/wtpse_hip.h).
@@ -777,43 +785,41 @@ extern "C" int wtpse_dgrad_bnb(const float* dy, int C, const float* wpacked, flo
                                const float* bn_y, const float* bn_ss, const float* bn_mean, int bn_relu, int bn_c0, int bn_c1,
                                float* stats, int B, int H, int W, int Cout, int ksize, void* stream) {
   WTPSE_REQUIRE(bn_y && bn_ss && bn_mean && stats);
+  ConvExtras ex; ex.bn = BnbArgs{bn_ss, bn_mean, bn_relu, bn_c0, bn_c1};
   return conv_fwd_impl(dy, C, nullptr, 0, wpacked, nullptr, nullptr, nullptr, 0, out0, out1, Csplit, stats, B, H, W, Cout, ksize, 0,
-                       bn_y, nullptr, stream, BnbArgs{bn_ss, bn_mean, bn_relu, bn_c0, bn_c1});
+                       bn_y, nullptr, stream, ex);
 }
 
 // ---- the 16-channel 3x3 layers in the x3 arithmetic (MODE 3): Cout <= 16, Cin <= 16, one input tensor.  wx16: the layer's
 // fragments from wtpse_pack_conv16_x3.  Everything optional: bias, prologue, ReLU, BatchNorm (sum, sum^2) partials `stats`,
-// Gram partials `gram_partial` (Cout == 16), ReLU mask `mask_ref`, or — with bn_mean — the BatchNorm-backward epilogue of
+// Gram partials `gram_partial` (Cout == 16), ReLU mask `mask_ref`, or — with ex.bn.mean — the BatchNorm-backward epilogue of
 // wtpse_dgrad_bnb over all output channels (mask_ref = that layer's raw conv output).
 // Arithmetic: wtpse_x3_terms() == 2 -> x2h (MODE 4), unless the input is a GRADIENT (in_is_grad) whose amax table is not given — a
 // gradient has no scale known a priori, and an extra pass to find it costs more than this HBM-bound kernel gains: those launches stay
 // on x3 (the packed fragments carry both formats).
-extern int g_x3_terms;      // conv_x3.hip
 static int conv16_x3_impl(const float* in0, int C0, const unsigned short* wx16, const float* bias, const float* pro0,
-                          int pro_relu, float* out0, float* stats, float* gram_partial, const float* mask_ref,
-                          const float* bn_ss, const float* bn_mean, int bn_relu, int B, int H, int W, int Cout, int relu_out,
-                          int in_is_grad, const unsigned* in_amax, void* stream, BnbTail tail = bnb_tail_none(),
-                          BnfTail ftail = bnf_tail_none(), unsigned* out_amax = nullptr) {
+                          int pro_relu, float* out0, float* stats, float* gram_partial, const float* mask_ref, int B, int H,
+                          int W, int Cout, int relu_out, int in_is_grad, const unsigned* in_amax, void* stream,
+                          const ConvExtras& ex = ConvExtras()) {
+  const float* const bn_ss = ex.bn.ss; const float* const bn_mean = ex.bn.mean;
   WTPSE_REQUIRE(in0 && wx16 && out0 && B > 0 && H > 0 && W > 0 && C0 > 0 && C0 <= 16 && Cout > 0 && Cout <= 16);
   WTPSE_REQUIRE(!(stats && relu_out) && !(gram_partial && (Cout != 16 || relu_out)));
   WTPSE_REQUIRE((((uintptr_t)wx16) & 15) == 0);
   const bool bnb = bn_mean != nullptr;
   WTPSE_REQUIRE(bnb || !(stats && mask_ref));
   WTPSE_REQUIRE(!bnb || (mask_ref && stats && bn_ss && !bias && !relu_out && !gram_partial));
-  WTPSE_REQUIRE(!(out_amax && (mask_ref || bnb)));
-  WTPSE_REQUIRE(!tail.tickets || (bnb && tail.partial2 && tail.gamma && tail.invstd && tail.coef && tail.dgamma && tail.dbeta));
-  WTPSE_REQUIRE(!ftail.tickets || (!bnb && stats && !gram_partial && ftail.partial2 && ftail.gamma && ftail.beta && ftail.scale_shift &&
-                                   ftail.save_mean && ftail.save_invstd && (ftail.rmean == nullptr) == (ftail.rvar == nullptr)));
+  WTPSE_REQUIRE(!(ex.out_amax && (mask_ref || bnb)));
+  WTPSE_REQUIRE(tails_ok(ex.tail, ex.ftail, bnb, stats, gram_partial));
   ConvArgs a;
-  a.tail = tail;
-  a.ftail = ftail;
+  a.tail = ex.tail;
+  a.ftail = ex.ftail;
   a.in0 = in0; a.in1 = nullptr; a.wp = reinterpret_cast<const float*>(wx16); a.bias = bias; a.pro0 = pro0; a.pro1 = nullptr;
   a.out0 = out0; a.out1 = nullptr; a.stats = stats; a.mask = mask_ref; a.gram = gram_partial;
-  a.bn_ss = bn_ss; a.bn_mean = bn_mean; a.bn_relu = bn_relu; a.bn_c0 = 0; a.bn_c1 = bnb ? Cout : 0;
+  a.bn_ss = bn_ss; a.bn_mean = bn_mean; a.bn_relu = ex.bn.relu; a.bn_c0 = 0; a.bn_c1 = bnb ? Cout : 0;
   a.B = B; a.H = H; a.W = W; a.C0 = C0; a.C1 = 0; a.Cin = C0; a.CinP = 16;
   a.Cout = Cout; a.CoutP = 16; a.Csplit = Cout; a.pro_relu = pro_relu; a.relu_out = relu_out;
   a.tiles_x = a.tiles_y = 0;
-  a.in_amax = in_amax; a.in_scale = X3_FWD_SCALE; a.out_amax = out_amax;
+  a.in_amax = in_amax; a.in_scale = X3_FWD_SCALE; a.out_amax = ex.out_amax;
   hipStream_t st = (hipStream_t)stream;
   if (g_x3_terms == 2 && (!in_is_grad || in_amax)) {
     if (bnb) return launch_fwd<3, 4, false, 2>(a, st);
@@ -829,23 +835,14 @@ extern "C" int wtpse_conv16_x3(const float* in0, int C0, const unsigned short* w
                                int pro_relu, float* out0, float* stats, float* gram_partial, const float* mask_ref,
                                const float* bn_ss, const float* bn_mean, int bn_relu, int B, int H, int W, int Cout, int relu_out,
                                int in_is_grad, const unsigned* in_amax, unsigned* out_amax, void* stream) {
-  return conv16_x3_impl(in0, C0, wx16, bias, pro0, pro_relu, out0, stats, gram_partial, mask_ref, bn_ss, bn_mean, bn_relu, B, H, W,
-                        Cout, relu_out, in_is_grad, in_amax, stream, bnb_tail_none(), bnf_tail_none(), out_amax);
+  ConvExtras ex; ex.bn = BnbArgs{bn_ss, bn_mean, bn_relu, 0, 0}; ex.out_amax = out_amax;
+  return conv16_x3_impl(in0, C0, wx16, bias, pro0, pro_relu, out0, stats, gram_partial, mask_ref, B, H, W, Cout, relu_out,
+                        in_is_grad, in_amax, stream, ex);
 }
 
 // ---- wtpse_dgrad_bnb / wtpse_dgrad_x3_bnb / wtpse_conv16_x3(bn_mean) whose launch ALSO finishes the statistics: the last
 // workgroups fold the partials (common.h: bnb_tail) and leave (k1, k2, k3) in `coef`, dgamma / dbeta (+)= in place, so that the
 // BatchNorm backward is this launch + wtpse_bn_bwd_apply_coef.  layout: 0 fp32 (`wd`), 1 x3, 2 the 16-channel x3 fragments.
-extern "C" int wtpse_dgrad_x3_bnb_tail(const float* dy, int C, const unsigned short* wpacked, float* out0, float* out1, int Csplit,
-                                       const float* bn_y, const float* bn_ss, const float* bn_mean, int bn_relu, int bn_c0,
-                                       int bn_c1, float* stats, const BnbTail* tail, int B, int H, int W, int Cout, int ksize,
-                                       const unsigned* in_amax, void* stream);
-
-extern "C" int wtpse_conv_fwd_x3_ftail(const float* in0, int C0, const float* in1, int C1, const unsigned short* wpacked,
-                                       const float* bias, const float* pro0, const float* pro1, int pro_relu, float* out0,
-                                       float* stats, const BnfTail* ftail, int B, int H, int W, int Cout, int ksize,
-                                       const unsigned* in_amax0, const unsigned* in_amax1, void* stream);
-
 // ---- a forward convolution in front of a train-mode BatchNorm whose launch ALSO finishes the statistics (common.h: bnf_tail):
 // wtpse_conv_fwd / wtpse_conv_fwd_x3 / wtpse_conv16_x3 with `stats` + wtpse_bn_finalize in one launch.  layout as below.
 extern "C" int wtpse_conv_fwd_bnf(const float* in0, int C0, const float* in1, int C1, const void* wpacked, int layout,
@@ -856,20 +853,21 @@ extern "C" int wtpse_conv_fwd_bnf(const float* in0, int C0, const float* in1, in
                                   const unsigned* in_amax0, const unsigned* in_amax1, unsigned* act_amax, void* stream) {
   WTPSE_REQUIRE(stats && gamma && beta && scale_shift && save_mean && save_invstd && partial2 && tickets);
   WTPSE_REQUIRE(layout >= 0 && layout <= 2);
-  BnfTail t = bnf_tail_none();
+  ConvExtras ex;
+  BnfTail& t = ex.ftail;
   t.partial2 = partial2; t.tickets = tickets; t.gamma = gamma; t.beta = beta; t.rmean = running_mean; t.rvar = running_var;
   t.nbt = num_batches; t.momentum = momentum; t.eps = eps; t.scale_shift = scale_shift; t.save_mean = save_mean;
   t.save_invstd = save_invstd; t.act_amax = act_amax;
   if (layout == 1)
-    return wtpse_conv_fwd_x3_ftail(in0, C0, in1, C1, static_cast<const unsigned short*>(wpacked), bias, pro0, pro1, pro_relu, out0,
-                                   stats, &t, B, H, W, Cout, ksize, in_amax0, in_amax1, stream);
+    return conv_fwd_x3_ftail(in0, C0, in1, C1, static_cast<const unsigned short*>(wpacked), bias, pro0, pro1, pro_relu, out0,
+                             stats, &t, B, H, W, Cout, ksize, in_amax0, in_amax1, stream);
   if (layout == 2) {
     WTPSE_REQUIRE(ksize == 3 && !in1 && C1 == 0 && !pro1);
     return conv16_x3_impl(in0, C0, static_cast<const unsigned short*>(wpacked), bias, pro0, pro_relu, out0, stats, nullptr, nullptr,
-                          nullptr, nullptr, 0, B, H, W, Cout, 0, 0, in_amax0, stream, bnb_tail_none(), t);
+                          B, H, W, Cout, 0, 0, in_amax0, stream, ex);
   }
   return conv_fwd_impl(in0, C0, in1, C1, static_cast<const float*>(wpacked), bias, pro0, pro1, pro_relu, out0, nullptr, Cout, stats,
-                       B, H, W, Cout, ksize, 0, nullptr, nullptr, stream, BnbArgs{nullptr, nullptr, 0, 0, 0}, bnb_tail_none(), t);
+                       B, H, W, Cout, ksize, 0, nullptr, nullptr, stream, ex);
 }
 
 extern "C" int wtpse_bnb_tail_partial2(int nblk, int Cout) { return bnb_tail_groups(nblk) * bnb_tail_ctot(Cout) * 2; }
@@ -882,19 +880,20 @@ extern "C" int wtpse_dgrad_bnb_coef(const float* dy, int C, const void* wpacked,
                                     int Cout, int ksize, const unsigned* in_amax, void* stream) {
   WTPSE_REQUIRE(bn_y && bn_ss && bn_mean && stats && gamma && invstd && coef && dgamma && dbeta && partial2 && tickets);
   WTPSE_REQUIRE(layout >= 0 && layout <= 2);
-  BnbTail t = bnb_tail_none();
+  ConvExtras ex; ex.bn = BnbArgs{bn_ss, bn_mean, bn_relu, bn_c0, bn_c1};
+  BnbTail& t = ex.tail;
   t.partial2 = partial2; t.tickets = tickets; t.gamma = gamma; t.invstd = invstd; t.coef = coef; t.dgamma = dgamma; t.dbeta = dbeta;
   t.accumulate = accumulate;
   if (layout == 1)
-    return wtpse_dgrad_x3_bnb_tail(dy, C, static_cast<const unsigned short*>(wpacked), out0, out1, Csplit, bn_y, bn_ss, bn_mean,
-                                   bn_relu, bn_c0, bn_c1, stats, &t, B, H, W, Cout, ksize, in_amax, stream);
+    return dgrad_x3_bnb_tail(dy, C, static_cast<const unsigned short*>(wpacked), out0, out1, Csplit, bn_y, bn_ss, bn_mean,
+                             bn_relu, bn_c0, bn_c1, stats, &t, B, H, W, Cout, ksize, in_amax, stream);
   if (layout == 2) {
     WTPSE_REQUIRE(ksize == 3 && !out1 && Csplit == Cout && bn_c0 == 0 && bn_c1 == Cout);
-    return conv16_x3_impl(dy, C, static_cast<const unsigned short*>(wpacked), nullptr, nullptr, 0, out0, stats, nullptr, bn_y, bn_ss,
-                          bn_mean, bn_relu, B, H, W, Cout, 0, 1, in_amax, stream, t);
+    return conv16_x3_impl(dy, C, static_cast<const unsigned short*>(wpacked), nullptr, nullptr, 0, out0, stats, nullptr, bn_y, B, H, W,
+                          Cout, 0, 1, in_amax, stream, ex);
   }
   return conv_fwd_impl(dy, C, nullptr, 0, static_cast<const float*>(wpacked), nullptr, nullptr, nullptr, 0, out0, out1, Csplit, stats,
-                       B, H, W, Cout, ksize, 0, bn_y, nullptr, stream, BnbArgs{bn_ss, bn_mean, bn_relu, bn_c0, bn_c1}, t);
+                       B, H, W, Cout, ksize, 0, bn_y, nullptr, stream, ex);
 }
 
 // Weight fragments of the 16-channel x3 / x2h path, all convs of a network in one launch.  desc: n_desc x 8 ints {w_off, Cout, Cin,
@@ -959,8 +958,9 @@ extern "C" int wtpse_conv_fwd_gram(const float* in0, int C0, const float* wpacke
                                    unsigned* out_amax, void* stream) {
   WTPSE_REQUIRE(gram_partial && Cout == 16);
   WTPSE_REQUIRE(!relu_out);     // the Gram epilogue works on the accumulators before the ReLU clamp: it describes the stored map only without one
+  ConvExtras ex; ex.out_amax = out_amax;
   return conv_fwd_impl(in0, C0, nullptr, 0, wpacked, bias, pro0, nullptr, pro_relu, out0, nullptr, Cout, nullptr, B, H, W, Cout, 3,
-                       relu_out, nullptr, gram_partial, stream, BnbArgs{nullptr, nullptr, 0, 0, 0}, bnb_tail_none(), bnf_tail_none(), out_amax);
+                       relu_out, nullptr, gram_partial, stream, ex);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1303,7 +1303,7 @@ __global__ __launch_bounds__(256) void wgrad_fold4_k(const float* __restrict__ s
 }
 
 // fold of the k-split slabs for other translation units (conv_x3.hip)
-extern "C" void wtpse_wgrad_reduce_launch(const float* slab, int ksplit, int n, float* dw, int accumulate, void* stream) {
+void wgrad_reduce_launch(const float* slab, int ksplit, int n, float* dw, int accumulate, void* stream) {
   if (n % 4 == 0)
     hipLaunchKernelGGL(wgrad_fold4_k, dim3(ceil_div(n, 128)), dim3(256), 0, (hipStream_t)stream, slab, ksplit, n, dw, accumulate);
   else
@@ -1312,10 +1312,10 @@ extern "C" void wtpse_wgrad_reduce_launch(const float* slab, int ksplit, int n, 
 }
 
 // the same with the bias-gradient slabs folded in the same launch (wgrad_r.hip)
-extern "C" void wtpse_wgrad_reduce_launch2(const float* slab, int ksplit, int n, float* dw, int accumulate, const float* slab_b,
-                                           int n_b, float* db, void* stream) {
+void wgrad_reduce_launch2(const float* slab, int ksplit, int n, float* dw, int accumulate, const float* slab_b, int n_b,
+                          float* db, void* stream) {
   if (!db) {
-    wtpse_wgrad_reduce_launch(slab, ksplit, n, dw, accumulate, stream);
+    wgrad_reduce_launch(slab, ksplit, n, dw, accumulate, stream);
     return;
   }
   const int nblk_w = ceil_div(n, 32), nblk_b = ceil_div(n_b, 32);

@@ -251,20 +251,18 @@ extern "C" int wtpse_dgrad_x3_bnb(const float* dy, int C, const unsigned short* 
 }
 
 // wtpse_conv_fwd_bnf (conv.hip), x3 layout
-extern "C" int wtpse_conv_fwd_x3_ftail(const float* in0, int C0, const float* in1, int C1, const unsigned short* wpacked,
-                                       const float* bias, const float* pro0, const float* pro1, int pro_relu, float* out0,
-                                       float* stats, const BnfTail* ftail, int B, int H, int W, int Cout, int ksize,
-                                       const unsigned* in_amax0, const unsigned* in_amax1, void* stream) {
+int conv_fwd_x3_ftail(const float* in0, int C0, const float* in1, int C1, const unsigned short* wpacked, const float* bias,
+                      const float* pro0, const float* pro1, int pro_relu, float* out0, float* stats, const BnfTail* ftail, int B,
+                      int H, int W, int Cout, int ksize, const unsigned* in_amax0, const unsigned* in_amax1, void* stream) {
   WTPSE_REQUIRE(ftail && stats);
   return conv_x3_impl(in0, C0, in1, C1, wpacked, bias, pro0, pro1, pro_relu, out0, nullptr, Cout, stats, B, H, W, Cout, ksize, 0,
                       nullptr, nullptr, nullptr, 0, 0, 0, in_amax0, stream, bnb_tail_none(), *ftail, in_amax1);
 }
 
 // wtpse_dgrad_bnb_coef (conv.hip), x3 layout
-extern "C" int wtpse_dgrad_x3_bnb_tail(const float* dy, int C, const unsigned short* wpacked, float* out0, float* out1, int Csplit,
-                                       const float* bn_y, const float* bn_ss, const float* bn_mean, int bn_relu, int bn_c0,
-                                       int bn_c1, float* stats, const BnbTail* tail, int B, int H, int W, int Cout, int ksize,
-                                       const unsigned* in_amax, void* stream) {
+int dgrad_x3_bnb_tail(const float* dy, int C, const unsigned short* wpacked, float* out0, float* out1, int Csplit,
+                      const float* bn_y, const float* bn_ss, const float* bn_mean, int bn_relu, int bn_c0, int bn_c1, float* stats,
+                      const BnbTail* tail, int B, int H, int W, int Cout, int ksize, const unsigned* in_amax, void* stream) {
   WTPSE_REQUIRE(bn_y && bn_ss && bn_mean && stats && tail);
   return conv_x3_impl(dy, C, nullptr, 0, wpacked, nullptr, nullptr, nullptr, 0, out0, out1, Csplit, stats, B, H, W, Cout, ksize, 0,
                       bn_y, bn_ss, bn_mean, bn_relu, bn_c0, bn_c1, in_amax, stream, *tail);
@@ -561,8 +559,6 @@ extern "C" int wtpse_wgrad_x3_ksplit(int B, int H, int W, int Cin, int Cout) {
   return ks;
 }
 
-extern "C" void wtpse_wgrad_reduce_launch(const float* slab, int ksplit, int n, float* dw, int accumulate, void* stream);
-
 // Same contract as wtpse_conv_wgrad (include/wtpse_hip.h) without the bias gradient; requires wtpse_wgrad_x3_supported().
 extern "C" int wtpse_conv_wgrad_x3(const float* dy, const float* x0, int C0, const float* x1, int C1, const float* pro0,
                                    const float* pro1, int pro_relu, float* slab, int ksplit, float* dw, int accumulate, int B,
@@ -594,6 +590,6 @@ extern "C" int wtpse_conv_wgrad_x3(const float* dy, const float* x0, int C0, con
   }
   int rc = wtpse_status();
   if (rc) return rc;
-  wtpse_wgrad_reduce_launch(slab, ksplit, Cout * Cin * 9, dw, accumulate, stream);
+  wgrad_reduce_launch(slab, ksplit, Cout * Cin * 9, dw, accumulate, stream);
   return wtpse_status();
 }

@@ -21,7 +21,7 @@
 //     Ws[tap 3][term 3][k-half 2][cout CB][8 cin]     one kernel row of the weights (pre-split by the pack kernel)
 
 #include <stdlib.h>
-#include "common.h"
+#include "internal.h"
 #include <utility>
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));

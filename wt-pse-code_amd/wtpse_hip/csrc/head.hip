@@ -12,7 +12,7 @@
 // The weight gradients contract over pixels, which sit on lanes: the backward kernel transposes its four operands
 // (dh1, x, h1, dh2) through a wave-private LDS tile [32 rows][33] per 32-pixel block and keeps dW1 / dW2 in MFMA
 // accumulators over all the blocks a wave owns; per-workgroup slabs are folded in fp64 in a fixed order.
-#include "common.h"
+#include "internal.h"
 
 __device__ __forceinline__ int rho(int r, int u) { return (r & 3) + 8 * (r >> 2) + 4 * u; }
 typedef unsigned int u32x4v __attribute__((ext_vector_type(4)));
@@ -22,8 +22,6 @@ __device__ __forceinline__ float relu_keep_nan(float v) { return v < 0.f ? 0.f :
 __device__ __forceinline__ f32x16 mfma32h(u32x4v a, u32x4v b, f32x16 c) {      // 32x32x16, fp16 operands, fp32 accumulation
   return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h16x8, a), __builtin_bit_cast(h16x8, b), c, 0, 0, 0);
 }
-
-extern int g_x3_terms;      // conv_x3.hip: wtpse_x3_terms() — 2 (x2h, the default): the heads run on the fp16 matrix cores too
 
 struct HeadArgs {
   const float* x;      // [B][32][HW] head input as stored

@@ -17,7 +17,7 @@ union PlanArg {
   double d;
 };
 
-#include "_plan_thunks.inc"   // extern "C" prototypes, thunk_<k>(const PlanArg*, void* stream), PLAN_FN_NAMES[], PLAN_THUNKS[], PLAN_NFN
+#include "_plan_thunks.inc"   // thunk_<k>(const PlanArg*, void* stream), PLAN_FN_NAMES[], PLAN_THUNKS[], PLAN_NFN
 
 namespace {
 struct Cmd {
@@ -33,8 +33,6 @@ struct Plan {
   int tuning;          // wtpse_tuning_state() when the plan was created: the recorded calls were sized for this tiling / weight format
 };
 }  // namespace
-
-extern "C" int wtpse_tuning_state(void);      // conv_x3.hip
 
 extern "C" int wtpse_plan_fn_count(void) { return PLAN_NFN; }
 extern "C" const char* wtpse_plan_fn_name(int id) { return (id >= 0 && id < PLAN_NFN) ? PLAN_FN_NAMES[id] : ""; }

@@ -774,7 +774,6 @@ extern "C" int wtpse_upsample2x_fwd_stats(const float* x, float* out, float* sta
 // amax (optional): the amax table (common.h) of dx, ZERO on entry — dx is the dY of the 1x1 convolution in front of the upsampling
 // (every wave folds its maximum into a shard with one no-return atomic).
 static inline dim3 up_bwd_grid(int per_plane, int planes, bool) { return PLANE_GRID(per_plane, planes); }
-extern "C" int wtpse_amax(const float* x, long long n, unsigned* amax_table, void* stream);
 extern "C" int wtpse_upsample2x_bwd(const float* dout, float* dx, int accumulate, int B, int C, int H, int W, unsigned* amax, void* stream) {
   WTPSE_REQUIRE(dout && dx && B > 0 && C > 0 && H > 0 && W > 0);
   long long total = (long long)B * C * H * W;

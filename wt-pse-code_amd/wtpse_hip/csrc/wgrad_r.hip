@@ -21,7 +21,7 @@
 // Bias gradient (layers without BatchNorm): sum of the dY values the A fragments are made from, in the waves of cin block 0.
 #include <type_traits>
 #include <utility>
-#include "common.h"
+#include "internal.h"
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
@@ -565,10 +565,6 @@ extern "C" int wtpse_wgrad_r_slabs(int B, int H, int W, int Cin, int Cout) {
   return p.wpp / p.nw;
 }
 
-extern int g_x3_terms;      // conv_x3.hip: wtpse_x3_terms()
-extern "C" void wtpse_wgrad_reduce_launch2(const float* slab, int ksplit, int n, float* dw, int accumulate, const float* slab_b,
-                                           int n_b, float* db, void* stream);
-
 static int wgrad_r_impl(const float* dy, const float* x0, int C0, const float* x1, int C1, const float* pro0,
                         const float* pro1, int pro_relu, float* slab, float* dbias_slab, int nslab, float* dw,
                         float* dbias, int accumulate, int B, int H, int W, int Cout, const float* bn_y, const float* bn_coef,
@@ -645,7 +641,7 @@ static int wgrad_r_impl(const float* dy, const float* x0, int C0, const float* x
 #undef WR_LAUNCH1
   int rc = wtpse_status();
   if (rc) return rc;
-  wtpse_wgrad_reduce_launch2(slab, nslab, Cout * Cin * 9, dw, accumulate, dbias_slab, Cout, dbias, stream);
+  wgrad_reduce_launch2(slab, nslab, Cout * Cin * 9, dw, accumulate, dbias_slab, Cout, dbias, stream);
   return wtpse_status();
 }
 

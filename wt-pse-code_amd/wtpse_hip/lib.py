@@ -5,19 +5,12 @@ boundary.  There is no fallback: if the library is missing or a call fails, this
 """
 import ctypes
 import os
-import re
+
+from . import build
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libwtpse_hip.so")
 HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "include", "wtpse_hip.h"))
-
-_CTYPES = {
-    "int": ctypes.c_int,
-    "long long": ctypes.c_longlong,
-    "unsigned long long": ctypes.c_ulonglong,
-    "float": ctypes.c_float,
-    "double": ctypes.c_double,
-}
 
 
 class WtpseError(RuntimeError):
@@ -29,29 +22,13 @@ class PlanArg(ctypes.Union):
     _fields_ = [("p", ctypes.c_void_p), ("i", ctypes.c_longlong), ("u", ctypes.c_ulonglong), ("d", ctypes.c_double)]
 
 
-_SLOT = {ctypes.c_void_p: "p", ctypes.c_int: "i", ctypes.c_longlong: "i", ctypes.c_ulonglong: "u", ctypes.c_float: "d",
-         ctypes.c_double: "d"}
+_SLOT = {getattr(ctypes, c): field for c, field in build.C_TYPES.values()}
 
 
 def parse_header(path=HEADER_PATH):
-    """-> {name: [ctypes arg types]} for every `int wtpse_*(...)` declaration."""
-    text = open(path).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    protos = {}
-    for m in re.finditer(r"\bint\s+(wtpse_\w+)\s*\(([^)]*)\)\s*;", text):
-        name, args = m.group(1), m.group(2)
-        types = []
-        for a in args.split(","):
-            a = " ".join(a.split())
-            if not a or a == "void":
-                continue
-            if "*" in a:
-                types.append(ctypes.c_void_p)
-                continue
-            base = a.rsplit(" ", 1)[0].replace("const ", "").strip()
-            types.append(_CTYPES[base])
-        protos[name] = types
-    return protos
+    """-> {name: [ctypes arg types]} for every `int wtpse_*(...)` declaration (build.parse_prototypes: the one parser)."""
+    return {name: [getattr(ctypes, build.C_TYPES["void*" if "*" in t else t][0]) for t in types]
+            for name, types in build.parse_prototypes(path).items()}
 
 
 class _Lib:
@@ -71,7 +48,6 @@ class _Lib:
         self._dll = ctypes.CDLL(LIB_PATH)
         # a library built from other sources than the ones in the tree (stale .so after an edit, changed signature)
         # would be a silent ABI mismatch: only missing symbols are detected by the binding below
-        from . import build
         fn = getattr(self._dll, "wtpse_source_hash", None)
         have = None
         if fn is not None:

@@ -176,23 +176,12 @@ class HipNet(nn.Module):
     """Root of a parameter tree: owns the flat parameter / gradient / packed-weight buffers."""
 
     def _finish_init(self):
-        object.__setattr__(self, "_flat", None)
-        object.__setattr__(self, "_gflat", None)
-        object.__setattr__(self, "_gwork", None)
-        object.__setattr__(self, "_packed", None)
-        object.__setattr__(self, "_x3", None)
-        object.__setattr__(self, "_xdesc", None)
-        object.__setattr__(self, "_x16desc", None)
-        object.__setattr__(self, "_packed_version", -1)
-        object.__setattr__(self, "_desc", None)
-        object.__setattr__(self, "_touched", [])
-        object.__setattr__(self, "_noise_queue", [])
-        object.__setattr__(self, "_noise_seed", 0x5eed)
-        object.__setattr__(self, "_noise_ctr", None)
-        object.__setattr__(self, "_dp", None)
-        object.__setattr__(self, "_flag", None)
-        object.__setattr__(self, "_packed_valid", False)
-        object.__setattr__(self, "_attach_grads", True)
+        # (plain attributes, not registered with nn.Module; the step harness and the data-parallel workers set _dp, _packed_valid,
+        # _attach_grads and _defer_allreduce directly)
+        for name, value in dict(_flat=None, _gflat=None, _gwork=None, _packed=None, _x3=None, _xdesc=None, _x16desc=None, _desc=None,
+                                _packed_version=-1, _touched=[], _noise_queue=[], _noise_seed=0x5eed, _noise_ctr=None, _dp=None,
+                                _flag=None, _packed_valid=False, _attach_grads=True, _defer_allreduce=False, _join=[]).items():
+            object.__setattr__(self, name, value)
         self._convs = [m for m in self.modules() if isinstance(m, ConvP)]
         for m in self.modules():
             if isinstance(m, (ConvP, BNP, AttentionP, TeacherP, DeepWTP)):
@@ -281,20 +270,17 @@ class HipNet(nn.Module):
         object.__setattr__(self, "_gflat", torch.zeros(total, dtype=torch.float32, device=dev))
         object.__setattr__(self, "_gwork", None)
         object.__setattr__(self, "_packed", torch.empty(self._packed_size, dtype=torch.float32, device=dev))
-        desc = []
-        for c in self._convs:
-            desc += [self._offsets[self._pindex[id(c.weight)]], c.cout, c.cin, c.k * c.k, c.wf_off, c.wd_off, 0, 0]
-        object.__setattr__(self, "_desc", torch.tensor(desc, dtype=torch.int32).to(dev))
+
+        def table(convs, fwd, bwd):
+            """What the pack kernels take, 8 ints per conv: {w_off, Cout, Cin, taps, forward offset, data-gradient offset, 0, 0}."""
+            desc = [v for c in convs for v in (self.param_offset(c.weight), c.cout, c.cin, c.k * c.k, getattr(c, fwd), getattr(c, bwd), 0, 0)]
+            return torch.tensor(desc, dtype=torch.int32).to(dev) if desc else None
+
+        object.__setattr__(self, "_desc", table(self._convs, "wf_off", "wd_off"))
         object.__setattr__(self, "_packed_version", -1)
         object.__setattr__(self, "_x3", torch.empty(max(self._x3_size, 8), dtype=torch.int16, device=dev))
-        xdesc = []
-        for c in self._x3_convs:
-            xdesc += [self._offsets[self._pindex[id(c.weight)]], c.cout, c.cin, c.k * c.k, c.xf_off, c.xd_off, 0, 0]
-        object.__setattr__(self, "_xdesc", torch.tensor(xdesc, dtype=torch.int32).to(dev) if xdesc else None)
-        xdesc = []
-        for c in self._x16_convs:
-            xdesc += [self._offsets[self._pindex[id(c.weight)]], c.cout, c.cin, 9, c.x16f_off, c.x16d_off, 0, 0]
-        object.__setattr__(self, "_x16desc", torch.tensor(xdesc, dtype=torch.int32).to(dev) if xdesc else None)
+        object.__setattr__(self, "_xdesc", table(self._x3_convs, "xf_off", "xd_off"))
+        object.__setattr__(self, "_x16desc", table(self._x16_convs, "x16f_off", "x16d_off"))
         object.__setattr__(self, "_flag", torch.zeros(1, dtype=torch.int32, device=dev))
         ops._tickets(0, dev)          # the ticket ring of the self-folding data gradients: created outside any stream capture
         ops.amax_begin(dev)           # ... and the arena of the gradients' amax tables (x2h arithmetic)
@@ -345,6 +331,16 @@ class HipNet(nn.Module):
     def param_offset(self, p):
         return self._offsets[self._pindex[id(p)]]
 
+    def grange(self, first_param, n):
+        """The n floats of the current gradient target that start at first_param's gradient."""
+        off = self.param_offset(first_param)
+        return self._gtarget[off:off + n]
+
+    @property
+    def bn_synced(self):
+        """BatchNorm statistics are exchanged between the data-parallel ranks (dp.py): the launches that fold them alone are out."""
+        return self._dp is not None and self._dp.bn_sync
+
     # ---- gradients -----------------------------------------------------------------------------------------
     def begin_backward(self):
         """Choose the buffer this backward writes into: the attached flat gradient when every .grad is None
@@ -361,10 +357,8 @@ class HipNet(nn.Module):
 
     def gview(self, p):
         """View of the current gradient target for parameter p; marks p as reached by this backward."""
-        i = self._pindex[id(p)]
         self._touched.append(p)
-        off = self._offsets[i]
-        return self._gtarget[off:off + p.numel()]
+        return self.grange(p, p.numel())
 
     def grads_ready(self, first, last=None):
         """Data-parallel overlap: the parameter gradients of the consecutive submodules `first` .. `last` (a contiguous range of
@@ -381,8 +375,7 @@ class HipNet(nn.Module):
             return
         last = first if last is None else last
         pf, pl = next(first.parameters()), list(last.parameters())[-1]
-        lo = self._offsets[self._pindex[id(pf)]]
-        hi = self._offsets[self._pindex[id(pl)]] + pl.numel()
+        lo, hi = self.param_offset(pf), self.param_offset(pl) + pl.numel()
         cur = torch.cuda.current_stream()
         streams = [cur]
         side = _SIDE.get((self._gflat.device, ops.stream_ptr()))
@@ -391,21 +384,20 @@ class HipNet(nn.Module):
         dp.bucket_ready(self, self._gtarget, lo, hi, streams)
 
     def end_backward(self):
-        joins = self.__dict__.get("_join")
+        joins = self._join
         if joins:                                   # helper streams this backward put work on (weight gradients, prior chain)
             cur = torch.cuda.current_stream()
             for st in joins:
                 stream_wait(cur, st)
             joins.clear()
-        if self._dp is not None and not self.__dict__.get("_defer_allreduce"):     # the step harness issues it itself
+        if self._dp is not None and not self._defer_allreduce:     # the step harness issues it itself
             self._dp.allreduce_grads(self, self._gtarget)
         direct = self._gtarget is self._gflat
         if direct and not self._attach_grads:   # the step harness reads the flat buffer itself
             self._touched.clear()
             return
         for p in self._touched:
-            off = self._offsets[self._pindex[id(p)]]
-            g = self._gtarget[off:off + p.numel()].view(p.shape)
+            g = self.grange(p, p.numel()).view(p.shape)
             if direct:
                 p.grad = g
             elif p.grad is None:
@@ -471,6 +463,12 @@ class Act:
         return z
 
 
+    @staticmethod
+    def parts(a):
+        """(t, pro) of an optional second input."""
+        return (a.t, a.pro) if a is not None else (None, None)
+
+
 def as_act(x):
     return x if isinstance(x, Act) else Act(x)
 
@@ -513,25 +511,36 @@ def x3_eligible(k_dim, rows, ksize):
     return X3 and rows > 16 and 16 <= k_dim <= 256 and (ksize == 3 or k_dim >= 64)     # 256: wtpse_conv_fwd_x3 (include/wtpse_hip.h)
 
 
+def _weights(layer, dgrad=False, wide=False):
+    """Which packed layout a launch of `layer` runs on, and its weights there: -> (layout, device pointer), layout as the C ABI numbers
+    it (0 fp32-input MFMA, 1 x3, 2 the 16-channel x3 fragments).  dgrad: the data gradient instead of the forward launch; wide: the
+    launch has two inputs (forward) / a split output (data gradient), which the 16-channel kernels do not take."""
+    root = layer._root
+    x16, x3, w = (layer.x16d_off, layer.xd_off, layer.wd_off) if dgrad else (layer.x16f_off, layer.xf_off, layer.wf_off)
+    if x16 >= 0 and not wide:
+        return 2, root.x3_ptr(x16)
+    if x3 >= 0:
+        return 1, root.x3_ptr(x3)
+    return 0, root.packed_ptr(w)
+
+
 def _conv(layer, a0, a1=None, relu_out=False, want_stats=False, want_amax=False):
     """want_amax (x2h arithmetic): the launch also leaves the amax table of its output on the result (`y.wt_amax`) — for outputs
     that reach an x2h consumer without a train-mode BatchNorm in between (DeepWT's maps, the fusion conv, eval-mode BatchNorm)."""
-    root = layer._root
     a0 = as_act(a0)
     a1 = as_act(a1) if a1 is not None else None
+    t1, pro1 = Act.parts(a1)
     out_amax = ops.fwd_amax_table(a0.t.device) if want_amax else None
-    if layer.x16f_off >= 0 and a1 is None:
-        y, stats, _ = ops.conv16_x3(a0.t, root.x3_ptr(layer.x16f_off), layer.bias, layer.cout, a0.pro, _relu_bits(a0, None),
-                                    relu_out, want_stats, in_amax=act_amax(a0), out_amax=out_amax)
-        return y, stats
-    if layer.xf_off >= 0:
-        y, _, stats = ops.conv_fwd_x3(a0.t, a1.t if a1 is not None else None, root.x3_ptr(layer.xf_off), layer.bias, layer.cout,
-                                      layer.k, a0.pro, _relu_bits(a0, a1), relu_out, want_stats, None, None,
-                                      a1.pro if a1 is not None else None, act_amax(a0), act_amax(a1), out_amax)
-        return y, stats
-    y, _, stats = ops.conv_fwd(a0.t, a1.t if a1 is not None else None, root.packed_ptr(layer.wf_off), layer.bias, layer.cout,
-                               layer.k, a0.pro, _relu_bits(a0, a1), relu_out, want_stats, None, None,
-                               a1.pro if a1 is not None else None, out_amax)
+    layout, wptr = _weights(layer, wide=a1 is not None)
+    if layout == 2:
+        y, stats, _ = ops.conv16_x3(a0.t, wptr, layer.bias, layer.cout, a0.pro, _relu_bits(a0, None), relu_out, want_stats,
+                                    in_amax=act_amax(a0), out_amax=out_amax)
+    elif layout == 1:
+        y, _, stats = ops.conv_fwd_x3(a0.t, t1, wptr, layer.bias, layer.cout, layer.k, a0.pro, _relu_bits(a0, a1), relu_out, want_stats,
+                                      None, None, pro1, act_amax(a0), act_amax(a1), out_amax)
+    else:
+        y, _, stats = ops.conv_fwd(a0.t, t1, wptr, layer.bias, layer.cout, layer.k, a0.pro, _relu_bits(a0, a1), relu_out, want_stats,
+                                   None, None, pro1, out_amax)
     return y, stats
 
 
@@ -566,29 +575,22 @@ def _dgrad(layer, dy, split=None, mask_ref=None, below0=None, below1=None):
     with respect to (at most one of them): that gradient comes back as a PreBN."""
     root = layer._root
     below = below0 if below0 is not None else below1
+    layout, wptr = _weights(layer, dgrad=True, wide=split is not None)
     if (BN_FUSED_STATS and below is not None and mask_ref is None and below.mean is not None
-            and not (root._dp is not None and root._dp.bn_sync) and (below1 is None or split is not None)):
+            and not root.bn_synced and (below1 is None or split is not None)):
         bn = below.bn
         tail = (bn.weight, below.invstd, root.gview(bn.weight), root.gview(bn.bias)) if BN_TAIL else None
-        if layer.x16d_off >= 0 and split is None:
-            layout, wptr = 2, root.x3_ptr(layer.x16d_off)
-        elif layer.xd_off >= 0:
-            layout, wptr = 1, root.x3_ptr(layer.xd_off)
-        else:
-            layout, wptr = 0, root.packed_ptr(layer.wd_off)
         d0, d1, stats, coef = ops.dgrad_bnb(dy, wptr, layout, layer.cin, layer.k, below.y, below.ss, below.mean, below.relu, split,
                                             below1 is not None and below0 is None, tail,
                                             _gamax(dy) if layout == 1 else getattr(dy, "wt_amax", None) if layout == 2 else None)
         if below0 is not None:
             return PreBN(d0, stats, coef), d1
         return d0, PreBN(d1, stats, coef)
-    if layer.x16d_off >= 0 and split is None:
-        return ops.conv16_x3(dy, root.x3_ptr(layer.x16d_off), None, layer.cin, mask_ref=mask_ref, grad_in=True)[0], None
-    if layer.xd_off >= 0:
-        return ops.conv_fwd_x3(dy, None, root.x3_ptr(layer.xd_off), None, layer.cin, layer.k, None, 0, False, False, split,
-                               mask_ref, None, _gamax(dy))[:2]
-    return ops.conv_fwd(dy, None, root.packed_ptr(layer.wd_off), None, layer.cin, layer.k, None, 0, False, False, split,
-                        mask_ref)[:2]
+    if layout == 2:
+        return ops.conv16_x3(dy, wptr, None, layer.cin, mask_ref=mask_ref, grad_in=True)[0], None
+    if layout == 1:
+        return ops.conv_fwd_x3(dy, None, wptr, None, layer.cin, layer.k, None, 0, False, False, split, mask_ref, None, _gamax(dy))[:2]
+    return ops.conv_fwd(dy, None, wptr, None, layer.cin, layer.k, None, 0, False, False, split, mask_ref)[:2]
 
 
 # The weight gradient of a conv+BatchNorm block depends only on dy and the saved input, and nothing downstream in the
@@ -630,12 +632,8 @@ def stream_wait(waiter, waited):
 
 def note_join(root, stream):
     """end_backward() of `root` must wait for `stream`."""
-    j = root.__dict__.get("_join")
-    if j is None:
-        j = []
-        object.__setattr__(root, "_join", j)
-    if all(s is not stream for s in j):
-        j.append(stream)
+    if all(s is not stream for s in root._join):
+        root._join.append(stream)
 
 
 def _wgrad_side(layer, dy, a0, a1=None):
@@ -644,16 +642,17 @@ def _wgrad_side(layer, dy, a0, a1=None):
     root = layer._root
     if not WGRAD_SIDE_STREAM:
         return _wgrad(layer, dy, a0, a1, with_bias=False)
+    a0 = as_act(a0)
+    a1 = as_act(a1) if a1 is not None else None
     amax = _gamax(dy)                # (on the main stream, in front of the fork: the data gradient that follows uses the same slot)
-    # (likewise — normally there since the forward pass; only where the launch takes the x2h weight gradient: wgrad_r)
-    xam = (act_amax(as_act(a0)), act_amax(as_act(a1)) if a1 is not None else None) if _takes_wgrad_r(layer, as_act(a0), a1) else (None, None)
+    # (likewise the tables of the kernel's own choice — normally there since the forward pass)
+    kernel, tables = _wgrad_kernel(layer, dy, a0, a1, False)
     main = torch.cuda.current_stream()
     side = _side_stream(dy.device)
     stream_wait(side, main)
     with torch.cuda.stream(side):
-        _wgrad(layer, dy, a0, a1, with_bias=False)
-    a0 = as_act(a0)
-    for t in (dy, amax, a0.t, a0.pro) + xam + ((as_act(a1).t, as_act(a1).pro) if a1 is not None else ()):
+        _wgrad_launch(kernel, tables, layer, dy, a0, a1, False)
+    for t in (dy, amax, a0.t, a0.pro) + tables[1:] + Act.parts(a1):
         if t is not None:
             t.record_stream(side)       # the caching allocator must not hand these out again before the side stream is done
     # (Under stream capture the allocator keeps record_stream'ed blocks out of circulation until the capture ends.  Holding the
@@ -663,38 +662,61 @@ def _wgrad_side(layer, dy, a0, a1=None):
     note_join(root, side)
 
 
-def _takes_wgrad_r(layer, a0, a1, with_bias=False):
-    """3x3 layers on maps that are a multiple of 32 pixels (or exactly 16) wide: the x3 weight gradient with register-resident operands
-    (csrc/wgrad_r.hip; bias gradient only in its 16 x 16-channel form: the DeepWT layers)"""
-    return (X3 and X3_WGRAD and WGRAD_R and layer.k == 3 and
-            ops.wgrad_r_supported(layer.cin, layer.cout, 3, a0.t.shape[1] if a1 is not None else 16, a0.t.shape[3]) and
-            (not with_bias or (layer.cin % 32 != 0 and layer.cout % 32 != 0)))
+def _wgrad_kernel(layer, dy, a0, a1, with_bias):
+    """Which weight-gradient kernel the layer takes, and the amax tables that kernel reads (found here, on the caller's stream):
+    -> (kernel, (dy_amax, x_amax0, x_amax1)).
+    "r": 3x3 layers on maps that are a multiple of 32 pixels (or exactly 16) wide — the x3 weight gradient with register-resident
+    operands (csrc/wgrad_r.hip; bias gradient only in its 16 x 16-channel form: the DeepWT layers); "x3": csrc/conv_x3.hip, no
+    bias gradient; "fp32": csrc/conv.hip."""
+    c0, small = a0.t.shape[1], layer.cin % 32 != 0 and layer.cout % 32 != 0
+    if (X3 and X3_WGRAD and WGRAD_R and layer.k == 3 and
+            ops.wgrad_r_supported(layer.cin, layer.cout, 3, c0 if a1 is not None else 16, a0.t.shape[3]) and (not with_bias or small)):
+        # (the 16 x 16-channel blocks are HBM-bound: an extra pass over dY to find its scale costs more than x2h gains there — they
+        # take the table their dY's producer attached, or run in x3)
+        return "r", (getattr(dy, "wt_amax", None) if small else _gamax(dy), act_amax(a0), act_amax(a1))
+    if X3 and X3_WGRAD and not with_bias and ops.wgrad_x3_supported(layer.cin, layer.cout, layer.k, c0 if a1 is not None else 8):
+        return "x3", (None, None, None)
+    return "fp32", (None, None, None)
+
+
+def _wgrad_launch(kernel, tables, layer, dy, a0, a1, with_bias):
+    root = layer._root
+    t1, pro1 = Act.parts(a1)
+    dw = root.gview(layer.weight)
+    db = root.gview(layer.bias) if with_bias else None
+    if kernel == "r":
+        ops.conv_wgrad_r(dy, a0.t, t1, dw, db, a0.pro, _relu_bits(a0, a1), False, pro1, *tables)
+    elif kernel == "x3":
+        ops.conv_wgrad_x3(dy, a0.t, t1, layer.k, dw, a0.pro, _relu_bits(a0, a1), False, pro1)
+    else:
+        ops.conv_wgrad(dy, a0.t, t1, layer.k, dw, db, a0.pro, _relu_bits(a0, a1), False, pro1)
 
 
 def _wgrad(layer, dy, a0, a1=None, with_bias=True):
-    root = layer._root
     a0 = as_act(a0)
     a1 = as_act(a1) if a1 is not None else None
-    dw = root.gview(layer.weight)
-    db = root.gview(layer.bias) if with_bias else None
-    if _takes_wgrad_r(layer, a0, a1, with_bias):
-        # (the 16 x 16-channel blocks are HBM-bound: an extra pass over dY to find its scale costs more than x2h gains there — they
-        # take the table their dY's producer attached, or run in x3)
-        small = layer.cin % 32 != 0 and layer.cout % 32 != 0
-        ops.conv_wgrad_r(dy, a0.t, a1.t if a1 is not None else None, dw, db, a0.pro, _relu_bits(a0, a1), False,
-                         a1.pro if a1 is not None else None, getattr(dy, "wt_amax", None) if small else _gamax(dy),
-                         act_amax(a0), act_amax(a1))
-        return
-    if (X3 and X3_WGRAD and db is None and
-            ops.wgrad_x3_supported(layer.cin, layer.cout, layer.k, a0.t.shape[1] if a1 is not None else 8)):
-        ops.conv_wgrad_x3(dy, a0.t, a1.t if a1 is not None else None, layer.k, dw, a0.pro, _relu_bits(a0, a1), False,
-                          a1.pro if a1 is not None else None)
-        return
-    ops.conv_wgrad(dy, a0.t, a1.t if a1 is not None else None, layer.k, dw, db, a0.pro, _relu_bits(a0, a1), False,
-                   a1.pro if a1 is not None else None)
+    kernel, tables = _wgrad_kernel(layer, dy, a0, a1, with_bias)
+    _wgrad_launch(kernel, tables, layer, dy, a0, a1, with_bias)
 
 
 # ---- conv + BatchNorm (+ReLU): the result stays virtual (raw conv output + per-channel scale/shift) --------------
+def _bn_coeffs(root, bn, y, stats, training, tab=None, raw_amax=None):
+    """-> (ss, mean, invstd, tab): scale / shift of the BatchNorm over y and the amax table of its output (x2h).  Train mode: from
+    the (sum, sum^2) partials `stats`, exchanged first where BatchNorm is synchronised; tab: the zeroed table to fill (None: one is
+    taken here).  Eval mode: from the running statistics; the bound follows from raw_amax, the amax table of the data, if known."""
+    if not training:
+        ss = ops.bn_eval_coeffs(bn.weight, bn.bias, bn.running_mean, bn.running_var)
+        return ss, None, None, (ops.act_bound(ss, raw_amax) if raw_amax is not None else None)
+    B, _, H, W = y.shape
+    count = B * H * W
+    if root.bn_synced:
+        stats, count = root._dp.sync_bn_stats(stats, count)
+    if tab is None:
+        tab = ops.fwd_amax_table(y.device)
+    return ops.bn_finalize(stats, count, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked,
+                           act_amax=tab) + (tab,)
+
+
 def convbn_fwd(conv, bn, a0, a1, relu, training, want_tape=True):
     root = conv._root
     a0 = as_act(a0)
@@ -702,33 +724,17 @@ def convbn_fwd(conv, bn, a0, a1, relu, training, want_tape=True):
     # (x2h) the bound of the activated output travels with it to its consumers: from the statistics' fold in train mode
     # (|gamma| sqrt(N - 1) + |beta|: common.h, bn_act_bound), from the stored data's amax behind an eval-mode BatchNorm
     tab = ops.fwd_amax_table(a0.t.device) if training else None
-    if training and BN_TAIL and not (root._dp is not None and root._dp.bn_sync):
+    if training and BN_TAIL and not root.bn_synced:
         # the convolution finishes its own statistics (csrc/common.h: bnf_tail): no finalize launch
-        if conv.x16f_off >= 0 and a1 is None:
-            layout, wptr = 2, root.x3_ptr(conv.x16f_off)
-        elif conv.xf_off >= 0:
-            layout, wptr = 1, root.x3_ptr(conv.xf_off)
-        else:
-            layout, wptr = 0, root.packed_ptr(conv.wf_off)
-        y, ss, mean, invstd = ops.conv_fwd_bnf(a0.t, a1.t if a1 is not None else None, wptr, layout, conv.bias, conv.cout, conv.k,
-                                               a0.pro, _relu_bits(a0, a1), a1.pro if a1 is not None else None, bn.weight, bn.bias,
-                                               bn.running_mean, bn.running_var, bn.num_batches_tracked,
+        layout, wptr = _weights(conv, wide=a1 is not None)
+        t1, pro1 = Act.parts(a1)
+        y, ss, mean, invstd = ops.conv_fwd_bnf(a0.t, t1, wptr, layout, conv.bias, conv.cout, conv.k, a0.pro, _relu_bits(a0, a1), pro1,
+                                               bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked,
                                                in_amax0=act_amax(a0) if layout else None,
                                                in_amax1=act_amax(a1) if layout == 1 else None, act_amax=tab)
-    elif training:
-        y, stats = _conv(conv, a0, a1, False, True)
-        B, _, H, W = y.shape
-        if root._dp is not None and root._dp.bn_sync:
-            stats, count = root._dp.sync_bn_stats(stats, B * H * W)
-        else:
-            count = B * H * W
-        ss, mean, invstd = ops.bn_finalize(stats, count, bn.weight, bn.bias, bn.running_mean, bn.running_var,
-                                           bn.num_batches_tracked, act_amax=tab)
     else:
-        y, _ = _conv(conv, a0, a1, False, False, want_amax=True)
-        ss = ops.bn_eval_coeffs(bn.weight, bn.bias, bn.running_mean, bn.running_var)
-        tab = ops.act_bound(ss, y.wt_amax) if getattr(y, "wt_amax", None) is not None else None
-        mean = invstd = None
+        y, stats = _conv(conv, a0, a1, False, training, want_amax=not training)
+        ss, mean, invstd, tab = _bn_coeffs(root, bn, y, stats, training, tab, getattr(y, "wt_amax", None))
     z = Act(y, ss, relu, tab)
     if not want_tape:
         return z, None
@@ -748,7 +754,7 @@ def _bn_bwd(bn, t, dz, root):
         if dz.coef is not None:
             return ops.bn_bwd_apply_coef(dz.g, t.y, dz.coef)
         return ops.bn_bwd_from_stats(dz.g, t.y, dz.stats, bn.weight, t.mean, t.invstd, root.gview(bn.weight), root.gview(bn.bias))
-    if root._dp is not None and root._dp.bn_sync:
+    if root.bn_synced:
         return root._dp.bn_bwd_synced(dz, t, bn, root)
     return ops.bn_bwd(dz, t.y, t.ss, t.relu, bn.weight, t.mean, t.invstd, root.gview(bn.weight), root.gview(bn.bias))
 
@@ -796,7 +802,7 @@ def convd_bwd(blk, t, dz, dx_accum=None, need_dx=True, mask_x=False, below=None)
         return ops.relu_mask(d, t.x.t) if mask_x else d
     root = blk.conv1._root
     if (BN_FUSED_STATS and below is not None and below.mean is not None and t.x.relu and t.x.pro is not None
-            and not (root._dp is not None and root._dp.bn_sync)):
+            and not root.bn_synced):
         r = ops.maxpool2_bwd_bnb(t.x.t, d, dx_accum, t.x.pro, t.x.relu, below.mean)
         if r is not None:
             return PreBN(r[0], r[1])
@@ -816,22 +822,9 @@ CONVU_CONV_FIRST = os.environ.get("WTPSE_CONVU_REFERENCE_ORDER", "0") != "1"    
 def upbn_fwd(conv, bn, a0, training, want_tape=True):
     root = conv._root
     z, _ = _conv(conv, a0, None, False, False, want_amax=not training)      # low resolution, pre-BatchNorm
-    if training:
-        y, stats = ops.upsample2x_fwd_stats(z)
-        B, _, H, W = y.shape
-        if root._dp is not None and root._dp.bn_sync:
-            stats, count = root._dp.sync_bn_stats(stats, B * H * W)
-        else:
-            count = B * H * W
-        tab = ops.fwd_amax_table(y.device)
-        ss, mean, invstd = ops.bn_finalize(stats, count, bn.weight, bn.bias, bn.running_mean, bn.running_var,
-                                           bn.num_batches_tracked, act_amax=tab)
-    else:
-        y = ops.upsample2x_fwd(z)
-        ss = ops.bn_eval_coeffs(bn.weight, bn.bias, bn.running_mean, bn.running_var)
-        # (bilinear interpolation is a convex combination: the upsampled map is bounded by the amax of the low-resolution one)
-        tab = ops.act_bound(ss, z.wt_amax) if getattr(z, "wt_amax", None) is not None else None
-        mean = invstd = None
+    # (bilinear interpolation is a convex combination: the upsampled map is bounded by the amax of the low-resolution one)
+    y, stats = ops.upsample2x_fwd_stats(z) if training else (ops.upsample2x_fwd(z), None)
+    ss, mean, invstd, tab = _bn_coeffs(root, bn, y, stats, training, None, getattr(z, "wt_amax", None))
     out = Act(y, ss, True, tab)
     if not want_tape:
         return out, None
@@ -930,10 +923,10 @@ def _head_fusable(seq, idxs, x):
     if any(l.k != 1 for l in ls) or (x.t.shape[2] * x.t.shape[3]) % 32 != 0:
         return None
     root = ls[0]._root
-    off = root._offsets[root._pindex[id(ls[0].weight)]]
+    off = root.param_offset(ls[0].weight)
     for l in ls:
         for prm in (l.weight, l.bias):
-            if root._offsets[root._pindex[id(prm)]] != off:
+            if root.param_offset(prm) != off:
                 return None
             off += prm.numel()
     return ls
@@ -963,9 +956,7 @@ def head_bwd(seq, t, d, idxs):
         ls = [seq[i] for i in idxs]
         root = ls[0]._root
         views = [root.gview(prm) for l in ls for prm in (l.weight, l.bias)]      # marks them reached; contiguous range
-        total = sum(v.numel() for v in views)
-        off = root._offsets[root._pindex[id(ls[0].weight)]]
-        dparams = root._gtarget[off:off + total]
+        dparams = root.grange(ls[0].weight, sum(v.numel() for v in views))
         return ops.head_bwd(d, t.x.t, t.x.pro, t.x.relu, t.h1, t.h2, ls[0].weight, ls[1].weight,
                             ls[2].weight if len(ls) == 3 else None, dparams, b1=ls[0].bias, x_amax=act_amax(t.x), dy_amax=_gamax(d))
     for n in reversed(range(len(idxs))):
@@ -987,11 +978,13 @@ def _conv_gram(layer, a0):
     """3x3, 16 output channels, no BatchNorm: -> (z, (partial Grams, S))."""
     a0 = as_act(a0)
     out_amax = ops.fwd_amax_table(a0.t.device)       # z1 / z2 reach their x2h consumers as stored
-    if layer.x16f_off >= 0:
-        y, _, g = ops.conv16_x3(a0.t, layer._root.x3_ptr(layer.x16f_off), layer.bias, 16, a0.pro, _relu_bits(a0, None), False,
-                                want_gram=True, in_amax=act_amax(a0), out_amax=out_amax)
+    layout, wptr = _weights(layer)
+    if layout == 2:
+        y, _, g = ops.conv16_x3(a0.t, wptr, layer.bias, 16, a0.pro, _relu_bits(a0, None), False, want_gram=True,
+                                in_amax=act_amax(a0), out_amax=out_amax)
         return y, g
-    return ops.conv_fwd_gram(a0.t, layer._root.packed_ptr(layer.wf_off), layer.bias, a0.pro, _relu_bits(a0, None), False, out_amax)
+    assert layout == 0, "a 16-output-channel layer has no x3 layout"
+    return ops.conv_fwd_gram(a0.t, wptr, layer.bias, a0.pro, _relu_bits(a0, None), False, out_amax)
 
 
 def deepwt_fwd(wt, x, want_tape=True, want_gram=False):

@@ -42,31 +42,45 @@ def workspace(tag, nfloats, device):
 
 
 # ----------------------------------------------------------------------------------------------- convolution
+def _out_pair(split, B, cout, H, W, device):
+    """-> (out0, out1 or None, csplit): the output of a launch, in two tensors cut at channel `split` when one is given."""
+    if split is None:
+        return torch.empty((B, cout, H, W), dtype=torch.float32, device=device), None, cout
+    csplit = int(split)
+    return (torch.empty((B, csplit, H, W), dtype=torch.float32, device=device),
+            torch.empty((B, cout - csplit, H, W), dtype=torch.float32, device=device), csplit)
+
+
+def _stats_blocks(layout, B, H, W, cout=0, ksize=0):
+    """Rows of the per-workgroup partials of a launch on the packed layout `layout` (0 fp32, 1 x3, 2 the 16-channel x3 fragments)."""
+    if layout == 1:
+        return lib().query("wtpse_conv_x3_stats_blocks", B, H, W, cout, int(ksize))
+    return lib().query("wtpse_conv_stats_blocks", B, H, W)
+
+
+def _conv_launch(name, layout, in_amax, in0, in1, wpacked_ptr, bias, cout, ksize, pro0, pro_relu, relu_out, want_stats, split, mask_ref,
+                 pro1, out_amax):
+    """conv_fwd / conv_fwd_x3: entry point `name`; in_amax: the pointers wtpse_conv_fwd_x3 takes in front of out_amax."""
+    _chk(in0, "in0"); _chk(in1, "in1"); _chk(pro0, "pro0"); _chk(pro1, "pro1")
+    B, C0, H, W = in0.shape
+    C1 = 0 if in1 is None else in1.shape[1]
+    out0, out1, csplit = _out_pair(split, B, cout, H, W, in0.device)
+    stats = None
+    if want_stats:
+        stats = torch.empty((_stats_blocks(layout, B, H, W, cout, ksize), cout, 2), dtype=torch.float32, device=in0.device)
+    lib().call(name, ptr(in0), C0, ptr(in1), C1, wpacked_ptr, ptr(bias), ptr(pro0), ptr(pro1), int(pro_relu), ptr(out0),
+               ptr(out1), csplit, ptr(stats), B, H, W, cout, ksize, int(relu_out), ptr(mask_ref), *in_amax, ptr(out_amax), stream_ptr())
+    if out_amax is not None:
+        out0.wt_amax = out_amax
+    return out0, out1, stats
+
+
 def conv_fwd(in0, in1, wpacked_ptr, bias, cout, ksize, pro0=None, pro_relu=0, relu_out=False, want_stats=False,
              split=None, mask_ref=None, pro1=None, out_amax=None):
     """-> (out0, out1 or None, stats or None).  `wpacked_ptr` is a raw device pointer into the packed-weight buffer.
     out_amax: a zeroed amax table (fwd_amax_table) that receives the largest magnitude of the stored output."""
-    _chk(in0, "in0"); _chk(in1, "in1"); _chk(pro0, "pro0"); _chk(pro1, "pro1")
-    B, C0, H, W = in0.shape
-    C1 = 0 if in1 is None else in1.shape[1]
-    L = lib()
-    if split is None:
-        out0 = torch.empty((B, cout, H, W), dtype=torch.float32, device=in0.device)
-        out1 = None
-        csplit = cout
-    else:
-        csplit = int(split)
-        out0 = torch.empty((B, csplit, H, W), dtype=torch.float32, device=in0.device)
-        out1 = torch.empty((B, cout - csplit, H, W), dtype=torch.float32, device=in0.device)
-    stats = None
-    if want_stats:
-        nblk = L.query("wtpse_conv_stats_blocks", B, H, W)
-        stats = torch.empty((nblk, cout, 2), dtype=torch.float32, device=in0.device)
-    L.call("wtpse_conv_fwd", ptr(in0), C0, ptr(in1), C1, wpacked_ptr, ptr(bias), ptr(pro0), ptr(pro1), int(pro_relu), ptr(out0),
-           ptr(out1), csplit, ptr(stats), B, H, W, cout, ksize, int(relu_out), ptr(mask_ref), ptr(out_amax), stream_ptr())
-    if out_amax is not None:
-        out0.wt_amax = out_amax
-    return out0, out1, stats
+    return _conv_launch("wtpse_conv_fwd", 0, (), in0, in1, wpacked_ptr, bias, cout, ksize, pro0, pro_relu, relu_out, want_stats, split,
+                        mask_ref, pro1, out_amax)
 
 
 def conv_fwd_gram(in0, wpacked_ptr, bias, pro0=None, pro_relu=0, relu_out=False, out_amax=None):
@@ -76,7 +90,7 @@ def conv_fwd_gram(in0, wpacked_ptr, bias, pro0=None, pro_relu=0, relu_out=False,
     B, C0, H, W = in0.shape
     L = lib()
     out = torch.empty((B, 16, H, W), dtype=torch.float32, device=in0.device)
-    nblk = L.query("wtpse_conv_stats_blocks", B, H, W)
+    nblk = _stats_blocks(0, B, H, W)
     partial = torch.empty((nblk, 256), dtype=torch.float32, device=in0.device)
     L.call("wtpse_conv_fwd_gram", ptr(in0), C0, wpacked_ptr, ptr(bias), ptr(pro0), int(pro_relu), ptr(out), ptr(partial), B, H, W,
            16, int(relu_out), ptr(out_amax), stream_ptr())
@@ -99,7 +113,7 @@ def conv16_x3(in0, wx16_ptr, bias, cout, pro0=None, pro_relu=0, relu_out=False, 
     B, C0, H, W = in0.shape
     L = lib()
     out = torch.empty((B, cout, H, W), dtype=torch.float32, device=in0.device)
-    nblk = L.query("wtpse_conv_stats_blocks", B, H, W)
+    nblk = _stats_blocks(2, B, H, W)
     stats = torch.empty((nblk, cout, 2), dtype=torch.float32, device=in0.device) if (want_stats or bnb is not None) else None
     gram = torch.empty((nblk, 256), dtype=torch.float32, device=in0.device) if want_gram else None
     bn_ss = bn_mean = None
@@ -131,6 +145,31 @@ _AMAX = {}
 _AMAX_TABLES = 512          # tables per arena (2 MB): a backward pass of the largest network hands out ~120
 
 
+class _Arena:
+    """An int32 buffer, zero when it is handed over, given out front to back: `buf` (None: no buffer), `next` = words given out so
+    far, take(n_words) -> the next slice, or None when there is no buffer or it is exhausted (the owner decides what happens
+    then).  renew(buf) starts over on a fresh buffer and keeps the last three in `retired` for work still queued on them."""
+    __slots__ = ("buf", "next", "retired")
+
+    def __init__(self, buf):
+        self.buf, self.next, self.retired = buf, 0, []
+
+    def take(self, n):
+        off = self.next
+        if self.buf is None or off + n > self.buf.numel():
+            return None
+        self.next = off + n
+        return self.buf[off:off + n]
+
+    def renew(self, buf):
+        self.retired.append(self.buf)
+        del self.retired[:-3]
+        self.buf, self.next = buf, 0
+
+    def __getitem__(self, i):       # (buf, next) by position: how the kernel tests have always read the ticket ring
+        return (self.buf, self.next)[i]
+
+
 def amax_begin(device):
     """Start of a backward pass: a fresh arena of zeroed amax tables for the gradients it produces.  ONE launch zeroes the WHOLE arena,
     unconditionally — the call is part of recorded launch plans / captured graphs, so what it zeroes must not depend on how many
@@ -140,14 +179,12 @@ def amax_begin(device):
     by whichever network began a backward pass next, under the feet of a pass of another network still in flight.  The producers of a
     pass (bn_bwd_*, upsample2x_bwd*) take their tables with _amax_table(); the tables (views, attached to the gradients as
     `wt_amax`) keep their arena alive, and the last few arenas are held a little longer for work still queued on side streams."""
-    st = _AMAX.get(device)
     buf = zero_(torch.empty(_AMAX_TABLES * AMAX_WORDS, dtype=torch.int32, device=device))     # (2 MB, ~2 us; recorded steps: from the capture's pool)
+    st = _AMAX.get(device)
     if st is None:
-        st = _AMAX[device] = [buf, 0, []]
+        _AMAX[device] = _Arena(buf)
     else:
-        st[2].append(st[0])
-        del st[2][:-3]
-        st[0], st[1] = buf, 0
+        st.renew(buf)
 
 
 def _amax_table(device):
@@ -155,30 +192,26 @@ def _amax_table(device):
     if x3_terms() != 2:
         return None
     st = _AMAX.get(device)
-    if st is None or st[1] >= _AMAX_TABLES:        # no arena yet / exhausted (micro-benchmarks looping without begin_backward)
-        return zero_(torch.empty(AMAX_WORDS, dtype=torch.int32, device=device))
-    t = st[0][st[1] * AMAX_WORDS:(st[1] + 1) * AMAX_WORDS]
-    st[1] += 1
-    return t
+    t = st.take(AMAX_WORDS) if st is not None else None
+    # no arena yet / exhausted (micro-benchmarks looping without begin_backward): a fresh zeroed table
+    return t if t is not None else zero_(torch.empty(AMAX_WORDS, dtype=torch.int32, device=device))
 
 
 _FWD_SCOPES = []
 FWD_SCOPE_TABLES = 256      # per forward pass (1 MB): a WT_PSE.update hands out ~60, an eval-mode predict ~170
 
 
-class fwd_scope:
+class fwd_scope(_Arena):
     """The amax tables of ONE forward pass (an update() / predict() call): forward activations carry a bound of their largest
     magnitude to their x2h consumers in tables like the gradients' (include/wtpse_hip.h, wtpse_x3_terms), and those tables must be zero
     when their producer runs.  A scope owns one buffer, zeroed by ONE launch when the pass starts (on the stream the pass starts on,
     in front of every fork), and hands out slices; the slices (held by the activations on the tape) keep the buffer alive until the
     backward pass is done with them.  Recorded steps: the buffer comes from the capture's pool and the zeroing is a recorded launch.
     Without a scope (block-level callers, tests) a table is a fresh zeroed tensor of its own."""
+    __slots__ = ()
 
     def __init__(self, device):
-        self.buf = None
-        if x3_terms() == 2:
-            self.buf = zero_(torch.empty(FWD_SCOPE_TABLES * AMAX_WORDS, dtype=torch.int32, device=device))
-        self.next = 0
+        super().__init__(zero_(torch.empty(FWD_SCOPE_TABLES * AMAX_WORDS, dtype=torch.int32, device=device)) if x3_terms() == 2 else None)
 
     def __enter__(self):
         _FWD_SCOPES.append(self)
@@ -195,11 +228,8 @@ def fwd_amax_table(device):
     if x3_terms() != 2:
         return None
     sc = _FWD_SCOPES[-1] if _FWD_SCOPES else None
-    if sc is None or sc.buf is None or sc.buf.device != device or sc.next >= FWD_SCOPE_TABLES:
-        return zero_(torch.empty(AMAX_WORDS, dtype=torch.int32, device=device))
-    t = sc.buf[sc.next * AMAX_WORDS:(sc.next + 1) * AMAX_WORDS]
-    sc.next += 1
-    return t
+    t = sc.take(AMAX_WORDS) if sc is not None and sc.buf is not None and sc.buf.device == device else None
+    return t if t is not None else zero_(torch.empty(AMAX_WORDS, dtype=torch.int32, device=device))
 
 
 def act_bound(ss, raw_amax):
@@ -226,52 +256,34 @@ def conv_fwd_x3(in0, in1, wpacked_ptr, bias, cout, ksize, pro0=None, pro_relu=0,
     """conv_fwd on the 16-bit matrix cores at fp32 accuracy (csrc/conv_x3.hip); `wpacked_ptr` points into the x3-packed weights.
     in_amax / in_amax1: the amax tables of in0 / in1 AS LOADED (a gradient's amax_of; a forward activation's bound, nn.act_amax) —
     include/wtpse_hip.h, wtpse_x3_terms; out_amax: as conv_fwd."""
-    _chk(in0, "in0"); _chk(in1, "in1"); _chk(pro0, "pro0"); _chk(pro1, "pro1")
-    B, C0, H, W = in0.shape
-    C1 = 0 if in1 is None else in1.shape[1]
-    L = lib()
-    if split is None:
-        out0 = torch.empty((B, cout, H, W), dtype=torch.float32, device=in0.device)
-        out1 = None
-        csplit = cout
-    else:
-        csplit = int(split)
-        out0 = torch.empty((B, csplit, H, W), dtype=torch.float32, device=in0.device)
-        out1 = torch.empty((B, cout - csplit, H, W), dtype=torch.float32, device=in0.device)
-    stats = None
-    if want_stats:
-        nblk = L.query("wtpse_conv_x3_stats_blocks", B, H, W, cout, int(ksize))
-        stats = torch.empty((nblk, cout, 2), dtype=torch.float32, device=in0.device)
-    L.call("wtpse_conv_fwd_x3", ptr(in0), C0, ptr(in1), C1, wpacked_ptr, ptr(bias), ptr(pro0), ptr(pro1), int(pro_relu), ptr(out0),
-           ptr(out1), csplit, ptr(stats), B, H, W, cout, ksize, int(relu_out), ptr(mask_ref), ptr(in_amax), ptr(in_amax1),
-           ptr(out_amax), stream_ptr())
-    if out_amax is not None:
-        out0.wt_amax = out_amax
-    return out0, out1, stats
+    return _conv_launch("wtpse_conv_fwd_x3", 1, (ptr(in_amax), ptr(in_amax1)), in0, in1, wpacked_ptr, bias, cout, ksize, pro0, pro_relu,
+                        relu_out, want_stats, split, mask_ref, pro1, out_amax)
 
 
-_TICKETS = {}
+_TICKETS = {}               # device -> _Arena: the eager ring
 _TICKET_RING = 1 << 22      # unsigneds (16 MB): ~1900 launches of the largest layer (5 training steps) before a slice comes round again; the
                             # streams of a step are joined at its end, so two users of a slice never run at the same time
-_TICKET_SCOPE = None        # [tensor, next]: a private ticket buffer while a step is being recorded (ticket_scope)
+_TICKET_SCOPE = None        # the ticket_scope a step is being recorded under: its private ticket buffer
 _DEBUG = __import__("os").environ.get("WTPSE_DEBUG", "0") == "1"
 
 
-class ticket_scope:
+class ticket_scope(_Arena):
     """While a step is recorded into a launch plan / captured into a graph, its launches take their ticket slices from a buffer of
     their OWN (allocated here, before the capture starts; owned by the recorded step and freed with it) instead of the eager ring:
     a replayed launch keeps its slice for as long as the recording lives, and the eager ring's pointer, which comes round every
     ~1900 launches, must never land on it (an eager step between two replays would have shared slices with the
     replayed launches that were in flight on other streams)."""
+    __slots__ = ()
 
     def __init__(self, device, n=1 << 21):
-        self.buf = torch.zeros(n, dtype=torch.int32, device=device)
+        super().__init__(torch.zeros(n, dtype=torch.int32, device=device))
         torch.cuda.current_stream(device).synchronize()
 
     def __enter__(self):
         global _TICKET_SCOPE
         assert _TICKET_SCOPE is None, "ticket scopes do not nest"
-        _TICKET_SCOPE = [self.buf, 0]
+        self.next = 0
+        _TICKET_SCOPE = self
         return self
 
     def __exit__(self, *exc):
@@ -285,28 +297,28 @@ def _tickets(n, device):
     of one ring per device — a slice is handed out again only after ~1900 further launches, long after its launch has finished.
     Launches recorded inside a ticket_scope: consecutive slices of the scope's private buffer, never reused.  -> (pointer, view)."""
     n = (n + 63) & ~63
-    if _TICKET_SCOPE is not None:
-        buf, off = _TICKET_SCOPE
-        if off + n > buf.numel():
-            raise RuntimeError("ticket_scope exhausted (%d unsigneds): a recorded step uses more ticket words than reserved" % buf.numel())
-        _TICKET_SCOPE[1] = off + n
-        return buf.data_ptr() + 4 * off, buf[off:off + n]
+    st = _TICKET_SCOPE
+    if st is not None:
+        view = st.take(n)
+        if view is None:
+            raise RuntimeError("ticket_scope exhausted (%d unsigneds): a recorded step uses more ticket words than reserved" % st.buf.numel())
+        return st.buf.data_ptr() + 4 * view.storage_offset(), view
     st = _TICKETS.get(device)
     if st is None:
         if torch.cuda.is_current_stream_capturing():
             # the zero fill would be captured instead of executed (and the ring would live in the capture's private pool)
             raise RuntimeError("the ticket ring must exist before a step is captured: HipNet.ensure_ready() creates it")
-        st = _TICKETS[device] = [torch.zeros(_TICKET_RING, dtype=torch.int32, device=device), 0]
+        st = _TICKETS[device] = _Arena(torch.zeros(_TICKET_RING, dtype=torch.int32, device=device))
         torch.cuda.current_stream(device).synchronize()
-    if st[1] + n > _TICKET_RING:
-        st[1] = 0
-    off = st[1]
-    st[1] += n
-    view = st[0][off:off + n]
+    view = st.take(n)
+    if view is None:                # the ring comes round
+        st.next = 0
+        view = st.take(n)
     if _DEBUG and n and not torch.cuda.is_current_stream_capturing():
         torch.cuda.synchronize(device)
+        off = view.storage_offset()
         assert not bool(view.any()), "ticket slice [%d, %d) is not zero on entry: a launch that used it failed or is still running" % (off, off + n)
-    return st[0].data_ptr() + 4 * off, view
+    return st.buf.data_ptr() + 4 * view.storage_offset(), view
 
 
 def _ticket_call(view, name, *args):
@@ -334,17 +346,10 @@ def dgrad_bnb(dy, wpacked_ptr, layout, cout, ksize, bn_y, bn_ss, bn_mean, bn_rel
     layout = int(layout)
     B, C, H, W = dy.shape
     L = lib()
-    if split is None:
-        csplit, c0, c1 = cout, 0, cout
-        out0 = torch.empty((B, cout, H, W), dtype=torch.float32, device=dy.device)
-        out1 = None
-    else:
-        csplit = int(split)
-        c0, c1 = (csplit, cout) if bn_second else (0, csplit)
-        out0 = torch.empty((B, csplit, H, W), dtype=torch.float32, device=dy.device)
-        out1 = torch.empty((B, cout - csplit, H, W), dtype=torch.float32, device=dy.device)
+    out0, out1, csplit = _out_pair(split, B, cout, H, W, dy.device)
+    c0, c1 = (csplit, cout) if (bn_second and split is not None) else (0, csplit)
     assert bn_y.shape == (B, c1 - c0, H, W), (bn_y.shape, (B, c1 - c0, H, W))
-    nblk = L.query("wtpse_conv_x3_stats_blocks", B, H, W, cout, int(ksize)) if layout == 1 else L.query("wtpse_conv_stats_blocks", B, H, W)
+    nblk = _stats_blocks(layout, B, H, W, cout, ksize)
     stats = torch.empty((nblk, c1 - c0, 2), dtype=torch.float32, device=dy.device)
     if tail is not None:
         gamma, invstd, dgamma, dbeta = tail
@@ -367,14 +372,18 @@ def dgrad_bnb(dy, wpacked_ptr, layout, cout, ksize, bn_y, bn_ss, bn_mean, bn_rel
     return out0, out1, stats, None
 
 
-def conv_wgrad(dy, x0, x1, ksize, dw, dbias, pro0=None, pro_relu=0, accumulate=False, pro1=None):
-    """dw / dbias are views into the flat gradient buffer ([Cout,Cin,k,k] / [Cout] or None)."""
+def _wgrad_dims(dy, x0, x1):
+    """The prelude of the weight-gradient wrappers: -> (lib, B, cout, H, W, C0, C1, cin) of dy [B,cout,H,W] and the inputs x0 (, x1)."""
     _chk(dy, "dy"); _chk(x0, "x0"); _chk(x1, "x1")
     B, cout, H, W = dy.shape
     C0 = x0.shape[1]
     C1 = 0 if x1 is None else x1.shape[1]
-    cin = C0 + C1
-    L = lib()
+    return lib(), B, cout, H, W, C0, C1, C0 + C1
+
+
+def conv_wgrad(dy, x0, x1, ksize, dw, dbias, pro0=None, pro_relu=0, accumulate=False, pro1=None):
+    """dw / dbias are views into the flat gradient buffer ([Cout,Cin,k,k] / [Cout] or None)."""
+    L, B, cout, H, W, C0, C1, cin = _wgrad_dims(dy, x0, x1)
     ks = L.query("wtpse_wgrad_ksplit", B, H, W, cin, cout)
     slab = workspace("wgrad_slab", ks * cout * cin * ksize * ksize, dy.device)
     dbs = workspace("wgrad_dbias", ks * cout, dy.device) if dbias is not None else None
@@ -388,12 +397,7 @@ def wgrad_x3_supported(cin, cout, ksize, c0):
 
 def conv_wgrad_x3(dy, x0, x1, ksize, dw, pro0=None, pro_relu=0, accumulate=False, pro1=None):
     """conv_wgrad in the x3 arithmetic (csrc/conv_x3.hip); no bias gradient."""
-    _chk(dy, "dy"); _chk(x0, "x0"); _chk(x1, "x1")
-    B, cout, H, W = dy.shape
-    C0 = x0.shape[1]
-    C1 = 0 if x1 is None else x1.shape[1]
-    cin = C0 + C1
-    L = lib()
+    L, B, cout, H, W, C0, C1, cin = _wgrad_dims(dy, x0, x1)
     ks = L.query("wtpse_wgrad_x3_ksplit", B, H, W, cin, cout)
     slab = workspace("wgrad_slab", ks * cout * cin * ksize * ksize, dy.device)
     L.call("wtpse_conv_wgrad_x3", ptr(dy), ptr(x0), C0, ptr(x1), C1, ptr(pro0), ptr(pro1), int(pro_relu), ptr(slab), ks, ptr(dw),
@@ -408,12 +412,7 @@ def conv_wgrad_r(dy, x0, x1, dw, dbias=None, pro0=None, pro_relu=0, accumulate=F
                  x_amax1=None):
     """3x3 conv_wgrad in the x3 arithmetic with register-resident operands (csrc/wgrad_r.hip); with bias gradient.
     dy_amax: amax_of(dy) (x2h: the scale of the gradient operand); x_amax0 / x_amax1: the bounds of x0 / x1 as loaded."""
-    _chk(dy, "dy"); _chk(x0, "x0"); _chk(x1, "x1")
-    B, cout, H, W = dy.shape
-    C0 = x0.shape[1]
-    C1 = 0 if x1 is None else x1.shape[1]
-    cin = C0 + C1
-    L = lib()
+    L, B, cout, H, W, C0, C1, cin = _wgrad_dims(dy, x0, x1)
     ns = L.query("wtpse_wgrad_r_slabs", B, H, W, cin, cout)
     slab = workspace("wgrad_slab", ns * cout * cin * 9, dy.device)
     dbs = workspace("wgrad_dbias", ns * cout, dy.device) if dbias is not None else None
@@ -423,12 +422,8 @@ def conv_wgrad_r(dy, x0, x1, dw, dbias=None, pro0=None, pro_relu=0, accumulate=F
 
 def conv_wgrad_r_bn(g, bn_y, coef, x0, x1, dw, pro0=None, pro_relu=0, accumulate=False, pro1=None):
     """conv_wgrad_r with dY = coef[:,0] * g + coef[:,1] * bn_y + coef[:,2] formed on load (no bias gradient)."""
-    _chk(g, "g"); _chk(bn_y, "bn_y"); _chk(x0, "x0"); _chk(x1, "x1")
-    B, cout, H, W = g.shape
-    C0 = x0.shape[1]
-    C1 = 0 if x1 is None else x1.shape[1]
-    cin = C0 + C1
-    L = lib()
+    _chk(bn_y, "bn_y")
+    L, B, cout, H, W, C0, C1, cin = _wgrad_dims(g, x0, x1)
     ns = L.query("wtpse_wgrad_r_slabs", B, H, W, cin, cout)
     slab = workspace("wgrad_slab", ns * cout * cin * 9, g.device)
     L.call("wtpse_conv_wgrad_r_bn", ptr(g), ptr(bn_y), ptr(coef), ptr(x0), C0, ptr(x1), C1, ptr(pro0), ptr(pro1), int(pro_relu),
@@ -448,7 +443,7 @@ def conv_fwd_bnf(in0, in1, wpacked_ptr, layout, bias, cout, ksize, pro0, pro_rel
     L = lib()
     dev = in0.device
     out = torch.empty((B, cout, H, W), dtype=torch.float32, device=dev)
-    nblk = L.query("wtpse_conv_x3_stats_blocks", B, H, W, cout, int(ksize)) if layout == 1 else L.query("wtpse_conv_stats_blocks", B, H, W)
+    nblk = _stats_blocks(layout, B, H, W, cout, ksize)
     stats = torch.empty((nblk, cout, 2), dtype=torch.float32, device=dev)
     ss = torch.empty((cout, 2), dtype=torch.float32, device=dev)
     mean = torch.empty((cout,), dtype=torch.float32, device=dev)
