@@ -371,6 +371,21 @@ int wtpse_roi(const float* image, const float* logit, float* roi, float* od_pred
  * device int holding the number of completed steps, so that a captured launch stays valid when replayed). */
 int wtpse_adam(float* p, const float* g, float* m, float* v, long long n, double lr, double beta1, double beta2, double eps,
                int step, const int* step_dev, void* stream);
+/* wtpse_adam with the learning rate read from device memory: lr_dev = one device float, so that a schedule can change the rate
+ * of a recorded launch between replays (a write on the stream, nothing recorded again).  The same kernel body serves both entry
+ * points: for the same float value, p / m / v come out bit-identical to wtpse_adam(..., lr = (double)*lr_dev, ...).
+ * hold (NULL: never held): one device int, read once per workgroup; when *hold != 0 the launch changes nothing — p, m, v keep
+ * their bits (the NaN flag of wtpse_loss_log: a poisoned loss is not applied to the weights). */
+int wtpse_adam_dev(float* p, const float* g, float* m, float* v, long long n, const float* lr_dev, double beta1, double beta2,
+                   double eps, int step, const int* step_dev, const int* hold, void* stream);
+/* Device-side loss log (Trainer.py:788-800, 828-832, 874-885, 917-919): one single-wave launch per update() call of a step.
+ * s0..s5: device fp32 scalars (trailing ones may be NULL); for every non-NULL sj: acc[j] += (double)*sj — the reference's
+ * `running += loss.item()`, so a double accumulator fed in iteration order holds its running sums bit for bit.
+ * NaN test on the first check_n scalars, in fp32 and in the reference's order: check_n = 3: isnan((s0 + s1) + s2) (inf + -inf
+ * counts), 1: isnan(s0), 0: none.  flag: two device ints, sticky (never cleared here): when the test holds and flag[0] == 0,
+ * flag[0] = 1 and flag[1] = *step_dev (the calling network's count of completed steps = the failing iteration; NULL: 0). */
+int wtpse_loss_log(const float* s0, const float* s1, const float* s2, const float* s3, const float* s4, const float* s5,
+                   double* acc, int check_n, int* flag, const int* step_dev, void* stream);
 
 /* ---- fused 1x1 heads (csrc/head.hip) ------------------------------------------------------------------------------ */
 /* The heads 32 -> 32 (ReLU) -> 8 [-> (ReLU) -> nc] as one kernel per direction: reference algorithms.py:1006-1012

@@ -647,20 +647,35 @@ __global__ __launch_bounds__(256) void roi_k(const float* __restrict__ image, co
 // step_dev (optional): device int holding the number of COMPLETED optimiser steps; the bias corrections are then formed
 // here from t = step + *step_dev (one thread per block, in double as on the host), so that a captured launch stays valid
 // when it is replayed (hipGraph): nothing that changes from step to step is passed by value.
+// lr_dev (optional): the learning rate as one device float, read in place of `lr` (wtpse_adam_dev: a schedule changes it between
+// the replays of a recorded step).  hold (optional): one device int; non-zero = the launch changes nothing (the loss log's NaN
+// flag, wtpse_loss_log).  Both are read by one thread per block, like step_dev; the element-wise part is the same code for both
+// entry points, so for the same float `lr` their results are the same bits.
 __global__ __launch_bounds__(256) void adam_k(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                               float* __restrict__ v, long long n, float lr, float b1, float b2, float eps,
                                               float bc1, float bc2_sqrt, int step, const int* __restrict__ step_dev,
-                                              double b1d, double b2d) {
-  if (step_dev) {
-    __shared__ float bc[2];
+                                              double b1d, double b2d, const float* __restrict__ lr_dev,
+                                              const int* __restrict__ hold) {
+  if (step_dev || lr_dev || hold) {
+    __shared__ float bc[3];
+    __shared__ int held;
     if (threadIdx.x == 0) {
-      const double t = (double)(step + *step_dev);
-      bc[0] = (float)(1.0 - pow(b1d, t));
-      bc[1] = (float)sqrt(1.0 - pow(b2d, t));
+      if (step_dev) {
+        const double t = (double)(step + *step_dev);
+        bc[0] = (float)(1.0 - pow(b1d, t));
+        bc[1] = (float)sqrt(1.0 - pow(b2d, t));
+      } else {
+        bc[0] = bc1;
+        bc[1] = bc2_sqrt;
+      }
+      bc[2] = lr_dev ? *lr_dev : lr;
+      held = hold ? *hold : 0;
     }
     __syncthreads();
+    if (held) return;
     bc1 = bc[0];
     bc2_sqrt = bc[1];
+    lr = bc[2];
   }
   long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
@@ -671,6 +686,27 @@ __global__ __launch_bounds__(256) void adam_k(float* __restrict__ p, const float
   v[i] = vi;
   float denom = sqrtf(vi) / bc2_sqrt + eps;
   p[i] -= (lr / bc1) * (mi / denom);
+}
+
+// ------------------------------------------------------------------------------------------------ loss log (Trainer.py:788-800, 874-885)
+// One wave: lane j < 6 folds scalar j into its running sum (the reference's `running_x += loss.item()`: an fp32 value widened to
+// double, added to a double); lane 0 evaluates the reference's NaN test in fp32, in its order, and raises the sticky flag.
+__global__ __launch_bounds__(64) void loss_log_k(const float* s0, const float* s1, const float* s2, const float* s3, const float* s4,
+                                                 const float* s5, double* __restrict__ acc, int check_n, int* __restrict__ flag,
+                                                 const int* __restrict__ step_dev) {
+  const int j = threadIdx.x;
+  if (j < 6) {
+    const float* s = j == 0 ? s0 : j == 1 ? s1 : j == 2 ? s2 : j == 3 ? s3 : j == 4 ? s4 : s5;
+    if (s) acc[j] += (double)*s;
+  }
+  if (j == 0 && check_n > 0) {
+    float t = *s0;
+    if (check_n == 3) t = (t + *s1) + *s2;
+    if (isnan(t) && flag[0] == 0) {
+      flag[0] = 1;
+      flag[1] = step_dev ? *step_dev : 0;
+    }
+  }
 }
 
 // ------------------------------------------------------------------------------------------------ Philox4x32-10 -> N(0,1)
@@ -993,7 +1029,24 @@ extern "C" int wtpse_adam(float* p, const float* g, float* m, float* v, long lon
   float bc1 = (float)(1.0 - pow(beta1, (double)step));
   float bc2s = (float)sqrt(1.0 - pow(beta2, (double)step));
   hipLaunchKernelGGL(adam_k, GRID1(n), dim3(256), 0, ST, p, g, m, v, n, (float)lr, (float)beta1, (float)beta2, (float)eps, bc1,
-                     bc2s, step, step_dev, beta1, beta2);
+                     bc2s, step, step_dev, beta1, beta2, (const float*)nullptr, (const int*)nullptr);
+  return wtpse_status();
+}
+extern "C" int wtpse_adam_dev(float* p, const float* g, float* m, float* v, long long n, const float* lr_dev, double beta1,
+                              double beta2, double eps, int step, const int* step_dev, const int* hold, void* stream) {
+  WTPSE_REQUIRE(p && g && m && v && lr_dev && n > 0 && step >= 1);
+  float bc1 = (float)(1.0 - pow(beta1, (double)step));
+  float bc2s = (float)sqrt(1.0 - pow(beta2, (double)step));
+  hipLaunchKernelGGL(adam_k, GRID1(n), dim3(256), 0, ST, p, g, m, v, n, 0.f, (float)beta1, (float)beta2, (float)eps, bc1, bc2s,
+                     step, step_dev, beta1, beta2, lr_dev, hold);
+  return wtpse_status();
+}
+extern "C" int wtpse_loss_log(const float* s0, const float* s1, const float* s2, const float* s3, const float* s4, const float* s5,
+                              double* acc, int check_n, int* flag, const int* step_dev, void* stream) {
+  WTPSE_REQUIRE(s0 && acc && flag && (check_n == 0 || check_n == 1 || check_n == 3));
+  WTPSE_REQUIRE(check_n != 3 || (s1 && s2));
+  WTPSE_REQUIRE((((uintptr_t)acc) & 7) == 0);
+  hipLaunchKernelGGL(loss_log_k, dim3(1), dim3(64), 0, ST, s0, s1, s2, s3, s4, s5, acc, check_n, flag, step_dev);
   return wtpse_status();
 }
 extern "C" int wtpse_randn(float* out, long long n, unsigned long long seed, unsigned long long offset,

@@ -863,6 +863,22 @@ def adam_step(p, g, m, v, lr, beta1, beta2, eps, step, step_dev=None):
                int(step), ptr(step_dev), stream_ptr())
 
 
+def adam_step_dev(p, g, m, v, lr_dev, beta1, beta2, eps, step, step_dev=None, hold=None):
+    """adam_step with the learning rate in device memory (lr_dev: one fp32) and an optional hold flag (device int32: non-zero =
+    the launch changes nothing)."""
+    lib().call("wtpse_adam_dev", ptr(p), ptr(g), ptr(m), ptr(v), p.numel(), ptr(lr_dev), float(beta1), float(beta2), float(eps),
+               int(step), ptr(step_dev), ptr(hold), stream_ptr())
+
+
+def loss_log(scalars, acc, offset, check_n, flag, step_dev):
+    """acc[offset + j] += scalars[j] (up to six 0-dim fp32 device tensors; acc: device float64) and the reference's NaN test on the
+    first check_n of them into flag (device int32 [2]); see wtpse_loss_log in include/wtpse_hip.h."""
+    if not 1 <= len(scalars) <= 6 or offset + len(scalars) > acc.numel():
+        raise ValueError("loss_log: %d scalars at offset %d of an accumulator of %d" % (len(scalars), offset, acc.numel()))
+    s = [ptr(t) for t in scalars] + [0] * (6 - len(scalars))
+    lib().call("wtpse_loss_log", *s, acc.data_ptr() + 8 * int(offset), int(check_n), ptr(flag), ptr(step_dev), stream_ptr())
+
+
 # ----------------------------------------------------------------------------------------------- validation back half
 def _chk_dev(t, name, dtype):
     if not (t.is_cuda and t.dtype == dtype and t.is_contiguous() and t.dim() == 4 and t.shape[1] == 1):

@@ -15,7 +15,7 @@ per-tensor updates, and the dead work listed in shape_networks.py's header is sk
 
 Replaying a recorded step: a step is ~1 900 kernel launches from one Python thread (tens of milliseconds of host time,
 about as long as the GPU needs for them).  The C ABI allocates nothing, never synchronises and takes nothing that changes
-from step to step by value (Adam's step number and the Philox stream position live in device memory), so a step can be
+from step to step by value (Adam's step number, its learning rate and the Philox stream position live in device memory), so a step can be
 recorded once and replayed:
   * `TrainStep(..., graph="plan")`: the step is recorded under stream capture — which pins every device address: the
     allocator serves the capture from a private pool and defers cross-stream frees — into native launch plans
@@ -25,19 +25,92 @@ recorded once and replayed:
     eager launches on this runtime (profiles/r02_hipgraph_vs_eager.txt); kept for comparison.
 With data-parallel training the gradient all-reduces stay outside (RCCL runs them eagerly between the replayed stretches):
 a step is then five plans / graphs with four collectives between them.
+
+What a recording freezes, and what it does not: the learning rates are device floats (`FlatAdam.lr`, `TrainStep.set_lr`: a
+stream-ordered write, picked up by the next replay); the optimiser state and the Philox positions are loaded INTO the buffers the
+recording reads (`load_state_dict`); betas, eps and the Philox seeds are passed by value and belong to the recording.
 """
 import torch
 
 from . import ops
 
 
+NET_KEYS = ("od", "od_shape", "oc", "oc_shape")      # the four networks in the order of train.py:120-138 (lr, lr_shape, lr_oc, lr_oc_shape)
+
+
+def adam_state_to_torch(m, v, t, shapes, lr, betas, eps):
+    """The flat moments m / v (1-D, parameters back to back in `shapes` order) and the step count t as torch.optim.Adam's
+    state_dict: state[i] = {step, exp_avg, exp_avg_sq} per parameter, one param_groups entry.  The tensors are copies."""
+    state, off = {}, 0
+    for i, shape in enumerate(shapes):
+        n = 1
+        for d in shape:
+            n *= int(d)
+        state[i] = {"step": torch.tensor(float(t)), "exp_avg": m[off:off + n].reshape(shape).clone(),
+                    "exp_avg_sq": v[off:off + n].reshape(shape).clone()}
+        off += n
+    if off != m.numel() or off != v.numel():
+        raise ValueError("the shapes describe %d elements, the moments hold %d / %d" % (off, m.numel(), v.numel()))
+    group = {"lr": float(lr), "betas": (float(betas[0]), float(betas[1])), "eps": float(eps), "weight_decay": 0, "amsgrad": False,
+             "params": list(range(len(shapes)))}
+    return {"state": state, "param_groups": [group]}
+
+
+def adam_state_from_torch(sd, shapes, m, v):
+    """The reverse: copies exp_avg / exp_avg_sq of a torch.optim.Adam state_dict into the existing flat m / v (in place) and
+    returns (t, param_group).  An empty state (an optimiser that has not stepped) is t = 0 with zero moments; a parameter
+    without an entry (torch keeps none for a parameter that never had a gradient) gets zero moments.  One flat step count
+    serves all parameters, so a state whose parameters have stepped different numbers of times is refused."""
+    groups = sd["param_groups"]
+    if len(groups) != 1:
+        raise ValueError("FlatAdam holds one parameter group (one learning rate per network), the state has %d" % len(groups))
+    g = groups[0]
+    if g.get("weight_decay", 0) != 0 or g.get("amsgrad", False) or g.get("maximize", False):
+        raise ValueError("FlatAdam is torch.optim.Adam with weight_decay=0, amsgrad=False, maximize=False; the state asks for "
+                         "weight_decay=%r amsgrad=%r maximize=%r" % (g.get("weight_decay"), g.get("amsgrad"), g.get("maximize")))
+    if list(g["params"]) != list(range(len(shapes))):
+        raise ValueError("the state's parameter group lists %d parameters, the network has %d" % (len(g["params"]), len(shapes)))
+    state = sd["state"]
+    if len(state) == 0:
+        m.zero_()
+        v.zero_()
+        return 0, g
+    # torch.optim.Adam keeps no entry for a parameter that never received a gradient (it skips `p.grad is None`); under a flat
+    # update such a parameter sees zero gradients, i.e. zero moments at any step count: that is what a missing entry becomes
+    have = [i for i in range(len(shapes)) if i in state]
+    steps = sorted({int(float(state[i]["step"])) for i in have})
+    if len(steps) != 1:
+        raise ValueError("the parameters' step counts differ (%s): one flat step count cannot represent them" % steps)
+    for i in have:
+        for k in ("exp_avg", "exp_avg_sq"):
+            if tuple(state[i][k].shape) != tuple(shapes[i]):
+                raise ValueError("parameter %d: %s has shape %s, the network's is %s" % (i, k, tuple(state[i][k].shape), tuple(shapes[i])))
+    off = 0
+    with torch.no_grad():
+        for i, shape in enumerate(shapes):
+            n = 1
+            for d in shape:
+                n *= int(d)
+            if i in state:
+                m[off:off + n].copy_(state[i]["exp_avg"].reshape(-1))
+                v[off:off + n].copy_(state[i]["exp_avg_sq"].reshape(-1))
+            else:
+                m[off:off + n].zero_()
+                v[off:off + n].zero_()
+            off += n
+    return steps[0], g
+
+
 class FlatAdam:
     """torch.optim.Adam(lr, betas, eps=1e-8, weight_decay=0) over a network's flat buffers: one launch per step.
-    The step count is a device integer (see wtpse_adam in include/wtpse_hip.h)."""
+    The step count is a device integer and the learning rate a device float (see wtpse_adam_dev in include/wtpse_hip.h): `lr` can
+    be assigned at any time, also between the replays of a recorded step — a write on the current stream, no host sync.
+    `hold`: optional device int32 (a LossLog's flag); while it is non-zero the launches change neither p nor m nor v."""
 
     def __init__(self, net, lr=5e-4, betas=(0.9, 0.99), eps=1e-8):
-        self.net, self.lr, self.betas, self.eps = net, lr, betas, eps
-        self.m = self.v = self.t_dev = None
+        self.net, self._lr, self.betas, self.eps = net, float(lr), betas, eps
+        self.m = self.v = self.t_dev = self.lr_dev = None
+        self.hold = None
 
     def ready(self):
         if self.m is None:
@@ -45,12 +118,23 @@ class FlatAdam:
             self.m = ops.zero_(torch.empty_like(p))
             self.v = ops.zero_(torch.empty_like(p))
             self.t_dev = torch.zeros(1, dtype=torch.int32, device=p.device)      # completed steps
+            self.lr_dev = torch.full((1,), self._lr, dtype=torch.float32, device=p.device)
+
+    @property
+    def lr(self):
+        return self._lr
+
+    @lr.setter
+    def lr(self, value):
+        self._lr = float(value)
+        if self.lr_dev is not None:
+            self.lr_dev.fill_(self._lr)          # rounds to fp32 as the (float) cast of wtpse_adam's by-value lr does
 
     def step(self):
         net = self.net
         p, g = net.flat_params(), net.flat_grads()
         self.ready()
-        ops.adam_step(p, g, self.m, self.v, self.lr, self.betas[0], self.betas[1], self.eps, 1, self.t_dev)
+        ops.adam_step_dev(p, g, self.m, self.v, self.lr_dev, self.betas[0], self.betas[1], self.eps, 1, self.t_dev, self.hold)
         ops.counter_add(self.t_dev, 1)
         net.invalidate_packed()
         net.ensure_ready()
@@ -59,9 +143,43 @@ class FlatAdam:
     def t(self):
         return 0 if self.t_dev is None else int(self.t_dev.item())
 
+    def _shapes(self):
+        self.net.ensure_ready()
+        return [tuple(p.shape) for p in self.net._plist]      # net.parameters() order = the order of the flat buffer
+
+    def state_dict(self):
+        """torch.optim.Adam's layout (adam_state_to_torch), on the device of the network; synchronises (reads the step count)."""
+        self.ready()
+        return adam_state_to_torch(self.m, self.v, self.t, self._shapes(), self._lr, self.betas, self.eps)
+
+    def load_state_dict(self, sd):
+        """From a FlatAdam or a torch.optim.Adam over the same parameters.  Copies into the existing m, v, step count and learning
+        rate float: a step that has already been recorded stays valid.  betas / eps are passed to the kernel by value (frozen into
+        a recording), so a state with other values than this optimiser's is refused."""
+        self.ready()
+        g = sd["param_groups"][0] if sd.get("param_groups") else {}
+        for k, mine in (("betas", tuple(float(b) for b in self.betas)), ("eps", float(self.eps))):
+            theirs = g.get(k, mine)
+            theirs = tuple(float(b) for b in theirs) if k == "betas" else float(theirs)
+            if theirs != mine:
+                raise ValueError("the state was written with %s=%r, this optimiser has %r (passed by value, part of a recorded "
+                                 "step): construct the TrainStep with the state's value" % (k, theirs, mine))
+        t, g = adam_state_from_torch(sd, self._shapes(), self.m, self.v)
+        self.t_dev.fill_(int(t))
+        self.lr = g["lr"]
+
 
 class TrainStep:
-    def __init__(self, model_od, shape_od, model_oc, shape_oc, hparams, lr=5e-4, betas=(0.9, 0.99), dp=None, graph=False):
+    """lr: one rate for all four networks or the 4-tuple (od, od_shape, oc, oc_shape) of train.py:120-138.
+    log: optional loss log (wtpse_hip.trainer.LossLog over `TrainStep.log_names(hparams)`).  With one, every call A-D folds its
+    loss scalars into the log's device sums with one single-wave launch (wtpse_loss_log) as soon as they exist, calls A and C
+    evaluate the reference's NaN test (Trainer.py:794-800, 878-885), and every Adam launch takes the log's flag as `hold`: from the
+    first NaN iteration on no parameter and no Adam moment changes any more (the reference raises before backward(); here the
+    step never synchronises, so the flag is read by whoever reads the log).  BatchNorm running statistics, the step counts and
+    the Philox positions still advance.  With multi-turn > 1 a shape call logs its last turn only (Trainer.py:827-832).
+    Without a log (the default) not one extra launch is issued."""
+
+    def __init__(self, model_od, shape_od, model_oc, shape_oc, hparams, lr=5e-4, betas=(0.9, 0.99), dp=None, graph=False, log=None):
         self.hp = hparams
         self.full = bool(hparams['whitening'])
         self.nets = [model_od, model_oc] + ([shape_od, shape_oc] if self.full else [])
@@ -76,9 +194,20 @@ class TrainStep:
             object.__setattr__(n, "_defer_allreduce", True)  # the gradient exchange is issued here, between backward and Adam
         if dp is not None:
             dp.broadcast_params(self.nets)
-        self.opt = {id(n): FlatAdam(n, lr, betas) for n in self.nets}
+        lrs = tuple(lr) if isinstance(lr, (tuple, list)) else (lr,) * 4
+        if len(lrs) != 4:
+            raise ValueError("lr: one rate or the four (od, od_shape, oc, oc_shape), got %d values" % len(lrs))
+        self.by_key = {k: n for k, n in zip(NET_KEYS, (model_od, shape_od, model_oc, shape_oc)) if any(n is x for x in self.nets)}
+        # (keyed by network, looked up by id() everywhere: its order — NET_KEYS', not self.nets' — carries no meaning)
+        self.opt = {id(self.by_key[k]): FlatAdam(self.by_key[k], r, betas) for k, r in zip(NET_KEYS, lrs) if k in self.by_key}
+        self.log = log
+        if log is not None:
+            want = self.log_names(hparams)
+            if list(log.names) != want:
+                raise ValueError("the loss log's names must be TrainStep.log_names(hparams) = %s, got %s" % (want, list(log.names)))
         for o in self.opt.values():
             o.ready()
+            o.hold = None if log is None else log.flag
         self.last_od_pred = None
         # exact data-parallel mode runs ~100 small collectives inside every forward: it stays eager
         self.graph = bool(graph) and not (dp is not None and dp.exact)
@@ -104,20 +233,27 @@ class TrainStep:
                 pw = ops.pos_weight_from_sums(self.dp.allreduce_sum(sums))
             loss = ops.bce_logits_pw_fwd(out, od_pred, target, pw)
             d_out = ops.bce_logits_pw_bwd(out, od_pred, target, pw)
+        r = {"seg": loss}
+        if self.full:
+            r["ins"], r["dom"] = res[2][0], res[2][3]
+        # the reference's running sums and NaN test of this call (Trainer.py:788-800 / 874-885), in front of backward and Adam
+        self._log("seg_od" if od_pred is None else "seg_oc", list(r.values()), len(r), model)
         model._backward_update(tape, d_out, None, None, w_ins=gi, w_dom=gd)
         del tape
         yield model
         self.opt[id(model)].step()
-        r = {"seg": loss}
-        if self.full:
-            r["ins"], r["dom"] = res[2][0], res[2][3]
         return out, r
 
     def _shape_call(self, shape, model, x, target):
         gi, gd = float(self.hp['instance_wt_gm']), float(self.hp['domain_wt_gm'])
         r = None
-        for _ in range(int(self.hp['multi-turn'])):
+        turns = int(self.hp['multi-turn'])
+        for turn in range(turns):
             scal, tape = shape._forward_update(model, x, target, want_tape=True)
+            if turn == turns - 1:       # the last turn's values only (Trainer.py:827-832, 915-919); the shape losses are never NaN-tested
+                od = shape is self.shape_od
+                self._log("kd_od" if od else "kd_oc", [scal[0], scal[1], scal[2], scal[3], scal[4]] if od else [scal[0], scal[1], scal[4]],
+                          0, shape)
             shape._backward_update(tape, None, None, None, None, w_kd=1.0, w_off=gi, w_diag=gi, w_dom=gd)
             del tape
             yield shape
@@ -143,6 +279,19 @@ class TrainStep:
             rd = yield from self._shape_call(self.shape_oc, self.model_oc, roi, target_oc)
             res.update(kd_oc=rd["kd"], ins_shape_oc=rd["ins_total"], dom_shape_oc=rd["dom"])
         return res
+
+    @staticmethod
+    def log_names(hparams):
+        """The loss names in the order a LossLog for this step holds them: the keys of step()'s result, call by call (A-D)."""
+        if not bool(hparams['whitening']):
+            return ["seg_od", "seg_oc"]
+        return ["seg_od", "ins_od", "dom_od", "kd_od", "ins_shape_od", "ins_ij_od", "ins_ii_od", "dom_shape_od",
+                "seg_oc", "ins_oc", "dom_oc", "kd_oc", "ins_shape_oc", "dom_shape_oc"]
+
+    def _log(self, first, scalars, check_n, net):
+        """One wtpse_loss_log launch: `scalars` into the log's slots that start at name `first`."""
+        if self.log is not None:
+            ops.loss_log(scalars, self.log.acc, self.log.names.index(first), check_n, self.log.flag, self.opt[id(net)].t_dev)
 
     def _exchange(self, net):
         if self.dp is not None:
@@ -213,6 +362,42 @@ class TrainStep:
                 g.replay()
             if net is not None:
                 self._exchange(net)
+
+    # ------------------------------------------------------------------------------------------------ rates and state
+    def set_lr(self, od=None, od_shape=None, oc=None, oc_shape=None):
+        """New learning rates (None: unchanged) from the next step on, recorded or not: stream-ordered writes, no host sync."""
+        for k, r in zip(NET_KEYS, (od, od_shape, oc, oc_shape)):
+            if r is not None and k in self.by_key:
+                self.opt[id(self.by_key[k])].lr = r
+
+    def get_lr(self):
+        """{network key: rate} as last set (host values)."""
+        return {k: self.opt[id(n)].lr for k, n in self.by_key.items()}
+
+    def state_dict(self):
+        """What a run needs beside the networks' own state_dict()s to continue where it stopped: per network the optimiser state
+        (torch.optim.Adam's layout, FlatAdam.state_dict) and the Philox seed and position of its sampling noise.  Synchronises."""
+        return {"optim": {k: self.opt[id(n)].state_dict() for k, n in self.by_key.items()},
+                "noise": {k: {"seed": int(n._noise_seed), "ctr": int(n._noise_ctr.item())} for k, n in self.by_key.items()}}
+
+    def load_state_dict(self, sd):
+        """Restores everything in place (moments, step counts, learning rates, Philox positions), so a step that has already been
+        recorded stays valid and continues from the loaded state.  The Philox SEED is passed to the kernels by value and is frozen
+        into a recording: once this TrainStep holds one, a state with another seed is refused.  Load the networks' own
+        state_dict()s first: their packed weight copies are refreshed here (a replayed step does not look at them again)."""
+        if set(sd["optim"]) != set(self.by_key) or set(sd["noise"]) != set(self.by_key):
+            raise ValueError("the state holds the networks %s, this step trains %s" % (sorted(sd["optim"]), sorted(self.by_key)))
+        for k, n in self.by_key.items():
+            seed = int(sd["noise"][k]["seed"])
+            if seed != int(n._noise_seed) and self._graphs is not None:
+                raise ValueError("network %r: the state's Philox seed %d differs from the seed %d this TrainStep has recorded (the seed "
+                                 "is passed by value): seed the networks with seed_noise(%d) before the first step, or close() and "
+                                 "record again" % (k, seed, n._noise_seed, seed))
+        for k, n in self.by_key.items():
+            self.opt[id(n)].load_state_dict(sd["optim"][k])
+            n.ensure_ready()
+            object.__setattr__(n, "_noise_seed", int(sd["noise"][k]["seed"]))
+            n._noise_ctr.fill_(int(sd["noise"][k]["ctr"]))
 
     def close(self):
         """Release the native launch plans (and their hipEvents) of a recorded step."""

@@ -1,0 +1,309 @@
+"""The training run: counterpart of the reference's Trainer.train() / train_epoch() (Trainer.py:729-1060) around
+`step.py::TrainStep` — epochs, the per-epoch loss sums, the NaN stop, the learning-rate schedule, validation every N epochs,
+checkpoints a run can be continued from.
+
+What differs from the reference loop, and why it cannot change a result:
+  * no host synchronisation inside an epoch.  The reference reads every loss of every iteration with `.item()` (eleven times per
+    iteration) for its running sums and its NaN test; here one single-wave launch per update() call folds the call's loss scalars
+    into device doubles and evaluates the NaN test (wtpse_loss_log), and the host reads sums and flag ONCE per epoch.  A double
+    accumulator fed in iteration order holds the reference's running sums bit for bit.
+  * the NaN stop.  The reference raises before backward(); a run that never synchronises cannot, so the flag the NaN test raises
+    holds every later Adam launch (wtpse_adam_dev's `hold`): from the failing iteration on no parameter and no Adam moment
+    changes, and `train_epoch()` raises the reference's ValueError, naming the iteration, when it reads the log.  The flag is read
+    before every validation and before every file this module writes: nothing is ever written from a poisoned run.
+  * no tensorboard scalars, image grids, `code/` snapshot or yaml dump.
+
+Data-parallel runs are not covered here (`TrainStep`'s own `dp` path is).
+"""
+import csv
+import os
+import random
+import time
+from bisect import bisect_right
+
+import numpy as np
+import torch
+
+from .step import NET_KEYS, TrainStep
+from .validate import best_checkpoint
+
+CKPT_KEYS = ("model", "model_shape", "model_oc", "model_oc_shape")     # Trainer.py:282-288, in the order (od, od_shape, oc, oc_shape)
+
+
+def reference_lr(epoch, max_epoch, base_lr, warmup_factor=0.001, steps=(100, 150), gamma=0.5):
+    """Trainer.lr_update's arithmetic (Trainer.py:989-1004 with the constants of :1016-1021) in Python floats: the rate that
+    applies after `epoch` has been trained.  Quirks kept:
+      * `warmup_steps = 2 * max_epoch`: alpha = epoch / (2 * max_epoch) never reaches 1 inside a run, so the warm-up never
+        completes — at the last epoch the factor is still about one half;
+      * the reference gives the shape networks the SEGMENTATION networks' base rates (lr for optim_shape, lr_oc for
+        optim_shape_oc), not lr_shape / lr_oc_shape: `TrainRun(lr_schedule="reference")` does the same."""
+    alpha = epoch / (max_epoch * 2)
+    wf = warmup_factor * (1 - alpha) + alpha
+    return base_lr * wf * gamma ** bisect_right(steps, epoch)
+
+
+class LossLog:
+    """Device-side running sums of a step's losses plus the NaN flag (wtpse_loss_log): `acc` float64 [len(names)] and `flag`
+    int32 [2] = (raised, iteration) share one allocation, so read() is one device-to-host copy."""
+
+    def __init__(self, device, names):
+        self.names = list(names)
+        n = len(self.names)
+        self._buf = torch.zeros(n + 1, dtype=torch.float64, device=device)
+        self.acc = self._buf[:n]
+        self.flag = self._buf[n:].view(torch.int32)
+
+    def read(self):
+        """-> ({name: sum}, (nan, iteration)): synchronises with the stream (one copy)."""
+        host = self._buf.cpu()
+        n = len(self.names)
+        flag = host[n:].view(torch.int32).tolist()
+        return dict(zip(self.names, host[:n].tolist())), (bool(flag[0]), int(flag[1]))
+
+    def reset(self):
+        """Zero the sums (stream-ordered).  The flag is sticky: it is never cleared."""
+        self.acc.zero_()
+
+
+class FundusBatches:
+    """`next_batch` over an on-disk dataset: Trainer.get_multi_batch (Trainer.py:29-55) on `FundusTree`s, one per source domain,
+    with the per-sample transforms on the GPU (`DeviceInputPipeline`).  Per call: the domain list is shuffled with the run's
+    `random.Random` (Trainer.py:769), the sample indices come from its numpy generator (fundus_dataloader.py:90), the crop draws
+    from the `random.Random` again (custom_transforms.py:342-346), one sample after the other as the reference's loader does.
+    The reference shuffles its domain list in place, so every shuffle starts from the order the previous one left: that order
+    (`order`: positions into the datasets as they were given) is run state — `state()` / `load_state()`, which TrainRun's
+    checkpoints carry — and a feed built anew from the same datasets in the same order continues a run where it stopped."""
+
+    def __init__(self, datasets, batch_size, device, size=256):
+        from .input_pipeline import DeviceInputPipeline
+        self.datasets = list(datasets)
+        self.order = list(range(len(self.datasets)))
+        # Trainer.py:1011: per_domain_batch = batch_size // source_domain_num — a batch holds domains * per_domain samples
+        # (30 for the reference's batch_size 32 over three source domains)
+        self.batch_size = int(batch_size)
+        self.per_domain = self.batch_size // len(self.datasets)
+        if self.per_domain < 1:
+            raise ValueError("batch_size %d is smaller than the number of source domains (%d)" % (batch_size, len(self.datasets)))
+        self.size = int(size)
+        self.pipe = DeviceInputPipeline(size, device)
+
+    def __len__(self):
+        """Trainer.py:1013-1014: iterations per epoch = total samples // batch size."""
+        return sum(len(d) for d in self.datasets) // self.batch_size
+
+    def __call__(self, py_rng, np_rng):
+        from .fundus_data import multi_batch
+        from .input_pipeline import draw
+        py_rng.shuffle(self.order)
+        images, masks = multi_batch([self.datasets[i] for i in self.order], self.per_domain, np_rng)
+        return self.pipe(images, masks, [draw(py_rng, self.size) for _ in images])
+
+    def state(self):
+        return {"order": list(self.order)}
+
+    def load_state(self, state):
+        order = [int(i) for i in state["order"]]
+        if sorted(order) != list(range(len(self.datasets))):
+            raise ValueError("the saved domain order %s is not a permutation of this feed's %d datasets" % (order, len(self.datasets)))
+        self.order = order
+
+
+def _py_state_to_lists(state):
+    version, words, gauss = state
+    return [int(version), [int(w) for w in words], -1.0 if gauss is None else float(gauss), gauss is not None]
+
+
+def _py_state_from_lists(s):
+    return (int(s[0]), tuple(int(w) for w in s[1]), float(s[2]) if s[3] else None)
+
+
+def _np_state_to_lists(state):
+    name, keys, pos, has_gauss, cached = state
+    return [str(name), torch.from_numpy(np.asarray(keys, dtype=np.int64)), int(pos), int(has_gauss), float(cached)]
+
+
+def _np_state_from_lists(s):
+    return (str(s[0]), np.asarray(s[1].tolist(), dtype=np.uint32), int(s[2]), int(s[3]), float(s[4]))
+
+
+class TrainRun:
+    """Trainer.train() for the four networks of train.py:91-138.
+
+    next_batch(py_rng, np_rng) -> (image [B,3,H,W], target_od [B,1,H,W], target_oc [B,1,H,W]) device fp32; the run owns the two
+    host generators (`random.Random(seed)`: crop draws and the per-iteration shuffle of the domain list; `numpy.random.
+    RandomState(seed)`: sample indices) and hands them to every call.  A feed that keeps state of its own between calls exposes it
+    as `state()` -> plain data / `load_state(state)` (`FundusBatches`: the order of its domain list); checkpoints carry it, so a
+    resumed run draws what the uninterrupted one would.
+    lr: the four base rates (od, od_shape, oc, oc_shape) or one for all.  lr_schedule: None (the reference's default: its call of
+    lr_update is commented out, Trainer.py:1040) or "reference" (`reference_lr` after every epoch, from the next epoch on).
+    val_batches: a sequence, or a callable returning an iterable, of (image, label_od, label_oc); validator: a `validate.Validator`.
+    checkpoint_every: write out_dir/run_checkpoint.pth.tar after every that many epochs (0: never).
+    """
+
+    def __init__(self, model_od, shape_od, model_oc, shape_oc, hparams, next_batch, iter_per_epoch, max_epoch, lr=(1e-3, 1e-3, 1e-3, 1e-3),
+                 stop_epoch=-1, val_batches=None, validator=None, interval_validate=10, lr_schedule=None, out_dir=None, graph="plan",
+                 seed=0, checkpoint_every=0, betas=(0.9, 0.99)):
+        if lr_schedule not in (None, "reference"):
+            raise ValueError("lr_schedule must be None or 'reference', got %r" % (lr_schedule,))
+        if (val_batches is None) != (validator is None):
+            raise ValueError("validation needs both val_batches and a Validator")
+        self.nets = (model_od, shape_od, model_oc, shape_oc)
+        self.hp = hparams
+        self.base_lr = tuple(float(r) for r in (lr if isinstance(lr, (tuple, list)) else (lr,) * 4))
+        self.next_batch, self.iter_per_epoch, self.max_epoch, self.stop_epoch = next_batch, int(iter_per_epoch), int(max_epoch), int(stop_epoch)
+        self.val_batches, self.validator, self.interval_validate = val_batches, validator, int(interval_validate)
+        self.lr_schedule, self.out_dir, self.seed, self.checkpoint_every = lr_schedule, out_dir, int(seed), int(checkpoint_every)
+        self.graph, self.betas = graph, tuple(float(b) for b in betas)
+        self.py_rng, self.np_rng = random.Random(self.seed), np.random.RandomState(self.seed)
+        device = next(model_od.parameters()).device
+        self.log = LossLog(device, TrainStep.log_names(hparams))
+        self.train_step = TrainStep(model_od, shape_od, model_oc, shape_oc, hparams, lr=self.base_lr, betas=betas, graph=graph, log=self.log)
+        self.epoch = 0                 # epochs completed = index of the epoch train_epoch() runs next
+        self.iteration = 0             # iterations completed
+        self.last = None               # what the last train_epoch() returned
+        self.best = [0, 0, 0, 0, 0, 0]  # the six values of the best validation so far (what train() returns)
+        if out_dir is not None:
+            os.makedirs(out_dir, exist_ok=True)
+
+    # ------------------------------------------------------------------------------------------------ one epoch
+    def _raise_if_nan(self, flag):
+        if flag[0]:
+            raise ValueError("loss is nan while training (iteration %d)" % flag[1])
+
+    def check(self):
+        """Reads the NaN flag (one small copy, synchronises) and raises the reference's error when it is set."""
+        self._raise_if_nan(self.log.read()[1])
+
+    def train_epoch(self):
+        """`iter_per_epoch` steps without a host synchronisation, then ONE read of the loss log.  Raises
+        ValueError('loss is nan while training ...') naming the 0-based iteration when the NaN test of Trainer.py:794-800 / 878-885
+        has held (`epoch` and `iteration` then stay where the epoch began).  -> {"epoch", "sums": {name: float}, "means": {name: sum / iter_per_epoch}, "lr": {key: rate}, "seconds"}.
+        (The reference divides SOME of its sums by len(self.train_loader), the number of source domains, and prints others
+        undivided, Trainer.py:974-987; that print-only quirk is not reproduced: every mean here is over the iterations.)"""
+        for n in self.nets:
+            if n is not None:
+                n.train()
+        start = time.perf_counter()
+        self.log.reset()
+        for _ in range(self.iter_per_epoch):
+            image, target_od, target_oc = self.next_batch(self.py_rng, self.np_rng)
+            self.train_step.step(image, target_od, target_oc)
+        sums, flag = self.log.read()
+        self._raise_if_nan(flag)
+        self.iteration += self.iter_per_epoch
+        seconds = time.perf_counter() - start
+        self.last = {"epoch": self.epoch, "sums": sums, "means": {k: v / self.iter_per_epoch for k, v in sums.items()},
+                     "lr": self.train_step.get_lr(), "seconds": seconds}
+        if self.out_dir is not None:
+            path = os.path.join(self.out_dir, "train_log.csv")
+            new = not os.path.isfile(path)
+            with open(path, "a", newline="") as f:
+                w = csv.writer(f)
+                if new:
+                    w.writerow(["epoch", "iteration"] + self.log.names + ["lr_" + k for k in NET_KEYS] + ["seconds"])
+                w.writerow([self.epoch, self.iteration] + [repr(self.last["means"][k]) for k in self.log.names]
+                           + [repr(self.last["lr"].get(k, "")) for k in NET_KEYS] + ["%.3f" % seconds])
+        self.epoch += 1
+        return self.last
+
+    # ------------------------------------------------------------------------------------------------ the run
+    def train(self):
+        """Trainer.py:1025-1056 in its order: train the epoch; stop when `stop_epoch == epoch` (before its validation); the
+        schedule; validate when (epoch + 1) % interval_validate == 0 and epoch > 2.  -> the six best values in the reference's
+        order [cup_dice, cup_hd, cup_asd, disc_dice, disc_hd, disc_asd] (zeros while no validation has improved;
+        they travel with a checkpoint, so a resumed run that finds no new best returns the earlier one)."""
+        for epoch in range(self.epoch, self.max_epoch):
+            self.train_epoch()
+            if self.stop_epoch == epoch:
+                print("Stop epoch at %d" % self.stop_epoch)
+                break
+            if self.lr_schedule == "reference":
+                od = reference_lr(epoch, self.max_epoch, self.base_lr[0])
+                oc = reference_lr(epoch, self.max_epoch, self.base_lr[2])
+                self.train_step.set_lr(od=od, od_shape=od, oc=oc, oc_shape=oc)
+            if self.validator is not None and (epoch + 1) % self.interval_validate == 0 and epoch > 2:
+                self.check()
+                batches = self.val_batches() if callable(self.val_batches) else self.val_batches
+                r = self.validator(epoch, *self.nets, batches)
+                if r[0] == 1:
+                    self.best = [float(v) for v in r[1:]]
+            if self.checkpoint_every > 0 and self.out_dir is not None and (epoch + 1) % self.checkpoint_every == 0:
+                self.save(os.path.join(self.out_dir, "run_checkpoint.pth.tar"))
+        return list(self.best)
+
+    # ------------------------------------------------------------------------------------------------ checkpoints
+    def config(self):
+        return {"lr": list(self.base_lr), "iter_per_epoch": self.iter_per_epoch, "max_epoch": self.max_epoch, "stop_epoch": self.stop_epoch,
+                "interval_validate": self.interval_validate, "lr_schedule": self.lr_schedule or "", "seed": self.seed,
+                "checkpoint_every": self.checkpoint_every, "graph": self.graph, "betas": list(self.betas)}
+
+    def state(self):
+        """Everything save() writes, as tensors, numbers, strings, lists and dicts only (torch.load(weights_only=True) reads it):
+        the four networks under the best-Dice checkpoint's four keys (test_visulization.py:132-193's filtered load reads a run
+        checkpoint too), TrainStep.state_dict(), epochs and iterations completed, the Validator's best and its six values, both host
+        generators, the feed's own state (when `next_batch` has one), the last epoch's loss sums."""
+        self.check()
+        d = best_checkpoint(*self.nets) if all(n is not None for n in self.nets) else \
+            {k: n.state_dict() for k, n in zip(CKPT_KEYS, self.nets) if n is not None}
+        d.update(train_step=self.train_step.state_dict(), epoch=self.epoch, iteration=self.iteration, config=self.config(),
+                 best_mean_dice=float(self.validator.best_mean_dice) if self.validator is not None else 0.0,
+                 best_epoch=int(self.validator.best_epoch) if self.validator is not None else -1,
+                 py_rng=_py_state_to_lists(self.py_rng.getstate()), np_rng=_np_state_to_lists(self.np_rng.get_state()),
+                 loss_sums=dict(self.last["sums"]) if self.last is not None else {},
+                 loss_names=list(self.log.names), best=list(self.best),
+                 feed=self.next_batch.state() if hasattr(self.next_batch, "state") else {})
+        return d
+
+    def save(self, path):
+        """Written to a temporary name beside `path` and moved into place (os.replace): a run that is killed while it writes leaves
+        the previous checkpoint whole.  Refuses (the reference's ValueError) when the NaN flag is set."""
+        d = self.state()
+        tmp = "%s.tmp%d" % (path, os.getpid())
+        torch.save(d, tmp)
+        os.replace(tmp, path)
+
+    @classmethod
+    def load(cls, path, model_od, shape_od, model_oc, shape_oc, hparams, next_batch, **kw):
+        """A TrainRun that continues the run `path` was saved from: the networks (new ones, or live ones) receive the saved weights
+        and buffers, the constructor arguments that save() recorded (rates, epochs, seed, ...) are the defaults of `kw`."""
+        d = torch.load(path, map_location="cpu", weights_only=True)
+        cfg = dict(d["config"])
+        cfg["lr_schedule"] = cfg["lr_schedule"] or None
+        cfg["lr"], cfg["betas"] = tuple(cfg["lr"]), tuple(cfg["betas"])
+        cfg.update(kw)
+        for key, n in zip(CKPT_KEYS, (model_od, shape_od, model_oc, shape_oc)):
+            if n is not None:
+                n.load_state_dict(d[key])
+        run = cls(model_od, shape_od, model_oc, shape_oc, hparams, next_batch, **cfg)
+        run.restore(d)
+        return run
+
+    def restore(self, d):
+        """The non-network part of a checkpoint, in place (also into a run whose step is already recorded).  Lines of
+        out_dir/train_log.csv for epochs the checkpoint has not seen (a run killed after an epoch's line and before its checkpoint)
+        are dropped: the resumed run writes them again."""
+        self.train_step.load_state_dict(d["train_step"])
+        self.epoch, self.iteration = int(d["epoch"]), int(d["iteration"])
+        if self.validator is not None:
+            self.validator.best_mean_dice, self.validator.best_epoch = float(d["best_mean_dice"]), int(d["best_epoch"])
+        self.py_rng.setstate(_py_state_from_lists(d["py_rng"]))
+        self.np_rng.set_state(_np_state_from_lists(d["np_rng"]))
+        self.best = [float(v) for v in d["best"]]
+        if d["feed"]:
+            if not hasattr(self.next_batch, "load_state"):
+                raise ValueError("the checkpoint carries the state of its batch feed (%s) and this run's next_batch cannot take it"
+                                 % sorted(d["feed"]))
+            self.next_batch.load_state(d["feed"])
+        path = os.path.join(self.out_dir, "train_log.csv") if self.out_dir is not None else None
+        if path is not None and os.path.isfile(path):
+            with open(path, newline="") as f:
+                rows = list(csv.reader(f))
+            keep = rows[:1] + [r for r in rows[1:] if int(r[0]) < self.epoch]
+            if len(keep) != len(rows):
+                tmp = "%s.tmp%d" % (path, os.getpid())
+                with open(tmp, "w", newline="") as f:
+                    csv.writer(f).writerows(keep)
+                os.replace(tmp, path)
+        if d["loss_sums"]:
+            self.last = {"epoch": self.epoch - 1, "sums": dict(d["loss_sums"]),
+                         "means": {k: v / self.iter_per_epoch for k, v in d["loss_sums"].items()}, "lr": self.train_step.get_lr(), "seconds": 0.0}
