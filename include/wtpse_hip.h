@@ -446,6 +446,24 @@ int wtpse_postprocess(const float* logit, unsigned char* out, void* ws, float th
 int wtpse_seg_metrics_ws(int B, int h, int w);
 int wtpse_seg_metrics(const unsigned char* mask, const float* label, long long* rec, void* ws, int B, int h, int w, void* stream);
 
+/* ---- test run (csrc/overlay.hip; test_visulization.py:238-269, utils.py:371-463) --------------------------------------- */
+/* The per-image pictures of the reference's test program, a batch at a time.  img [B][3][h][w] fp32: the normalised image at the
+ * label size; pred_od / pred_oc [B][h][w] uint8: wtpse_postprocess's masks; gt_od / gt_oc [B][h][w] uint8 labels, 0 / 1.
+ * original [B][h][w][3] uint8 = (img + 1) * 127.5 (two fp32 roundings) truncated; overlay [B][h][w][3] = the same with the contours
+ * painted: composite channel 0 = cup, channel 1 = disc OR cup; the prediction's channels with their border rows and columns zeroed,
+ * green for channel 1 then blue for channel 0; the ground truth's channels through largest-component + hole filling
+ * (wtpse_postprocess on a +-30 pseudo-logit), red, on top.  A contour vertex sits between every two 4-adjacent pixels that differ
+ * and paints seven pixels around itself; an index of -1 wraps as numpy's does, an index of h or w (the reference raises IndexError:
+ * ground truth touching the last row / column) is dropped.  ws: wtpse_overlay_ws(B, h, w) 4-byte words, 8-byte aligned; img,
+ * original, overlay 4-byte aligned.  2 <= h, w <= 4096. */
+int wtpse_overlay_ws(int B, int h, int w);
+int wtpse_overlay(const float* img, const unsigned char* pred_od, const unsigned char* pred_oc, const unsigned char* gt_od,
+                  const unsigned char* gt_oc, unsigned char* original, unsigned char* overlay, void* ws, int B, int h, int w,
+                  void* stream);
+/* The test feed's labels at their original size (fundus_dataloader.py:112-134): mask [n] uint8 grey levels ->
+ * od [n] = (mask <= 200), oc [n] = (mask <= 50), fp32. */
+int wtpse_label_thresholds(const unsigned char* mask, float* od, float* oc, long long n, void* stream);
+
 /* ---- small utilities ------------------------------------------------------------------------------------------- */
 int wtpse_relu_mask(const float* dz, const float* ref, float* dy, int accumulate, long long n, void* stream);
 int wtpse_axpy(float* dst, const float* src, float alpha, long long n, void* stream);

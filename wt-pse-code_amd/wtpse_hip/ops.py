@@ -920,3 +920,38 @@ def seg_metrics(mask, label):
     ws = workspace("seg_metrics", words, mask.device)
     L.call("wtpse_seg_metrics", ptr(mask), ptr(label), ptr(rec), ptr(ws), B, h, w, stream_ptr())
     return rec
+
+
+# ----------------------------------------------------------------------------------------------- test run
+def overlay(img, pred_od, pred_oc, gt_od, gt_oc):
+    """The pictures of the reference's test program on the device (csrc/overlay.hip; test_run.overlay_host byte for byte):
+    img [B,3,h,w] fp32 (normalised, at the label size), pred_od / pred_oc [B,1,h,w] uint8 (postprocess_masks), gt_od / gt_oc
+    [B,1,h,w] uint8 labels 0 / 1 -> (original, overlay), each uint8 [B,h,w,3]."""
+    _chk(img, "img")
+    if img.dim() != 4 or img.shape[1] != 3:
+        raise ValueError("img must be [B,3,h,w] (got %s)" % (tuple(img.shape),))
+    B, _, h, w = img.shape
+    for t, name in ((pred_od, "pred_od"), (pred_oc, "pred_oc"), (gt_od, "gt_od"), (gt_oc, "gt_oc")):
+        _chk_dev(t, name, torch.uint8)
+        if tuple(t.shape) != (B, 1, h, w) or t.device != img.device:
+            raise ValueError("%s %s (%s) does not match img %s (%s)" % (name, tuple(t.shape), t.device, tuple(img.shape), img.device))
+    L = lib()
+    words = L.query("wtpse_overlay_ws", B, h, w)
+    if words <= 0:
+        raise ValueError("overlay: unsupported size %s (2 <= h, w <= 4096)" % (tuple(img.shape),))
+    original = torch.empty((B, h, w, 3), dtype=torch.uint8, device=img.device)
+    over = torch.empty((B, h, w, 3), dtype=torch.uint8, device=img.device)
+    ws = workspace("overlay", words, img.device)
+    L.call("wtpse_overlay", ptr(img), ptr(pred_od), ptr(pred_oc), ptr(gt_od), ptr(gt_oc), ptr(original), ptr(over), ptr(ws), B, h, w,
+           stream_ptr())
+    return original, over
+
+
+def label_thresholds(mask):
+    """Grey-level masks uint8 [B,1,h,w] -> (original_od, original_oc) fp32 [B,1,h,w]: 1 where the byte is <= 200 / <= 50
+    (fundus_dataloader.py:112-134)."""
+    _chk_dev(mask, "mask", torch.uint8)
+    od = torch.empty(mask.shape, dtype=torch.float32, device=mask.device)
+    oc = torch.empty(mask.shape, dtype=torch.float32, device=mask.device)
+    lib().call("wtpse_label_thresholds", ptr(mask), ptr(od), ptr(oc), mask.numel(), stream_ptr())
+    return od, oc

@@ -165,13 +165,14 @@ def _device_records(pred, pred_oc, label_od, label_oc, threshold=0.75):
     return ops.seg_metrics(masks, labels).cpu().numpy()         # the one device -> host copy
 
 
-def device_metrics(pred, pred_oc, label_od, label_oc, threshold=0.75):
-    """Per-image {disc_dice, cup_dice, disc_hd, disc_asd, cup_hd, cup_asd} (lists, batch order) of one validation batch computed
-    on the GPU: pred / pred_oc [B,1,h,w] logits, label_od / label_oc [B,1,h,w] labels (nonzero = object), all device tensors.
-    Raises the host path's RuntimeError for an empty label under a non-empty prediction (cup before disc, image by image)."""
-    B = pred.shape[0]
-    rec = _device_records(pred, pred_oc, label_od, label_oc, threshold)
-    out = {k: [] for k in ("disc_dice", "cup_dice", "disc_hd", "disc_asd", "cup_hd", "cup_asd")}
+METRIC_KEYS = ("disc_dice", "cup_dice", "disc_hd", "disc_asd", "cup_hd", "cup_asd")
+
+
+def finish_records(rec, B):
+    """Host records [2B, 8] (disc images first, then cup) -> per-image {disc_dice, cup_dice, disc_hd, disc_asd, cup_hd, cup_asd}
+    (lists, batch order).  Raises the host path's RuntimeError for an empty label under a non-empty prediction (cup before disc,
+    image by image)."""
+    out = {k: [] for k in METRIC_KEYS}
     for i in range(B):
         out["disc_dice"].append(_finish_dice(rec[i]))
         out["cup_dice"].append(_finish_dice(rec[B + i]))
@@ -184,6 +185,58 @@ def device_metrics(pred, pred_oc, label_od, label_oc, threshold=0.75):
     return out
 
 
+def device_metrics(pred, pred_oc, label_od, label_oc, threshold=0.75):
+    """Per-image {disc_dice, cup_dice, disc_hd, disc_asd, cup_hd, cup_asd} (lists, batch order) of one validation batch computed
+    on the GPU: pred / pred_oc [B,1,h,w] logits, label_od / label_oc [B,1,h,w] labels (nonzero = object), all device tensors.
+    Raises the host path's RuntimeError for an empty label under a non-empty prediction (cup before disc, image by image)."""
+    return finish_records(_device_records(pred, pred_oc, label_od, label_oc, threshold), pred.shape[0])
+
+
+def host_metrics(pred, pred_oc, label_od, label_oc, masks=None):
+    """The same per-image lists on the host, as Trainer.validate's inner loop scores an image (Trainer.py:214-239): post-processing,
+    Dice of both classes, then the cup's surface metrics, then the disc's.  masks: [(post, post_oc)] per image when the caller has
+    post-processed already (the test run paints them too)."""
+    lod, loc = label_od.cpu().numpy(), label_oc.cpu().numpy()
+    out = {k: [] for k in METRIC_KEYS}
+    for i in range(pred.shape[0]):
+        post, post_oc = masks[i] if masks is not None else (postprocess(pred[i])[0], postprocess(pred_oc[i])[0])
+        out["disc_dice"].append(dice(post, lod[i, 0]))
+        out["cup_dice"].append(dice(post_oc, loc[i, 0]))
+        hd, a = surface_metrics(post_oc, loc[i, 0])
+        out["cup_hd"].append(hd)
+        out["cup_asd"].append(a)
+        hd, a = surface_metrics(post, lod[i, 0])
+        out["disc_hd"].append(hd)
+        out["disc_asd"].append(a)
+    return out
+
+
+def batch_metrics(pred, pred_oc, label_od, label_oc, metrics="host"):
+    """Per-image metric lists of one batch on the chosen side: what validate_epoch sums and test_run.TestRun tabulates."""
+    if metrics == "device":
+        return device_metrics(pred, pred_oc, label_od, label_oc)
+    return host_metrics(pred, pred_oc, label_od, label_oc)
+
+
+class MetricMeans:
+    """Running per-image sums in arrival order -> the means validate_epoch returns (sum / max(n, 1), plus n)."""
+
+    def __init__(self):
+        self.acc = dict(cup_dice=0.0, disc_dice=0.0, cup_hd=0.0, disc_hd=0.0, cup_asd=0.0, disc_asd=0.0)
+        self.total = 0
+
+    def add(self, m):
+        for i in range(len(m["disc_dice"])):
+            for k in self.acc:
+                self.acc[k] += m[k][i]
+            self.total += 1
+
+    def means(self):
+        out = {k: v / max(self.total, 1) for k, v in self.acc.items()}
+        out["n"] = self.total
+        return out
+
+
 def validate_epoch(model, model_shape, model_oc, model_shape_oc, batches, metrics="host"):
     """One pass of Trainer.validate's loop (Trainer.py:152-249) -> per-image means
     {cup_dice, disc_dice, cup_hd, disc_hd, cup_asd, disc_asd, n}.  batches: iterable of (image [B,3,H,W] device,
@@ -194,36 +247,15 @@ def validate_epoch(model, model_shape, model_oc, model_shape_oc, batches, metric
     modes = [n.training for n in nets]
     for n in nets:
         n.eval()
-    acc = dict(cup_dice=0.0, disc_dice=0.0, cup_hd=0.0, disc_hd=0.0, cup_asd=0.0, disc_asd=0.0)
-    total = 0
+    acc = MetricMeans()
     try:
         for image, label_od, label_oc in batches:
             pred, pred_oc = predict_pair(model, model_shape, model_oc, model_shape_oc, image, label_od.shape[2:])
-            if metrics == "device":
-                m = device_metrics(pred, pred_oc, label_od, label_oc)
-                for i in range(pred.shape[0]):
-                    for k in ("disc_dice", "cup_dice", "cup_hd", "cup_asd", "disc_hd", "disc_asd"):
-                        acc[k] += m[k][i]
-                    total += 1
-                continue
-            lod, loc = label_od.cpu().numpy(), label_oc.cpu().numpy()
-            for i in range(pred.shape[0]):
-                post, post_oc = postprocess(pred[i])[0], postprocess(pred_oc[i])[0]
-                acc["disc_dice"] += dice(post, lod[i, 0])
-                acc["cup_dice"] += dice(post_oc, loc[i, 0])
-                hd, a = surface_metrics(post_oc, loc[i, 0])
-                acc["cup_hd"] += hd
-                acc["cup_asd"] += a
-                hd, a = surface_metrics(post, lod[i, 0])
-                acc["disc_hd"] += hd
-                acc["disc_asd"] += a
-                total += 1
+            acc.add(batch_metrics(pred, pred_oc, label_od, label_oc, metrics))
     finally:
         for n, m in zip(nets, modes):
             n.train(m)
-    out = {k: v / max(total, 1) for k, v in acc.items()}
-    out["n"] = total
-    return out
+    return acc.means()
 
 
 def best_checkpoint(model, model_shape, model_oc, model_shape_oc):
