@@ -182,6 +182,14 @@ int wtpse_dgrad_bnb_coef(const float* dy, int C, const void* wpacked, int layout
                          float* stats, const float* gamma, const float* invstd, float* coef, float* dgamma, float* dbeta,
                          int accumulate, double* partial2, unsigned* tickets, int B, int H, int W, int Cout, int ksize,
                          const unsigned* in_amax, void* stream);      /* in_amax: of dy, used by layout 1 (see wtpse_x3_terms) */
+/* The same into a BatchNorm on frozen statistics (see wtpse_bn_bwd_frozen below): bn_mean / invstd = the running mean and
+ * 1 / sqrt(running_var + eps); the tail leaves coef = (k1, 0, 0) and also writes dbias [Cbn] (+)=, the gradient of the bias of the
+ * convolution in front of that BatchNorm. */
+int wtpse_dgrad_bnb_coef_frozen(const float* dy, int C, const void* wpacked, int layout, float* out0, float* out1, int Csplit,
+                                const float* bn_y, const float* bn_ss, const float* bn_mean, int bn_relu, int bn_c0, int bn_c1,
+                                float* stats, const float* gamma, const float* invstd, float* coef, float* dgamma, float* dbeta,
+                                float* dbias, int accumulate, double* partial2, unsigned* tickets, int B, int H, int W, int Cout,
+                                int ksize, const unsigned* in_amax, void* stream);
 
 /* dW[Cout][C0+C1][k][k] (+)= sum dY * X, dbias (+)= sum dY (dbias/dbias_slab NULL: skip).  slab: [ksplit][Cout*Cin*k*k],
  * dbias_slab: [ksplit][Cout], ksplit = wtpse_wgrad_ksplit(...).  x inputs take the same prologue as the forward. */
@@ -265,6 +273,33 @@ int wtpse_bn_bwd_finalize_coef(const float* stats_partial, int nblk, int C, long
                                int accumulate, void* stream);
 /* dy = k1 * g + k2 * y + k3 with coef [C][3] from wtpse_dgrad_bnb_coef. */
 int wtpse_bn_bwd_apply_coef(const float* g, const float* y, const float* coef, float* dy, int B, int C, int HW, unsigned* amax, void* stream);
+
+/* ---- backward through an EVAL-mode BatchNorm ("frozen" statistics: module.eval() followed by update() and backward(),
+ *      algorithms.py:1238, shape_networks.py:524-526 — the module mode changes nothing but BatchNorm) ---------------------------
+ * z = act(s y + beta - s m) with s = gamma r, m = running_mean, r = 1 / sqrt(running_var + eps); g = dz [z > 0]:
+ *   dy = s g,  dbeta = sum g,  dgamma = r sum g (y - m),  d(bias of the conv in front) = s sum g.
+ * The entry points below are the train-mode ones above with mean / invstd = m / r: the same partials, the same fixed-order fp64
+ * folds (no float atomics: two runs agree bitwise), the two terms through the batch statistics dropped (coef = (k1, 0, 0), so the
+ * consumers that form dy on load — wtpse_upsample2x_bwd_bn, wtpse_conv_wgrad_r_bn — take it as it is) and `dbias` [C] written (+)=.
+ * The partials of wtpse_dgrad_bnb / wtpse_dgrad_x3_bnb / wtpse_conv16_x3 / wtpse_maxpool2_bwd_bnb are formed with mean = m.
+ * A gradient that is written fills its amax table (ZERO on entry) as wtpse_bn_bwd_apply_coef does. */
+/* wtpse_bn_eval_coeffs that also emits (m, r): what the backward takes in place of the saved batch statistics.  scale_shift has
+ * the bits wtpse_bn_eval_coeffs gives. */
+int wtpse_bn_eval_coeffs_stats(const float* gamma, const float* beta, const float* running_mean, const float* running_var,
+                               float eps, int C, float* scale_shift, float* save_mean, float* save_invstd, void* stream);
+/* wtpse_bn_bwd: dz -> dgamma, dbeta, dbias, dy = k1 * dz [z > 0] (the fp32 product).  partial, coef: as there. */
+int wtpse_bn_bwd_frozen(const float* dz, const float* y, const float* scale_shift, int relu, const float* gamma,
+                        const float* mean, const float* invstd, float* partial, float* coef, float* dgamma, float* dbeta,
+                        float* dbias, int accumulate, float* dy, int B, int C, int HW, unsigned* amax, void* stream);
+/* wtpse_bn_bwd_from_stats: g already masked, stats_partial [nblk][C][2] = (sum g, sum g (y - m)); y is not needed: dy = k1 * g. */
+int wtpse_bn_bwd_from_stats_frozen(const float* g, const float* stats_partial, int nblk, const float* gamma, const float* invstd,
+                                   float* coef, float* dgamma, float* dbeta, float* dbias, int accumulate, float* dy, int B, int C,
+                                   int HW, unsigned* amax, void* stream);
+/* wtpse_bn_bwd_finalize_coef: the fold alone -> coef = (k1, 0, 0), dgamma / dbeta / dbias (+)=. */
+int wtpse_bn_bwd_finalize_coef_frozen(const float* stats_partial, int nblk, int C, const float* gamma, const float* invstd,
+                                      float* coef, float* dgamma, float* dbeta, float* dbias, int accumulate, void* stream);
+/* wtpse_bn_bwd_apply_coef for such a coef: dy = k1 * g, a third less traffic (y is not read). */
+int wtpse_bn_bwd_scale_coef(const float* g, const float* coef, float* dy, int B, int C, int HW, unsigned* amax, void* stream);
 
 /* ---- WT (whitening) loss: compute_whitening_loss + compute_MMD (algorithms.py:1277-1309,59-121;
  *      shape_networks.py:561-594,240-309) ------------------------------------------------------------------------ */

@@ -2,6 +2,7 @@
 """What the training-run driver costs (wtpse_hip/trainer.py; numbers in profiles/trainer_driver.md).
 
     python tools/bench_trainer.py                 ms/step of TrainStep(graph="plan") with and without a LossLog, alternating
+    python tools/bench_trainer.py --freeze-bn     ms/step of TrainStep(graph="plan") on batch statistics and on frozen ones (freeze_bn=True), alternating
     python tools/bench_trainer.py --end-to-end    images/s of TrainRun.train_epoch() fed from a synthetic PNG tree, beside the bare step
     rocprofv3 --kernel-trace --stats -d DIR -- python tools/bench_trainer.py --adam-only [--tree PARENT_CHECKOUT]
                                                   Adam launches alone, for the per-call time of the kernel in a trace of its own
@@ -25,6 +26,7 @@ ap.add_argument("--end-to-end", action="store_true")
 ap.add_argument("--epochs", type=int, default=3)
 ap.add_argument("--iters", type=int, default=40, help="iterations per epoch of the end-to-end run")
 ap.add_argument("--adam-only", action="store_true")
+ap.add_argument("--freeze-bn", action="store_true", help="the step on frozen BatchNorm statistics beside the train-mode step")
 ap.add_argument("--tree", default=None, help="import the package from this checkout (e.g. an export of the parent commit)")
 args = ap.parse_args()
 
@@ -77,6 +79,27 @@ def step_with_and_without_log():
     sums, flag = variants["logged"].log.read()
     out = {"what": "TrainStep(graph='plan') ms/step, B=%d %dx%d, %d steps per block" % (B, args.size, args.size, args.steps),
            "plain": spread(ms["plain"]), "logged": spread(ms["logged"]), "nan_flag": flag[0],
+           "images_per_s": {k: round(1e3 * B / sorted(v)[len(v) // 2], 2) for k, v in ms.items()}}
+    print(json.dumps(out))
+
+
+def step_frozen_and_train():
+    B = args.batch
+    batch = make_batch(B, args.size, args.size, DEV, seed=1)
+    variants = {}
+    for name in ("train", "frozen"):
+        nets = bench.build_nets(HP, B // 3, DEV)
+        ts = TrainStep(*nets, HP, graph="plan", freeze_bn=name == "frozen")
+        for _ in range(args.warmup):
+            ts.step(*batch)
+        torch.cuda.synchronize()
+        variants[name] = ts
+    ms = {k: [] for k in variants}
+    for _ in range(args.rounds):
+        for name, ts in variants.items():
+            ms[name].append(timed(lambda: ts.step(*batch), args.steps))
+    out = {"what": "TrainStep(graph='plan') ms/step, B=%d %dx%d, %d steps per block" % (B, args.size, args.size, args.steps),
+           "train": spread(ms["train"]), "frozen": spread(ms["frozen"]),
            "images_per_s": {k: round(1e3 * B / sorted(v)[len(v) // 2], 2) for k, v in ms.items()}}
     print(json.dumps(out))
 
@@ -139,6 +162,8 @@ def adam_only():
 if __name__ == "__main__":
     if args.adam_only:
         adam_only()
+    elif args.freeze_bn:
+        step_frozen_and_train()
     elif args.end_to_end:
         end_to_end()
     else:

@@ -72,13 +72,17 @@ __global__ __launch_bounds__(NT) void bn_finalize_k(const float* __restrict__ pa
 
 __global__ void bn_eval_coeffs_k(const float* __restrict__ gamma, const float* __restrict__ beta,
                                  const float* __restrict__ rmean, const float* __restrict__ rvar, float eps, int C,
-                                 float* __restrict__ scale_shift) {
+                                 float* __restrict__ scale_shift, float* __restrict__ save_mean, float* __restrict__ save_invstd) {
   int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= C) return;
   float invstd = 1.f / sqrtf(rvar[c] + eps);
   float sc = gamma[c] * invstd;
   scale_shift[2 * c] = sc;
   scale_shift[2 * c + 1] = beta[c] - rmean[c] * sc;
+  if (save_mean) {          // what a backward through this (frozen) BatchNorm takes in place of the batch statistics
+    save_mean[c] = rmean[c];
+    save_invstd[c] = invstd;
+  }
 }
 
 // Bound of |scale[c] * y + shift[c]| over a tensor y whose largest magnitude is known (raw_amax: the amax table its producer's epilogue
@@ -190,7 +194,8 @@ __global__ __launch_bounds__(NT) void bn_bwd_finalize_k(const float* __restrict_
                                                          const float* __restrict__ invstd, float* __restrict__ dgamma,
                                                          float* __restrict__ dbeta, int accumulate,
                                                          float* __restrict__ coef, const float* __restrict__ global_sums,
-                                                         float* __restrict__ sums_out, int centred_s2) {
+                                                         float* __restrict__ sums_out, int centred_s2,
+                                                         float* __restrict__ dbias) {
   // one workgroup per channel; fp64 fold in a fixed order (lane-strided, butterfly, the waves in order); NT: see bn_finalize_k
   __shared__ double shs[2][NT / 64];
   const int c = blockIdx.x, t = threadIdx.x;
@@ -241,6 +246,10 @@ __global__ __launch_bounds__(NT) void bn_bwd_finalize_k(const float* __restrict_
     double k1 = (double)gamma[c] * invstd[c];
     double k2 = -(double)gamma[c] * invstd[c] * invstd[c] * s2 / count;
     double k3 = -k1 * s1 / count - k2 * mean[c];
+    if (dbias) {      // frozen statistics (common.h: bnb_tail): dy = k1 g, and the conv bias in front has the gradient k1 sum g
+      k2 = k3 = 0.0;
+      dbias[c] = accumulate ? dbias[c] + (float)(k1 * s1) : (float)(k1 * s1);
+    }
     coef[3 * c] = (float)k1;
     coef[3 * c + 1] = (float)k2;
     coef[3 * c + 2] = (float)k3;
@@ -279,6 +288,47 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_k(const float* __restrict__ 
       float g = dz[base + p], v = y[base + p];
       if (relu && !(fmaf(v, sc, sf) > 0.f)) g = 0.f;
       const float o = fmaf(k1, g, fmaf(k2, v, k3));
+      dy[base + p] = o;
+      am = amax_bits(o);
+    }
+  }
+  if (amax) amax_publish_wave(amax, am, blockIdx.x * 4u + (threadIdx.x >> 6));
+}
+
+// Frozen statistics: dy = k1 * dz*[z>0] — no term in y, which is read for the ReLU mask only (y null: dz is already masked and a
+// third of the traffic goes).  Items and amax as bn_bwd_apply_k.
+template <bool VEC>
+__global__ __launch_bounds__(256) void bn_bwd_scale_k(const float* __restrict__ dz, const float* __restrict__ y,
+                                                      const float* __restrict__ ss, int relu, const float* __restrict__ coef,
+                                                      int C, int HW, int bpp, float* __restrict__ dy, unsigned* __restrict__ amax) {
+  const int bc = blockIdx.x / bpp, blk = blockIdx.x - bc * bpp, c = bc % C;
+  const bool mask = relu && y;
+  const float sc = mask ? ss[2 * c] : 1.f, sf = mask ? ss[2 * c + 1] : 1.f;
+  const float k1 = coef[3 * c];
+  const size_t base = (size_t)bc * HW;
+  unsigned am = 0u;
+  if (VEC) {
+    int p = (blk * 256 + threadIdx.x) * 4;
+    if (p < HW) {
+      float4 g = *reinterpret_cast<const float4*>(dz + base + p);
+      if (mask) {
+        const float4 v = *reinterpret_cast<const float4*>(y + base + p);
+        if (!(fmaf(v.x, sc, sf) > 0.f)) g.x = 0.f;
+        if (!(fmaf(v.y, sc, sf) > 0.f)) g.y = 0.f;
+        if (!(fmaf(v.z, sc, sf) > 0.f)) g.z = 0.f;
+        if (!(fmaf(v.w, sc, sf) > 0.f)) g.w = 0.f;
+      }
+      float4 o;
+      o.x = k1 * g.x; o.y = k1 * g.y; o.z = k1 * g.z; o.w = k1 * g.w;
+      *reinterpret_cast<float4*>(dy + base + p) = o;
+      am = max(max(amax_bits(o.x), amax_bits(o.y)), max(amax_bits(o.z), amax_bits(o.w)));
+    }
+  } else {
+    int p = blk * 256 + threadIdx.x;
+    if (p < HW) {
+      float g = dz[base + p];
+      if (mask && !(fmaf(y[base + p], sc, sf) > 0.f)) g = 0.f;
+      const float o = k1 * g;
       dy[base + p] = o;
       am = amax_bits(o);
     }
@@ -362,13 +412,13 @@ __global__ __launch_bounds__(1024) void bn_bwd_small_k(const float* __restrict__
 
 static void bwd_finalize(hipStream_t st, const float* partial, int nsplit, int C, double count, const float* gamma, const float* mean,
                          const float* invstd, float* dgamma, float* dbeta, int accumulate, float* coef, const float* global_sums,
-                         float* sums_out, int centred_s2) {
+                         float* sums_out, int centred_s2, float* dbias = nullptr) {
   if (nsplit >= 2048)
     hipLaunchKernelGGL(bn_bwd_finalize_k<1024>, dim3(C), dim3(1024), 0, st, partial, nsplit, C, count, gamma, mean, invstd, dgamma, dbeta,
-                       accumulate, coef, global_sums, sums_out, centred_s2);
+                       accumulate, coef, global_sums, sums_out, centred_s2, dbias);
   else
     hipLaunchKernelGGL(bn_bwd_finalize_k<256>, dim3(C), dim3(256), 0, st, partial, nsplit, C, count, gamma, mean, invstd, dgamma, dbeta,
-                       accumulate, coef, global_sums, sums_out, centred_s2);
+                       accumulate, coef, global_sums, sums_out, centred_s2, dbias);
 }
 
 static inline bool vec_ok(int HW, const void* a, const void* b, const void* c) {
@@ -413,7 +463,16 @@ extern "C" int wtpse_bn_eval_coeffs(const float* gamma, const float* beta, const
                                     const float* running_var, float eps, int C, float* scale_shift, void* stream) {
   WTPSE_REQUIRE(gamma && beta && running_mean && running_var && scale_shift && C > 0);
   hipLaunchKernelGGL(bn_eval_coeffs_k, dim3(ceil_div(C, 64)), dim3(64), 0, (hipStream_t)stream, gamma, beta,
-                     running_mean, running_var, eps, C, scale_shift);
+                     running_mean, running_var, eps, C, scale_shift, (float*)nullptr, (float*)nullptr);
+  return wtpse_status();
+}
+
+extern "C" int wtpse_bn_eval_coeffs_stats(const float* gamma, const float* beta, const float* running_mean,
+                                          const float* running_var, float eps, int C, float* scale_shift, float* save_mean,
+                                          float* save_invstd, void* stream) {
+  WTPSE_REQUIRE(gamma && beta && running_mean && running_var && scale_shift && save_mean && save_invstd && C > 0);
+  hipLaunchKernelGGL(bn_eval_coeffs_k, dim3(ceil_div(C, 64)), dim3(64), 0, (hipStream_t)stream, gamma, beta,
+                     running_mean, running_var, eps, C, scale_shift, save_mean, save_invstd);
   return wtpse_status();
 }
 
@@ -537,5 +596,68 @@ extern "C" int wtpse_bn_bwd_apply_coef(const float* g, const float* y, const flo
   WTPSE_REQUIRE(g && y && coef && dy && B > 0 && C > 0 && HW > 0);
   hipStream_t st = (hipStream_t)stream;
   launch_apply(g, y, coef, 0, coef, dy, B, C, HW, amax, st);
+  return wtpse_status();
+}
+
+// ---- frozen statistics: the backward through an EVAL-mode BatchNorm (z = act(s y + beta - s m), s = gamma r, m / r = the running
+// mean and 1 / sqrt(running_var + eps): wtpse_bn_eval_coeffs_stats).  The same fixed-order folds as above with mean / invstd = m / r:
+// dbeta = sum g, dgamma = r sum g (y - m); the two terms through the batch statistics are gone (k2 = k3 = 0: dy = s g), and the
+// bias of the convolution in front, whose gradient a train-mode BatchNorm cancels exactly, receives s sum g.
+static void launch_scale(const float* dz, const float* y, const float* ss, int relu, const float* coef, float* dy, int B, int C, int HW,
+                         unsigned* amax, hipStream_t st) {
+  if (vec_ok(HW, dz, y, dy))
+    hipLaunchKernelGGL(bn_bwd_scale_k<true>, dim3(ceil_div(HW, 1024) * B * C), dim3(256), 0, st, dz, y, ss, relu, coef, C, HW,
+                       ceil_div(HW, 1024), dy, amax);
+  else
+    hipLaunchKernelGGL(bn_bwd_scale_k<false>, dim3(ceil_div(HW, 256) * B * C), dim3(256), 0, st, dz, y, ss, relu, coef, C, HW,
+                       ceil_div(HW, 256), dy, amax);
+}
+
+extern "C" int wtpse_bn_bwd_frozen(const float* dz, const float* y, const float* scale_shift, int relu, const float* gamma,
+                                   const float* mean, const float* invstd, float* partial, float* coef, float* dgamma,
+                                   float* dbeta, float* dbias, int accumulate, float* dy, int B, int C, int HW, unsigned* amax,
+                                   void* stream) {
+  WTPSE_REQUIRE(dz && y && scale_shift && gamma && mean && invstd && partial && coef && dgamma && dbeta && dbias && dy);
+  WTPSE_REQUIRE(B > 0 && C > 0 && HW > 0);
+  hipStream_t st = (hipStream_t)stream;
+  const int ns = wtpse_bn_bwd_nsplit(B, C, HW);
+  if (vec_ok(HW, dz, y, nullptr))
+    hipLaunchKernelGGL(bn_bwd_reduce_k<true>, dim3(C, ns), dim3(256), 0, st, dz, y, scale_shift, relu, mean, invstd, B, C, HW,
+                       bn_bwd_segs(B, C, HW), partial);
+  else
+    hipLaunchKernelGGL(bn_bwd_reduce_k<false>, dim3(C, ns), dim3(256), 0, st, dz, y, scale_shift, relu, mean, invstd, B, C, HW,
+                       bn_bwd_segs(B, C, HW), partial);
+  bwd_finalize(st, partial, ns, C, (double)B * HW, gamma, mean, invstd, dgamma, dbeta, accumulate, coef, (const float*)nullptr,
+               (float*)nullptr, 0, dbias);
+  launch_scale(dz, y, scale_shift, relu, coef, dy, B, C, HW, amax, st);
+  return wtpse_status();
+}
+
+extern "C" int wtpse_bn_bwd_finalize_coef_frozen(const float* stats_partial, int nblk, int C, const float* gamma, const float* invstd,
+                                                 float* coef, float* dgamma, float* dbeta, float* dbias, int accumulate,
+                                                 void* stream) {
+  WTPSE_REQUIRE(stats_partial && gamma && invstd && coef && dgamma && dbeta && dbias && nblk > 0 && C > 0);
+  // (count and mean only enter the two coefficients that frozen statistics do not have)
+  bwd_finalize((hipStream_t)stream, stats_partial, nblk, C, 1.0, gamma, invstd, invstd, dgamma, dbeta, accumulate, coef,
+               (const float*)nullptr, (float*)nullptr, 1, dbias);
+  return wtpse_status();
+}
+
+extern "C" int wtpse_bn_bwd_from_stats_frozen(const float* g, const float* stats_partial, int nblk, const float* gamma,
+                                              const float* invstd, float* coef, float* dgamma, float* dbeta, float* dbias,
+                                              int accumulate, float* dy, int B, int C, int HW, unsigned* amax, void* stream) {
+  WTPSE_REQUIRE(g && stats_partial && gamma && invstd && coef && dgamma && dbeta && dbias && dy);
+  WTPSE_REQUIRE(nblk > 0 && B > 0 && C > 0 && HW > 0);
+  hipStream_t st = (hipStream_t)stream;
+  bwd_finalize(st, stats_partial, nblk, C, 1.0, gamma, invstd, invstd, dgamma, dbeta, accumulate, coef, (const float*)nullptr,
+               (float*)nullptr, 1, dbias);
+  launch_scale(g, nullptr, nullptr, 0, coef, dy, B, C, HW, amax, st);
+  return wtpse_status();
+}
+
+extern "C" int wtpse_bn_bwd_scale_coef(const float* g, const float* coef, float* dy, int B, int C, int HW, unsigned* amax,
+                                       void* stream) {
+  WTPSE_REQUIRE(g && coef && dy && B > 0 && C > 0 && HW > 0);
+  launch_scale(g, nullptr, nullptr, 0, coef, dy, B, C, HW, amax, (hipStream_t)stream);
   return wtpse_status();
 }

@@ -239,6 +239,7 @@ struct BnbTail {
   float* coef;             // [Cbn][3]
   float* dgamma;
   float* dbeta;
+  float* dbias;            // null: batch statistics.  Frozen (running) statistics: gradient of the conv bias in front, k1 * sum g
   double count;
   int accumulate, ngroups, ntiles, ctot, t2_off;
 };
@@ -388,8 +389,12 @@ __device__ __forceinline__ void bnb_tail(const TailTicket& tk, const BnbTail& tl
     tl.dbeta[cb] = tl.accumulate ? tl.dbeta[cb] + (float)s1 : (float)s1;
     tl.dgamma[cb] = tl.accumulate ? tl.dgamma[cb] + (float)s2 : (float)s2;
     const double k1 = ga * is;
-    const double k2 = -ga * is * is * s2 / tl.count;
-    const double k3 = -k1 * s1 / tl.count - k2 * (double)bn_mean[cb];
+    double k2 = -ga * is * is * s2 / tl.count;
+    double k3 = -k1 * s1 / tl.count - k2 * (double)bn_mean[cb];
+    if (tl.dbias) {          // frozen statistics (mean / invstd = the running ones): no term through them, dy = k1 g
+      k2 = k3 = 0.0;
+      tl.dbias[cb] = tl.accumulate ? tl.dbias[cb] + (float)(k1 * s1) : (float)(k1 * s1);
+    }
     tl.coef[3 * cb] = (float)k1;
     tl.coef[3 * cb + 1] = (float)k2;
     tl.coef[3 * cb + 2] = (float)k3;
@@ -459,6 +464,7 @@ static inline int bnb_tail_t2off(int ntiles, int Cout) { return ((Cout + 15) / 1
 static inline BnbTail bnb_tail_none() {
   BnbTail t;
   t.partial2 = nullptr; t.tickets = nullptr; t.gamma = nullptr; t.invstd = nullptr; t.coef = nullptr; t.dgamma = nullptr; t.dbeta = nullptr;
+  t.dbias = nullptr;
   t.count = 1.0; t.accumulate = 0; t.ngroups = 0; t.ntiles = 0; t.ctot = 0; t.t2_off = 0;
   return t;
 }

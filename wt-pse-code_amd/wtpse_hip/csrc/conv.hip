@@ -896,6 +896,32 @@ extern "C" int wtpse_dgrad_bnb_coef(const float* dy, int C, const void* wpacked,
                        B, H, W, Cout, ksize, 0, bn_y, nullptr, stream, ex);
 }
 
+// wtpse_dgrad_bnb_coef into a BatchNorm on frozen (running) statistics: bn_mean / invstd = the running mean and 1 / sqrt(var + eps);
+// the tail writes (k1, 0, 0) and the gradient of the conv bias in front (common.h: bnb_tail).
+extern "C" int wtpse_dgrad_bnb_coef_frozen(const float* dy, int C, const void* wpacked, int layout, float* out0, float* out1,
+                                           int Csplit, const float* bn_y, const float* bn_ss, const float* bn_mean, int bn_relu,
+                                           int bn_c0, int bn_c1, float* stats, const float* gamma, const float* invstd, float* coef,
+                                           float* dgamma, float* dbeta, float* dbias, int accumulate, double* partial2,
+                                           unsigned* tickets, int B, int H, int W, int Cout, int ksize, const unsigned* in_amax,
+                                           void* stream) {
+  WTPSE_REQUIRE(bn_y && bn_ss && bn_mean && stats && gamma && invstd && coef && dgamma && dbeta && dbias && partial2 && tickets);
+  WTPSE_REQUIRE(layout >= 0 && layout <= 2);
+  ConvExtras ex; ex.bn = BnbArgs{bn_ss, bn_mean, bn_relu, bn_c0, bn_c1};
+  BnbTail& t = ex.tail;
+  t.partial2 = partial2; t.tickets = tickets; t.gamma = gamma; t.invstd = invstd; t.coef = coef; t.dgamma = dgamma; t.dbeta = dbeta;
+  t.dbias = dbias; t.accumulate = accumulate;
+  if (layout == 1)
+    return dgrad_x3_bnb_tail(dy, C, static_cast<const unsigned short*>(wpacked), out0, out1, Csplit, bn_y, bn_ss, bn_mean,
+                             bn_relu, bn_c0, bn_c1, stats, &t, B, H, W, Cout, ksize, in_amax, stream);
+  if (layout == 2) {
+    WTPSE_REQUIRE(ksize == 3 && !out1 && Csplit == Cout && bn_c0 == 0 && bn_c1 == Cout);
+    return conv16_x3_impl(dy, C, static_cast<const unsigned short*>(wpacked), nullptr, nullptr, 0, out0, stats, nullptr, bn_y, B, H, W,
+                          Cout, 0, 1, in_amax, stream, ex);
+  }
+  return conv_fwd_impl(dy, C, nullptr, 0, static_cast<const float*>(wpacked), nullptr, nullptr, nullptr, 0, out0, out1, Csplit, stats,
+                       B, H, W, Cout, ksize, 0, bn_y, nullptr, stream, ex);
+}
+
 // Weight fragments of the 16-channel x3 / x2h path, all convs of a network in one launch.  desc: n_desc x 8 ints {w_off, Cout, Cin,
 // 9, fwd_off (-1: none), dgrad_off (-1: none), 0, 0}, w_off in floats into `params`, *_off in unsigned shorts into `packed`;
 // one direction = 8 shorts of header (float {1 / scale, scale}) + [5 k-steps][3 terms][64 lanes][8] bf16 (x3: 7680 shorts) +

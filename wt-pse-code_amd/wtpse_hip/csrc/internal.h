@@ -37,6 +37,9 @@ static inline bool tail_in_launch(long long workgroups) {
 // after a launch whose tails were switched off for size: the same results from the stand-alone kernels
 static inline int tail_after_launch(const BnbTail& tl, const BnfTail& fl, float* stats, int nblk, int Cout, int bn_c0, int bn_c1,
                                     const float* bn_mean, long long count, void* stream) {
+  if (tl.tickets && tl.dbias)
+    return wtpse_bn_bwd_finalize_coef_frozen(stats, nblk, bn_c1 - bn_c0, tl.gamma, tl.invstd, tl.coef, tl.dgamma, tl.dbeta, tl.dbias,
+                                             tl.accumulate, stream);
   if (tl.tickets)
     return wtpse_bn_bwd_finalize_coef(stats, nblk, bn_c1 - bn_c0, count, tl.gamma, bn_mean, tl.invstd, tl.coef, tl.dgamma, tl.dbeta,
                                       tl.accumulate, stream);

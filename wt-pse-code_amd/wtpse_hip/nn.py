@@ -180,7 +180,8 @@ class HipNet(nn.Module):
         # _attach_grads and _defer_allreduce directly)
         for name, value in dict(_flat=None, _gflat=None, _gwork=None, _packed=None, _x3=None, _xdesc=None, _x16desc=None, _desc=None,
                                 _packed_version=-1, _touched=[], _noise_queue=[], _noise_seed=0x5eed, _noise_ctr=None, _dp=None,
-                                _flag=None, _packed_valid=False, _attach_grads=True, _defer_allreduce=False, _join=[]).items():
+                                _flag=None, _packed_valid=False, _attach_grads=True, _defer_allreduce=False, _join=[],
+                                _frozen_bias={}, _frozen_pass=False).items():
             object.__setattr__(self, name, value)
         self._convs = [m for m in self.modules() if isinstance(m, ConvP)]
         for m in self.modules():
@@ -360,6 +361,15 @@ class HipNet(nn.Module):
         self._touched.append(p)
         return self.grange(p, p.numel())
 
+    def gbias(self, conv):
+        """gview of the bias of a convolution in front of a BatchNorm on FROZEN statistics.  Only such a backward writes these
+        gradients (behind batch statistics they are exactly zero and are never written: convbn_bwd), so the flat buffer remembers
+        them: end_backward() of the next train-mode pass clears them."""
+        object.__setattr__(self, "_frozen_pass", True)
+        if self._gtarget is self._gflat:
+            self._frozen_bias[id(conv.bias)] = conv.bias
+        return self.gview(conv.bias)
+
     def grads_ready(self, first, last=None):
         """Data-parallel overlap: the parameter gradients of the consecutive submodules `first` .. `last` (a contiguous range of
         the flat buffer) are complete once the work queued so far on the current stream and on its weight-gradient side stream
@@ -393,6 +403,12 @@ class HipNet(nn.Module):
         if self._dp is not None and not self._defer_allreduce:     # the step harness issues it itself
             self._dp.allreduce_grads(self, self._gtarget)
         direct = self._gtarget is self._gflat
+        if direct and self._frozen_bias and not self._frozen_pass:
+            # the first train-mode pass after one on frozen statistics: the pre-BatchNorm bias gradients are zero again
+            for p in self._frozen_bias.values():
+                ops.zero_(self.grange(p, p.numel()))
+            self._frozen_bias.clear()
+        object.__setattr__(self, "_frozen_pass", False)
         if direct and not self._attach_grads:   # the step harness reads the flat buffer itself
             self._touched.clear()
             return
@@ -436,7 +452,7 @@ class HipNet(nn.Module):
 # ================================================================================================ block schedules
 class Tape:
     """Attribute bag holding what a block's backward needs."""
-    pass
+    frozen = False      # conv + BatchNorm layers (convbn_fwd / upbn_fwd): the BatchNorm ran on its running statistics (eval mode)
 
 
 class Act:
@@ -580,6 +596,8 @@ def _dgrad(layer, dy, split=None, mask_ref=None, below0=None, below1=None):
             and not root.bn_synced and (below1 is None or split is not None)):
         bn = below.bn
         tail = (bn.weight, below.invstd, root.gview(bn.weight), root.gview(bn.bias)) if BN_TAIL else None
+        if tail is not None and below.frozen:          # frozen statistics: the fold also writes the gradient of the conv bias in front
+            tail += (root.gbias(below.conv),)
         d0, d1, stats, coef = ops.dgrad_bnb(dy, wptr, layout, layer.cin, layer.k, below.y, below.ss, below.mean, below.relu, split,
                                             below1 is not None and below0 is None, tail,
                                             _gamax(dy) if layout == 1 else getattr(dy, "wt_amax", None) if layout == 2 else None)
@@ -700,13 +718,18 @@ def _wgrad(layer, dy, a0, a1=None, with_bias=True):
 
 
 # ---- conv + BatchNorm (+ReLU): the result stays virtual (raw conv output + per-channel scale/shift) --------------
-def _bn_coeffs(root, bn, y, stats, training, tab=None, raw_amax=None):
+def _bn_coeffs(root, bn, y, stats, training, tab=None, raw_amax=None, want_tape=False):
     """-> (ss, mean, invstd, tab): scale / shift of the BatchNorm over y and the amax table of its output (x2h).  Train mode: from
     the (sum, sum^2) partials `stats`, exchanged first where BatchNorm is synchronised; tab: the zeroed table to fill (None: one is
-    taken here).  Eval mode: from the running statistics; the bound follows from raw_amax, the amax table of the data, if known."""
+    taken here).  Eval mode: from the running statistics; the bound follows from raw_amax, the amax table of the data, if known.
+    With a tape, mean / invstd are then the running mean and 1 / sqrt(running_var + eps): what the frozen folds of the backward take
+    in place of the batch statistics (the same launch emits them)."""
     if not training:
-        ss = ops.bn_eval_coeffs(bn.weight, bn.bias, bn.running_mean, bn.running_var)
-        return ss, None, None, (ops.act_bound(ss, raw_amax) if raw_amax is not None else None)
+        if want_tape:
+            ss, mean, invstd = ops.bn_eval_coeffs_stats(bn.weight, bn.bias, bn.running_mean, bn.running_var)
+        else:
+            ss, mean, invstd = ops.bn_eval_coeffs(bn.weight, bn.bias, bn.running_mean, bn.running_var), None, None
+        return ss, mean, invstd, (ops.act_bound(ss, raw_amax) if raw_amax is not None else None)
     B, _, H, W = y.shape
     count = B * H * W
     if root.bn_synced:
@@ -734,13 +757,13 @@ def convbn_fwd(conv, bn, a0, a1, relu, training, want_tape=True):
                                                in_amax1=act_amax(a1) if layout == 1 else None, act_amax=tab)
     else:
         y, stats = _conv(conv, a0, a1, False, training, want_amax=not training)
-        ss, mean, invstd, tab = _bn_coeffs(root, bn, y, stats, training, tab, getattr(y, "wt_amax", None))
+        ss, mean, invstd, tab = _bn_coeffs(root, bn, y, stats, training, tab, getattr(y, "wt_amax", None), want_tape)
     z = Act(y, ss, relu, tab)
     if not want_tape:
         return z, None
     t = Tape()
     t.a0, t.a1, t.y, t.ss, t.mean, t.invstd, t.relu = a0, a1, y, ss, mean, invstd, relu
-    t.bn = bn
+    t.bn, t.conv, t.frozen = bn, conv, not training
     return z, t
 
 
@@ -750,6 +773,17 @@ def convbn_fwd(conv, bn, a0, a1, relu, training, want_tape=True):
 BN_IN = os.environ.get("WTPSE_BN_IN", "1") != "0"
 def _bn_bwd(bn, t, dz, root):
     """BatchNorm (+ReLU) backward of a convbn / upbn tape: dz = gradient wrt the activated output, plain or PreBN."""
+    if t.frozen:
+        # eval-mode BatchNorm: the same folds on the running statistics, dy = k1 g, and the conv bias in front has a gradient
+        if root.bn_synced:
+            raise RuntimeError("frozen BatchNorm statistics are not supported together with synchronised BatchNorm")
+        if isinstance(dz, PreBN):
+            if dz.coef is not None:            # (the producing launch's tail wrote dgamma, dbeta and the bias gradient)
+                return ops.bn_bwd_scale_coef(dz.g, dz.coef)
+            return ops.bn_bwd_from_stats_frozen(dz.g, dz.stats, bn.weight, t.invstd, root.gview(bn.weight), root.gview(bn.bias),
+                                                root.gbias(t.conv))
+        return ops.bn_bwd_frozen(dz, t.y, t.ss, t.relu, bn.weight, t.mean, t.invstd, root.gview(bn.weight), root.gview(bn.bias),
+                                 root.gbias(t.conv))
     if isinstance(dz, PreBN):
         if dz.coef is not None:
             return ops.bn_bwd_apply_coef(dz.g, t.y, dz.coef)
@@ -766,6 +800,7 @@ def convbn_bwd(conv, bn, t, dz, need_dx=True, below0=None, below1=None):
     dy = _bn_bwd(bn, t, dz, root)
     # the conv bias in front of a train-mode BatchNorm has an exactly-zero gradient (sum of dy over the batch
     # vanishes); the reference carries rounding noise there. It is left at 0.
+    # (Behind frozen statistics it is k1 sum g, which the BatchNorm-backward fold has written: _bn_bwd / _dgrad.)
     _wgrad_side(conv, dy, t.a0, t.a1)
     if not need_dx:
         return None, None
@@ -824,13 +859,13 @@ def upbn_fwd(conv, bn, a0, training, want_tape=True):
     z, _ = _conv(conv, a0, None, False, False, want_amax=not training)      # low resolution, pre-BatchNorm
     # (bilinear interpolation is a convex combination: the upsampled map is bounded by the amax of the low-resolution one)
     y, stats = ops.upsample2x_fwd_stats(z) if training else (ops.upsample2x_fwd(z), None)
-    ss, mean, invstd, tab = _bn_coeffs(root, bn, y, stats, training, None, getattr(z, "wt_amax", None))
+    ss, mean, invstd, tab = _bn_coeffs(root, bn, y, stats, training, None, getattr(z, "wt_amax", None), want_tape)
     out = Act(y, ss, True, tab)
     if not want_tape:
         return out, None
     t = Tape()
     t.a0, t.a1, t.y, t.ss, t.mean, t.invstd, t.relu = a0, None, y, ss, mean, invstd, True
-    t.bn = bn
+    t.bn, t.conv, t.frozen = bn, conv, not training
     return out, t
 
 

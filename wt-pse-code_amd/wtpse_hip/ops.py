@@ -340,7 +340,9 @@ def dgrad_bnb(dy, wpacked_ptr, layout, cout, ksize, bn_y, bn_ss, bn_mean, bn_rel
     epilogue masks the result with the ReLU of the conv + BatchNorm layer it flows into and forms that layer's BatchNorm-backward
     reductions (include/wtpse_hip.h, wtpse_dgrad_bnb).  With a split the BatchNorm'd tensor is out0, or out1 if `bn_second`.
     tail = (gamma, invstd, dgamma, dbeta) of that BatchNorm: the launch also folds the partials and leaves the coefficients
-    (wtpse_dgrad_bnb_coef).
+    (wtpse_dgrad_bnb_coef).  A fifth element, dbias: that BatchNorm runs on frozen statistics — bn_mean / invstd are the running
+    ones, the coefficients come out as (k1, 0, 0) and dbias receives the gradient of the conv bias in front of it
+    (wtpse_dgrad_bnb_coef_frozen).
     -> (out0, out1 or None, stats [nblk, Cbn, 2], coef [Cbn, 3] or None)."""
     _chk(dy, "dy"); _chk(bn_y, "bn_y"); _chk(bn_ss, "bn_ss"); _chk(bn_mean, "bn_mean")
     layout = int(layout)
@@ -352,10 +354,16 @@ def dgrad_bnb(dy, wpacked_ptr, layout, cout, ksize, bn_y, bn_ss, bn_mean, bn_rel
     nblk = _stats_blocks(layout, B, H, W, cout, ksize)
     stats = torch.empty((nblk, c1 - c0, 2), dtype=torch.float32, device=dy.device)
     if tail is not None:
-        gamma, invstd, dgamma, dbeta = tail
+        gamma, invstd, dgamma, dbeta = tail[:4]
         coef = torch.empty((c1 - c0, 3), dtype=torch.float32, device=dy.device)
         partial2 = torch.empty(L.query("wtpse_bnb_tail_partial2", nblk, cout), dtype=torch.float64, device=dy.device)
         tickets, tview = _tickets(L.query("wtpse_bnb_tail_tickets", nblk, cout), dy.device)
+        if len(tail) == 5:
+            _ticket_call(tview, "wtpse_dgrad_bnb_coef_frozen", ptr(dy), C, wpacked_ptr, layout, ptr(out0), ptr(out1), csplit, ptr(bn_y),
+                         ptr(bn_ss), ptr(bn_mean), int(bool(bn_relu)), c0, c1, ptr(stats), ptr(gamma), ptr(invstd), ptr(coef),
+                         ptr(dgamma), ptr(dbeta), ptr(tail[4]), 0, ptr(partial2), tickets, B, H, W, cout, ksize, ptr(in_amax),
+                         stream_ptr())
+            return out0, out1, stats, coef
         _ticket_call(tview, "wtpse_dgrad_bnb_coef", ptr(dy), C, wpacked_ptr, layout, ptr(out0), ptr(out1), csplit, ptr(bn_y), ptr(bn_ss),
                ptr(bn_mean), int(bool(bn_relu)), c0, c1, ptr(stats), ptr(gamma), ptr(invstd), ptr(coef), ptr(dgamma), ptr(dbeta), 0,
                ptr(partial2), tickets, B, H, W, cout, ksize, ptr(in_amax), stream_ptr())
@@ -475,6 +483,18 @@ def bn_eval_coeffs(gamma, beta, rmean, rvar, eps=1e-5):
     return ss
 
 
+def bn_eval_coeffs_stats(gamma, beta, rmean, rvar, eps=1e-5):
+    """bn_eval_coeffs plus what a backward through the eval-mode BatchNorm takes for the batch statistics: -> (ss, mean, invstd) with
+    mean = the running mean, invstd = 1 / sqrt(running_var + eps)."""
+    C = gamma.numel()
+    ss = torch.empty((C, 2), dtype=torch.float32, device=gamma.device)
+    mean = torch.empty((C,), dtype=torch.float32, device=gamma.device)
+    invstd = torch.empty((C,), dtype=torch.float32, device=gamma.device)
+    lib().call("wtpse_bn_eval_coeffs_stats", ptr(gamma), ptr(beta), ptr(rmean), ptr(rvar), float(eps), C, ptr(ss), ptr(mean),
+               ptr(invstd), stream_ptr())
+    return ss, mean, invstd
+
+
 def affine_act(y, ss, relu):
     _chk(y, "y")
     B, C, H, W = y.shape
@@ -508,6 +528,66 @@ def bn_bwd_from_stats(g, y, stats, gamma, mean, invstd, dgamma, dbeta, accumulat
     lib().call("wtpse_bn_bwd_from_stats", ptr(g), ptr(y), ptr(stats), stats.shape[0], ptr(gamma), ptr(mean), ptr(invstd), ptr(coef),
                ptr(dgamma), ptr(dbeta), int(accumulate), ptr(dy), B, C, H * W, ptr(dy.wt_amax), stream_ptr())
     return dy
+
+
+# ---- frozen statistics: the backward through an eval-mode BatchNorm (include/wtpse_hip.h, wtpse_bn_bwd_frozen).  mean / invstd:
+# from bn_eval_coeffs_stats; dbias: the gradient view of the bias of the convolution in front of the BatchNorm.
+def bn_bwd_frozen(dz, y, ss, relu, gamma, mean, invstd, dgamma, dbeta, dbias, accumulate=False):
+    _chk(dz, "dz"); _chk(y, "y")
+    B, C, H, W = y.shape
+    L = lib()
+    ns = L.query("wtpse_bn_bwd_nsplit", B, C, H * W)
+    partial = workspace("bn_bwd_partial", ns * C * 2, y.device)
+    coef = workspace("bn_bwd_coef", C * 3, y.device)
+    dy = torch.empty_like(y)
+    dy.wt_amax = _amax_table(y.device)
+    L.call("wtpse_bn_bwd_frozen", ptr(dz), ptr(y), ptr(ss), int(relu), ptr(gamma), ptr(mean), ptr(invstd), ptr(partial), ptr(coef),
+           ptr(dgamma), ptr(dbeta), ptr(dbias), int(accumulate), ptr(dy), B, C, H * W, ptr(dy.wt_amax), stream_ptr())
+    return dy
+
+
+def bn_bwd_from_stats_frozen(g, stats, gamma, invstd, dgamma, dbeta, dbias, accumulate=False):
+    """g = masked incoming gradient, stats = its partials against the running mean (dgrad_bnb / maxpool2_bwd_bnb).  -> dy."""
+    _chk(g, "g"); _chk(stats, "stats")
+    B, C, H, W = g.shape
+    assert stats.shape[1] == C
+    coef = workspace("bn_bwd_coef", C * 3, g.device)
+    dy = torch.empty_like(g)
+    dy.wt_amax = _amax_table(g.device)
+    lib().call("wtpse_bn_bwd_from_stats_frozen", ptr(g), ptr(stats), stats.shape[0], ptr(gamma), ptr(invstd), ptr(coef), ptr(dgamma),
+               ptr(dbeta), ptr(dbias), int(accumulate), ptr(dy), B, C, H * W, ptr(dy.wt_amax), stream_ptr())
+    return dy
+
+
+def bn_bwd_finalize_coef_frozen(stats, gamma, invstd, dgamma, dbeta, dbias, accumulate=False):
+    """The fold alone: partials -> coef [C, 3] = (k1, 0, 0), dgamma / dbeta / dbias."""
+    _chk(stats, "stats")
+    C = stats.shape[1]
+    coef = torch.empty((C, 3), dtype=torch.float32, device=stats.device)
+    lib().call("wtpse_bn_bwd_finalize_coef_frozen", ptr(stats), stats.shape[0], C, ptr(gamma), ptr(invstd), ptr(coef), ptr(dgamma),
+               ptr(dbeta), ptr(dbias), int(accumulate), stream_ptr())
+    return coef
+
+
+def bn_bwd_scale_coef(g, coef):
+    """dy = k1 g with the coefficients a frozen dgrad_bnb(..., tail=) launch left (k2 = k3 = 0: y is not read)."""
+    _chk(g, "g"); _chk(coef, "coef")
+    B, C, H, W = g.shape
+    dy = torch.empty_like(g)
+    dy.wt_amax = _amax_table(g.device)
+    lib().call("wtpse_bn_bwd_scale_coef", ptr(g), ptr(coef), ptr(dy), B, C, H * W, ptr(dy.wt_amax), stream_ptr())
+    return dy
+
+
+def bn_frozen_fold_spec(g, y, gamma, running_mean, running_var, eps=1e-5):
+    """Host specification of the frozen fold (any device, any float dtype; the tests hold the kernels and torch's autograd of
+    F.batch_norm(training=False) against it): g = the gradient already masked with the layer's ReLU, y = the raw conv output,
+    both [B, C, H, W].  -> (dy, dgamma, dbeta, dbias, mean, invstd)."""
+    r = 1.0 / torch.sqrt(running_var + eps)
+    s = gamma * r
+    sum_g = g.sum(dim=(0, 2, 3))
+    sum_gy = (g * (y - running_mean.view(1, -1, 1, 1))).sum(dim=(0, 2, 3))
+    return s.view(1, -1, 1, 1) * g, r * sum_gy, sum_g, s * sum_g, running_mean, r
 
 
 # ----------------------------------------------------------------------------------------------- WT loss

@@ -177,16 +177,25 @@ class TrainStep:
     first NaN iteration on no parameter and no Adam moment changes any more (the reference raises before backward(); here the
     step never synchronises, so the flag is read by whoever reads the log).  BatchNorm running statistics, the step counts and
     the Philox positions still advance.  With multi-turn > 1 a shape call logs its last turn only (Trainer.py:827-832).
-    Without a log (the default) not one extra launch is issued."""
+    Without a log (the default) not one extra launch is issued.
+    freeze_bn: train on FROZEN BatchNorm statistics — the four networks are kept in eval mode (which changes nothing but BatchNorm:
+    update() samples as in training either way), every BatchNorm normalises with its running statistics, which are never written,
+    and the backward runs the frozen folds (wtpse_hip/nn.py: _bn_bwd): fine-tuning a trained checkpoint on a few images.  The mode
+    is part of a recorded step; step() refuses to run when a network's mode is not the one the step was built for.  It is an
+    argument of its own: hparams['freeze_bn'] (which the reference ships and never reads) is NOT looked at."""
 
-    def __init__(self, model_od, shape_od, model_oc, shape_oc, hparams, lr=5e-4, betas=(0.9, 0.99), dp=None, graph=False, log=None):
+    def __init__(self, model_od, shape_od, model_oc, shape_oc, hparams, lr=5e-4, betas=(0.9, 0.99), dp=None, graph=False, log=None,
+                 freeze_bn=False):
         self.hp = hparams
+        self.freeze_bn = bool(freeze_bn)
+        if self.freeze_bn and dp is not None:
+            raise ValueError("freeze_bn=True is not supported together with data-parallel training (dp=)")
         self.full = bool(hparams['whitening'])
         self.nets = [model_od, model_oc] + ([shape_od, shape_oc] if self.full else [])
         self.model_od, self.shape_od, self.model_oc, self.shape_oc = model_od, shape_od, model_oc, shape_oc
         self.dp = dp
         for n in self.nets:
-            n.train()
+            n.train(not self.freeze_bn)
             n.ensure_ready(repack=True)
             object.__setattr__(n, "_packed_valid", True)     # this harness owns the optimiser and repacks after each step
             object.__setattr__(n, "_attach_grads", False)
@@ -424,6 +433,11 @@ class TrainStep:
         Returns {name: 0-dim device tensor}; nothing is synchronised with the host.  With graph=True the returned tensors
         are the graphs' own output buffers: read them before the next step() overwrites them."""
         image = image.contiguous()
+        for n in self.nets:
+            if any(m.training == self.freeze_bn for m in n.modules()):
+                raise RuntimeError("this TrainStep was built with freeze_bn=%r: its networks must be in %s mode (the schedule — and a "
+                                   "recorded step — belongs to that mode); a module of %s is not"
+                                   % (self.freeze_bn, "eval" if self.freeze_bn else "train", type(n).__name__))
         if self.graph and not noise:
             if self._graphs is None:
                 self._capture(image, target_od, target_oc)

@@ -138,11 +138,13 @@ class TrainRun:
     lr_update is commented out, Trainer.py:1040) or "reference" (`reference_lr` after every epoch, from the next epoch on).
     val_batches: a sequence, or a callable returning an iterable, of (image, label_od, label_oc); validator: a `validate.Validator`.
     checkpoint_every: write out_dir/run_checkpoint.pth.tar after every that many epochs (0: never).
+    freeze_bn: train on frozen BatchNorm statistics (TrainStep(freeze_bn=True)): train_epoch() keeps the networks in eval mode, the
+    running statistics never change.  Part of config(), so load() restores it; a checkpoint from before the flag loads as False.
     """
 
     def __init__(self, model_od, shape_od, model_oc, shape_oc, hparams, next_batch, iter_per_epoch, max_epoch, lr=(1e-3, 1e-3, 1e-3, 1e-3),
                  stop_epoch=-1, val_batches=None, validator=None, interval_validate=10, lr_schedule=None, out_dir=None, graph="plan",
-                 seed=0, checkpoint_every=0, betas=(0.9, 0.99)):
+                 seed=0, checkpoint_every=0, betas=(0.9, 0.99), freeze_bn=False):
         if lr_schedule not in (None, "reference"):
             raise ValueError("lr_schedule must be None or 'reference', got %r" % (lr_schedule,))
         if (val_batches is None) != (validator is None):
@@ -154,10 +156,12 @@ class TrainRun:
         self.val_batches, self.validator, self.interval_validate = val_batches, validator, int(interval_validate)
         self.lr_schedule, self.out_dir, self.seed, self.checkpoint_every = lr_schedule, out_dir, int(seed), int(checkpoint_every)
         self.graph, self.betas = graph, tuple(float(b) for b in betas)
+        self.freeze_bn = bool(freeze_bn)
         self.py_rng, self.np_rng = random.Random(self.seed), np.random.RandomState(self.seed)
         device = next(model_od.parameters()).device
         self.log = LossLog(device, TrainStep.log_names(hparams))
-        self.train_step = TrainStep(model_od, shape_od, model_oc, shape_oc, hparams, lr=self.base_lr, betas=betas, graph=graph, log=self.log)
+        self.train_step = TrainStep(model_od, shape_od, model_oc, shape_oc, hparams, lr=self.base_lr, betas=betas, graph=graph, log=self.log,
+                                    freeze_bn=self.freeze_bn)
         self.epoch = 0                 # epochs completed = index of the epoch train_epoch() runs next
         self.iteration = 0             # iterations completed
         self.last = None               # what the last train_epoch() returned
@@ -182,7 +186,7 @@ class TrainRun:
         undivided, Trainer.py:974-987; that print-only quirk is not reproduced: every mean here is over the iterations.)"""
         for n in self.nets:
             if n is not None:
-                n.train()
+                n.train(not self.freeze_bn)
         start = time.perf_counter()
         self.log.reset()
         for _ in range(self.iter_per_epoch):
@@ -235,7 +239,17 @@ class TrainRun:
     def config(self):
         return {"lr": list(self.base_lr), "iter_per_epoch": self.iter_per_epoch, "max_epoch": self.max_epoch, "stop_epoch": self.stop_epoch,
                 "interval_validate": self.interval_validate, "lr_schedule": self.lr_schedule or "", "seed": self.seed,
-                "checkpoint_every": self.checkpoint_every, "graph": self.graph, "betas": list(self.betas)}
+                "checkpoint_every": self.checkpoint_every, "graph": self.graph, "betas": list(self.betas), "freeze_bn": self.freeze_bn}
+
+    @staticmethod
+    def config_kwargs(config):
+        """A saved config() as constructor arguments.  A checkpoint written before `freeze_bn` existed carries no such key: it was
+        trained on batch statistics and loads as freeze_bn=False."""
+        cfg = dict(config)
+        cfg["lr_schedule"] = cfg["lr_schedule"] or None
+        cfg["lr"], cfg["betas"] = tuple(cfg["lr"]), tuple(cfg["betas"])
+        cfg["freeze_bn"] = bool(cfg.get("freeze_bn", False))
+        return cfg
 
     def state(self):
         """Everything save() writes, as tensors, numbers, strings, lists and dicts only (torch.load(weights_only=True) reads it):
@@ -267,9 +281,7 @@ class TrainRun:
         """A TrainRun that continues the run `path` was saved from: the networks (new ones, or live ones) receive the saved weights
         and buffers, the constructor arguments that save() recorded (rates, epochs, seed, ...) are the defaults of `kw`."""
         d = torch.load(path, map_location="cpu", weights_only=True)
-        cfg = dict(d["config"])
-        cfg["lr_schedule"] = cfg["lr_schedule"] or None
-        cfg["lr"], cfg["betas"] = tuple(cfg["lr"]), tuple(cfg["betas"])
+        cfg = cls.config_kwargs(d["config"])
         cfg.update(kw)
         for key, n in zip(CKPT_KEYS, (model_od, shape_od, model_oc, shape_oc)):
             if n is not None:
