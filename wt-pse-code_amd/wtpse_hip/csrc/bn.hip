@@ -502,6 +502,19 @@ extern "C" int wtpse_bn_bwd_nsplit(int B, int C, int HW) {
   return ns;
 }
 
+// the reduction pass (sum dzh, sum dzh (y - mean) invstd) of every channel over wtpse_bn_bwd_nsplit() splits -> partial; -> the split count
+static int launch_reduce(const float* dz, const float* y, const float* ss, int relu, const float* mean, const float* invstd,
+                         float* partial, int B, int C, int HW, hipStream_t st) {
+  const int ns = wtpse_bn_bwd_nsplit(B, C, HW);
+  if (vec_ok(HW, dz, y, nullptr))
+    hipLaunchKernelGGL(bn_bwd_reduce_k<true>, dim3(C, ns), dim3(256), 0, st, dz, y, ss, relu, mean, invstd, B, C, HW,
+                       bn_bwd_segs(B, C, HW), partial);
+  else
+    hipLaunchKernelGGL(bn_bwd_reduce_k<false>, dim3(C, ns), dim3(256), 0, st, dz, y, ss, relu, mean, invstd, B, C, HW,
+                       bn_bwd_segs(B, C, HW), partial);
+  return ns;
+}
+
 extern "C" int wtpse_bn_bwd(const float* dz, const float* y, const float* scale_shift, int relu, const float* gamma,
                             const float* save_mean, const float* save_invstd, float* partial, float* coef,
                             float* dgamma, float* dbeta, int accumulate, float* dy, int B, int C, int HW,
@@ -515,13 +528,7 @@ extern "C" int wtpse_bn_bwd(const float* dz, const float* y, const float* scale_
                        dgamma, dbeta, accumulate, dy, B, C, HW, amax);
     return wtpse_status();
   }
-  const int ns = wtpse_bn_bwd_nsplit(B, C, HW);
-  if (vec_ok(HW, dz, y, nullptr))
-    hipLaunchKernelGGL(bn_bwd_reduce_k<true>, dim3(C, ns), dim3(256), 0, st, dz, y, scale_shift, relu, save_mean,
-                       save_invstd, B, C, HW, bn_bwd_segs(B, C, HW), partial);
-  else
-    hipLaunchKernelGGL(bn_bwd_reduce_k<false>, dim3(C, ns), dim3(256), 0, st, dz, y, scale_shift, relu, save_mean,
-                       save_invstd, B, C, HW, bn_bwd_segs(B, C, HW), partial);
+  const int ns = launch_reduce(dz, y, scale_shift, relu, save_mean, save_invstd, partial, B, C, HW, st);
   bwd_finalize(st, partial, ns, C, (double)B * HW, gamma, save_mean,
                      save_invstd, dgamma, dbeta, accumulate, coef, (const float*)nullptr, (float*)nullptr, 0);
   launch_apply(dz, y, scale_shift, relu, coef, dy, B, C, HW, amax, st);
@@ -536,13 +543,7 @@ extern "C" int wtpse_bn_bwd_reduce(const float* dz, const float* y, const float*
                                    int B, int C, int HW, void* stream) {
   WTPSE_REQUIRE(dz && y && scale_shift && save_mean && save_invstd && partial && sums_local && B > 0 && C > 0 && HW > 0);
   hipStream_t st = (hipStream_t)stream;
-  const int ns = wtpse_bn_bwd_nsplit(B, C, HW);
-  if (vec_ok(HW, dz, y, nullptr))
-    hipLaunchKernelGGL(bn_bwd_reduce_k<true>, dim3(C, ns), dim3(256), 0, st, dz, y, scale_shift, relu, save_mean,
-                       save_invstd, B, C, HW, bn_bwd_segs(B, C, HW), partial);
-  else
-    hipLaunchKernelGGL(bn_bwd_reduce_k<false>, dim3(C, ns), dim3(256), 0, st, dz, y, scale_shift, relu, save_mean,
-                       save_invstd, B, C, HW, bn_bwd_segs(B, C, HW), partial);
+  const int ns = launch_reduce(dz, y, scale_shift, relu, save_mean, save_invstd, partial, B, C, HW, st);
   bwd_finalize(st, partial, ns, C, 1.0, (const float*)nullptr, save_mean,
                      save_invstd, (float*)nullptr, (float*)nullptr, 0, (float*)nullptr, (const float*)nullptr, sums_local, 0);
   return wtpse_status();
@@ -620,13 +621,7 @@ extern "C" int wtpse_bn_bwd_frozen(const float* dz, const float* y, const float*
   WTPSE_REQUIRE(dz && y && scale_shift && gamma && mean && invstd && partial && coef && dgamma && dbeta && dbias && dy);
   WTPSE_REQUIRE(B > 0 && C > 0 && HW > 0);
   hipStream_t st = (hipStream_t)stream;
-  const int ns = wtpse_bn_bwd_nsplit(B, C, HW);
-  if (vec_ok(HW, dz, y, nullptr))
-    hipLaunchKernelGGL(bn_bwd_reduce_k<true>, dim3(C, ns), dim3(256), 0, st, dz, y, scale_shift, relu, mean, invstd, B, C, HW,
-                       bn_bwd_segs(B, C, HW), partial);
-  else
-    hipLaunchKernelGGL(bn_bwd_reduce_k<false>, dim3(C, ns), dim3(256), 0, st, dz, y, scale_shift, relu, mean, invstd, B, C, HW,
-                       bn_bwd_segs(B, C, HW), partial);
+  const int ns = launch_reduce(dz, y, scale_shift, relu, mean, invstd, partial, B, C, HW, st);
   bwd_finalize(st, partial, ns, C, (double)B * HW, gamma, mean, invstd, dgamma, dbeta, accumulate, coef, (const float*)nullptr,
                (float*)nullptr, 0, dbias);
   launch_scale(dz, y, scale_shift, relu, coef, dy, B, C, HW, amax, st);

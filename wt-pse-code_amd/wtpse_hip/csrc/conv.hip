@@ -672,11 +672,10 @@ template <int KS, int MODE, bool DB, int EPI>
 static int launch_fwd(const ConvArgs& a, hipStream_t st) {
   constexpr int CB = (MODE == 0 || MODE == 3 || MODE == 4) ? 16 : 32 * MODE;
   ConvArgs args = a;
-  const bool narrow = a.W <= 16;  // 16x16 tiles for the deepest levels, 8x32 otherwise
-  const int TW = narrow ? 16 : 32, TH = 256 / TW;
-  args.tiles_x = ceil_div(a.W, TW);
-  args.tiles_y = ceil_div(a.H, TH);
-  dim3 grid((unsigned)(a.B * args.tiles_x * args.tiles_y), (unsigned)ceil_div(a.CoutP, CB));
+  const Tiling t = conv_tiling(a.B, a.H, a.W);
+  args.tiles_x = t.tiles_x;
+  args.tiles_y = t.tiles_y;
+  dim3 grid((unsigned)t.tiles, (unsigned)ceil_div(a.CoutP, CB));
   // XCD-aware tile order (WTPSE_C16_XCD=0: dispatch order): first for the HBM-bound 16-channel x3 kernel (MODE 3), then every mode
   static const bool xcd_on = [] { const char* e = getenv("WTPSE_C16_XCD"); return !(e && e[0] == '0'); }();
   args.xcd_tiles = (xcd_on && grid.x % 8 == 0 && (long long)grid.x * grid.y >= 64) ? (int)(grid.x / 8) : 0;
@@ -684,90 +683,88 @@ static int launch_fwd(const ConvArgs& a, hipStream_t st) {
   if (!in_launch) args.tail.tickets = args.ftail.tickets = nullptr;
   if (args.tail.tickets) bnb_tail_geometry(args.tail, (int)grid.x, a.Cout, (double)a.B * a.H * a.W);
   if (args.ftail.tickets) bnf_tail_geometry(args.ftail, (int)grid.x, a.Cout, (double)a.B * a.H * a.W);
-  if (narrow)
+  if (t.TW == 16)
     hipLaunchKernelGGL((conv_fwd_k<KS, MODE, 4, DB, EPI>), grid, dim3(256), 0, st, args);
   else
     hipLaunchKernelGGL((conv_fwd_k<KS, MODE, 5, DB, EPI>), grid, dim3(256), 0, st, args);
-  int rc = wtpse_status();
-  if (rc == 0 && !in_launch)
-    rc = tail_after_launch(a.tail, a.ftail, a.stats, (int)grid.x, a.Cout, a.bn_c0, a.bn_c1, a.bn_mean, (long long)a.B * a.H * a.W, st);
-  return rc;
+  const int rc = wtpse_status();
+  return rc == 0 && !in_launch ? tail_after_launch(a, (int)grid.x, st) : rc;
 }
 
-extern "C" int wtpse_conv_stats_blocks(int B, int H, int W) {
-  const int TW = W <= 16 ? 16 : 32, TH = 256 / TW;
-  return B * ceil_div(W, TW) * ceil_div(H, TH);
-}
+extern "C" int wtpse_conv_stats_blocks(int B, int H, int W) { return conv_tiling(B, H, W).tiles; }
 
-struct BnbArgs {   // EPI 2 parameters (all null / 0: none); conv16_x3_impl covers all output channels and ignores c0, c1
-  const float* ss;
-  const float* mean;
-  int relu, c0, c1;
-};
-
-struct ConvExtras {   // what only some entry points pass to conv_fwd_impl / conv16_x3_impl; the defaults mean "none"
-  BnbArgs bn = {nullptr, nullptr, 0, 0, 0};
-  BnbTail tail = bnb_tail_none();
-  BnfTail ftail = bnf_tail_none();
-  unsigned* out_amax = nullptr;
-};
-
-// preconditions of the in-launch tails, shared by both implementations
-static bool tails_ok(const BnbTail& tail, const BnfTail& ftail, bool bnb, const float* stats, const float* gram) {
-  return (!tail.tickets || (bnb && tail.partial2 && tail.gamma && tail.invstd && tail.coef && tail.dgamma && tail.dbeta)) &&
-         (!ftail.tickets || (!bnb && stats && !gram && ftail.partial2 && ftail.gamma && ftail.beta && ftail.scale_shift &&
-                             ftail.save_mean && ftail.save_invstd && (ftail.rmean == nullptr) == (ftail.rvar == nullptr)));
-}
-
-static int conv_fwd_impl(const float* in0, int C0, const float* in1, int C1, const float* wpacked, const float* bias,
-                         const float* pro0, const float* pro1, int pro_relu, float* out0, float* out1, int Csplit, float* stats,
-                         int B, int H, int W, int Cout, int ksize, int relu_out, const float* mask_ref, float* gram,
-                         void* stream, const ConvExtras& ex = ConvExtras()) {
-  const BnbArgs& bn = ex.bn; unsigned* const out_amax = ex.out_amax;
-  WTPSE_REQUIRE(in0 && wpacked && out0 && B > 0 && H > 0 && W > 0 && C0 > 0 && C1 >= 0 && Cout > 0);
-  WTPSE_REQUIRE(ksize == 1 || ksize == 3);
-  WTPSE_REQUIRE((C1 == 0) == (in1 == nullptr));
-  WTPSE_REQUIRE(Csplit > 0 && Csplit <= Cout && ((Csplit == Cout) == (out1 == nullptr)));
-  WTPSE_REQUIRE(Csplit == Cout || Csplit % 16 == 0);   // the epilogue picks the output tensor per register, not per lane
-  WTPSE_REQUIRE(!(stats && relu_out));
+// Every precondition of the nine entry points, once: the clauses all layouts share, then what only one of them asks.
+static int conv_check(const ConvCall& c, int layout) {
+  const BnbArgs& bn = c.bn;
+  const BnbTail& t = c.tail;
+  const BnfTail& f = c.ftail;
   const bool bnb = bn.mean != nullptr;
-  WTPSE_REQUIRE(bnb || !(stats && mask_ref));
-  WTPSE_REQUIRE(bnb || !(mask_ref && out1));
-  WTPSE_REQUIRE(!bnb || (mask_ref && stats && bn.ss && !bias && !relu_out && !gram && bn.c0 >= 0 && bn.c0 < bn.c1 && bn.c1 <= Cout &&
-                         bn.c0 % 16 == 0 && (bn.c1 % 16 == 0 || bn.c1 == Cout)));
-  WTPSE_REQUIRE(C1 == 0 || C0 % 16 == 0);   // a channel chunk must not straddle the two inputs
-  WTPSE_REQUIRE(!(out_amax && (mask_ref || bnb)));
-  WTPSE_REQUIRE(tails_ok(ex.tail, ex.ftail, bnb, stats, gram));
+  WTPSE_REQUIRE(layout == CONV_FP32 || layout == CONV_X3 || layout == CONV_C16);
+  WTPSE_REQUIRE(c.in0 && c.w && c.out0 && c.B > 0 && c.H > 0 && c.W > 0 && c.C0 > 0 && c.C1 >= 0 && c.Cout > 0);
+  WTPSE_REQUIRE(c.ksize == 1 || c.ksize == 3);
+  WTPSE_REQUIRE((c.C1 == 0) == (c.in1 == nullptr));
+  WTPSE_REQUIRE(c.Csplit > 0 && c.Csplit <= c.Cout && ((c.Csplit == c.Cout) == (c.out1 == nullptr)));
+  WTPSE_REQUIRE(c.Csplit == c.Cout || c.Csplit % 16 == 0);   // the epilogue picks the output tensor per register, not per lane
+  WTPSE_REQUIRE(!(c.stats && c.relu_out));
+  WTPSE_REQUIRE(bnb || !(c.stats && c.mask_ref));
+  WTPSE_REQUIRE(bnb || !(c.mask_ref && c.out1));
+  WTPSE_REQUIRE(!bnb || (c.mask_ref && c.stats && bn.ss && !c.bias && !c.relu_out && !c.gram && bn.c0 >= 0 && bn.c0 < bn.c1 &&
+                         bn.c1 <= c.Cout && bn.c0 % 16 == 0 && (bn.c1 % 16 == 0 || bn.c1 == c.Cout)));
+  WTPSE_REQUIRE(c.C1 == 0 || c.C0 % 16 == 0);   // a channel chunk must not straddle the two inputs
+  WTPSE_REQUIRE(!(c.out_amax && (c.mask_ref || bnb)));
+  // the Gram epilogue works on 16 accumulator rows before the ReLU clamp: it describes the stored map only without one
+  WTPSE_REQUIRE(!c.gram || (c.Cout == 16 && !c.relu_out));
+  // the in-launch tails
+  WTPSE_REQUIRE(!t.tickets || (bnb && t.partial2 && t.gamma && t.invstd && t.coef && t.dgamma && t.dbeta));
+  WTPSE_REQUIRE(!f.tickets || (!bnb && c.stats && !c.gram && f.partial2 && f.gamma && f.beta && f.scale_shift && f.save_mean &&
+                               f.save_invstd && (f.rmean == nullptr) == (f.rvar == nullptr)));
+  if (layout == CONV_X3) {     // no Gram epilogue; prologue coefficients staged in LDS (conv_x3_k: PRO_MAX), 512 only with the 64-channel blocks on 256-pixel tiles
+    const X3Tiling g = x3_tiling(c.B, c.H, c.W, c.Cout, c.ksize);
+    WTPSE_REQUIRE(!c.gram && !(c.in_amax1 && !c.in1) && ((c.C0 + c.C1 + 15) & ~15) <= (g.mt == 2 && !g.half ? 512 : 256));
+  }
+  // 3x3, one input of at most 16 channels, at most 16 output channels, 16-byte-aligned fragments.  (With Cout <= 16 the shared clauses
+  // already leave one output only, Csplit == Cout, and a BatchNorm backward over all channels, bn.c0 == 0 && bn.c1 == Cout.)
+  if (layout == CONV_C16)
+    WTPSE_REQUIRE(c.ksize == 3 && c.C0 <= 16 && c.Cout <= 16 && (((uintptr_t)c.w) & 15) == 0 && !c.in1 && !c.pro1);
+  return 0;
+}
+
+// The launcher of conv_fwd_k: the fp32 kernels (MODE 0..2, chosen here) and the 16-channel 3x3 layers in the x3 arithmetic (MODE 3 | 4:
+// Cout, Cin <= 16, c.w = the layer's fragments from wtpse_pack_conv16_x3).  Arithmetic of the latter: wtpse_x3_terms() == 2 -> x2h
+// (MODE 4), unless the input is a GRADIENT (in_is_grad) whose amax table is not given — a gradient has no scale known a priori, and an
+// extra pass to find it costs more than this HBM-bound kernel gains: those launches stay on x3 (the packed fragments carry both formats).
+static int conv_launch_fwd(const ConvCall& c, bool c16, hipStream_t st) {
+  const bool bnb = c.bn.mean != nullptr;
   ConvArgs a;
-  a.tail = ex.tail;
-  a.ftail = ex.ftail;
-  a.bn_ss = bn.ss; a.bn_mean = bn.mean; a.bn_relu = bn.relu; a.bn_c0 = bnb ? bn.c0 : 0; a.bn_c1 = bnb ? bn.c1 : 0;
-  a.in0 = in0; a.in1 = in1; a.wp = wpacked; a.bias = bias; a.pro0 = pro0; a.pro1 = pro1; a.out0 = out0; a.out1 = out1; a.stats = stats; a.mask = mask_ref; a.gram = gram;
-  a.in_amax = nullptr; a.in_scale = 1.f; a.out_amax = out_amax;
-  a.B = B; a.H = H; a.W = W; a.C0 = C0; a.C1 = C1; a.Cin = C0 + C1; a.CinP = (a.Cin + 3) & ~3;
-  a.Cout = Cout; a.CoutP = (Cout + 15) & ~15; a.Csplit = Csplit; a.pro_relu = pro_relu; a.relu_out = relu_out;
+  a.tail = c.tail;
+  a.ftail = c.ftail;
+  a.bn_ss = c.bn.ss; a.bn_mean = c.bn.mean; a.bn_relu = c.bn.relu; a.bn_c0 = bnb ? c.bn.c0 : 0; a.bn_c1 = bnb ? c.bn.c1 : 0;
+  a.in0 = c.in0; a.in1 = c.in1; a.wp = static_cast<const float*>(c.w); a.bias = c.bias; a.pro0 = c.pro0; a.pro1 = c.pro1;
+  a.out0 = c.out0; a.out1 = c.out1; a.stats = c.stats; a.mask = c.mask_ref; a.gram = c.gram;
+  a.in_amax = c16 ? c.in_amax0 : nullptr; a.in_scale = c16 ? X3_FWD_SCALE : 1.f; a.out_amax = c.out_amax;
+  a.B = c.B; a.H = c.H; a.W = c.W; a.C0 = c.C0; a.C1 = c.C1; a.Cin = c.C0 + c.C1; a.CinP = c16 ? 16 : (a.Cin + 3) & ~3;
+  a.Cout = c.Cout; a.CoutP = (c.Cout + 15) & ~15; a.Csplit = c.Csplit; a.pro_relu = c.pro_relu; a.relu_out = c.relu_out;
   a.tiles_x = a.tiles_y = 0;
-  hipStream_t st = (hipStream_t)stream;
-  int mode = Cout <= 16 ? 0 : (Cout % 64 == 0 ? 2 : 1);  // ragged channel counts run on the 32-wide path
+#define FWD(KS, M, DB) (bnb ? launch_fwd<KS, M, DB, 2>(a, st) : c.mask_ref ? launch_fwd<KS, M, DB, 1>(a, st) : launch_fwd<KS, M, DB, 0>(a, st))
+  if (c16) return (g_x3_terms == 2 && (!c.in_is_grad || c.in_amax0)) ? FWD(3, 4, false) : FWD(3, 3, false);
+  int mode = c.Cout <= 16 ? 0 : (c.Cout % 64 == 0 ? 2 : 1);  // ragged channel counts run on the 32-wide path
   // Grids that cannot give every CU ~3 workgroups (the 16x16 / 32x32 levels): halve the cout block to double the
   // workgroup count, and overlap each workgroup's own loads with its MFMAs (register double-buffering)
-  const int tiles = wtpse_conv_stats_blocks(B, H, W);
+  const int tiles = conv_tiling(c.B, c.H, c.W).tiles;
   if (mode == 2 && tiles * (a.CoutP / 64) < 512) mode = 1;
   if (mode == 1 && tiles * ceil_div(a.CoutP, 32) < 384) mode = 0;   // still under two workgroups per CU: 16-cout blocks
   const int cb = mode == 0 ? 16 : 32 * mode;
-  const bool db = tiles * ceil_div(a.CoutP, cb) < 768 && a.CinP > (mode == 0 ? WTPSE_P16_KC(ksize) : 8);
-#define FWD(KS, M) (bnb ? (db ? launch_fwd<KS, M, true, 2>(a, st) : launch_fwd<KS, M, false, 2>(a, st)) \
-                    : mask_ref ? (db ? launch_fwd<KS, M, true, 1>(a, st) : launch_fwd<KS, M, false, 1>(a, st)) \
-                               : (db ? launch_fwd<KS, M, true, 0>(a, st) : launch_fwd<KS, M, false, 0>(a, st)))
-  if (ksize == 3) {
-    if (mode == 0) return FWD(3, 0);
-    if (mode == 1) return FWD(3, 1);
-    return FWD(3, 2);
-  }
-  if (mode == 0) return FWD(1, 0);
-  if (mode == 1) return FWD(1, 1);
-  return FWD(1, 2);
+  const bool db = tiles * ceil_div(a.CoutP, cb) < 768 && a.CinP > (mode == 0 ? WTPSE_P16_KC(c.ksize) : 8);
+#define FWD_DB(KS, M) (db ? FWD(KS, M, true) : FWD(KS, M, false))
+  if (c.ksize == 3) return mode == 0 ? FWD_DB(3, 0) : mode == 1 ? FWD_DB(3, 1) : FWD_DB(3, 2);
+  return mode == 0 ? FWD_DB(1, 0) : mode == 1 ? FWD_DB(1, 1) : FWD_DB(1, 2);
+#undef FWD_DB
 #undef FWD
+}
+
+int conv_run(const ConvCall& c, int layout, hipStream_t st) {
+  if (const int rc = conv_check(c, layout)) return rc;
+  return layout == CONV_X3 ? conv_launch_x3(c, st) : conv_launch_fwd(c, layout == CONV_C16, st);
 }
 
 // See include/wtpse_hip.h for the contract.
@@ -775,9 +772,11 @@ extern "C" int wtpse_conv_fwd(const float* in0, int C0, const float* in1, int C1
                               const float* bias, const float* pro0, const float* pro1, int pro_relu, float* out0, float* out1,
                               int Csplit, float* stats, int B, int H, int W, int Cout, int ksize, int relu_out,
                               const float* mask_ref, unsigned* out_amax, void* stream) {
-  ConvExtras ex; ex.out_amax = out_amax;
-  return conv_fwd_impl(in0, C0, in1, C1, wpacked, bias, pro0, pro1, pro_relu, out0, out1, Csplit, stats, B, H, W, Cout, ksize,
-                       relu_out, mask_ref, nullptr, stream, ex);
+  ConvCall c;
+  c.in0 = in0; c.C0 = C0; c.in1 = in1; c.C1 = C1; c.w = wpacked; c.bias = bias; c.pro0 = pro0; c.pro1 = pro1; c.pro_relu = pro_relu;
+  c.out0 = out0; c.out1 = out1; c.Csplit = Csplit; c.stats = stats; c.mask_ref = mask_ref; c.out_amax = out_amax;
+  c.B = B; c.H = H; c.W = W; c.Cout = Cout; c.ksize = ksize; c.relu_out = relu_out;
+  return conv_run(c, CONV_FP32, (hipStream_t)stream);
 }
 
 // Data gradient that also performs the first half of the BatchNorm backward of the layer it flows into (include/wtpse_hip.h).
@@ -785,66 +784,31 @@ extern "C" int wtpse_dgrad_bnb(const float* dy, int C, const float* wpacked, flo
                                const float* bn_y, const float* bn_ss, const float* bn_mean, int bn_relu, int bn_c0, int bn_c1,
                                float* stats, int B, int H, int W, int Cout, int ksize, void* stream) {
   WTPSE_REQUIRE(bn_y && bn_ss && bn_mean && stats);
-  ConvExtras ex; ex.bn = BnbArgs{bn_ss, bn_mean, bn_relu, bn_c0, bn_c1};
-  return conv_fwd_impl(dy, C, nullptr, 0, wpacked, nullptr, nullptr, nullptr, 0, out0, out1, Csplit, stats, B, H, W, Cout, ksize, 0,
-                       bn_y, nullptr, stream, ex);
+  ConvCall c;
+  c.in0 = dy; c.C0 = C; c.w = wpacked; c.out0 = out0; c.out1 = out1; c.Csplit = Csplit; c.stats = stats; c.mask_ref = bn_y;
+  c.bn.ss = bn_ss; c.bn.mean = bn_mean; c.bn.relu = bn_relu; c.bn.c0 = bn_c0; c.bn.c1 = bn_c1;
+  c.B = B; c.H = H; c.W = W; c.Cout = Cout; c.ksize = ksize;
+  return conv_run(c, CONV_FP32, (hipStream_t)stream);
 }
 
-// ---- the 16-channel 3x3 layers in the x3 arithmetic (MODE 3): Cout <= 16, Cin <= 16, one input tensor.  wx16: the layer's
-// fragments from wtpse_pack_conv16_x3.  Everything optional: bias, prologue, ReLU, BatchNorm (sum, sum^2) partials `stats`,
-// Gram partials `gram_partial` (Cout == 16), ReLU mask `mask_ref`, or — with ex.bn.mean — the BatchNorm-backward epilogue of
-// wtpse_dgrad_bnb over all output channels (mask_ref = that layer's raw conv output).
-// Arithmetic: wtpse_x3_terms() == 2 -> x2h (MODE 4), unless the input is a GRADIENT (in_is_grad) whose amax table is not given — a
-// gradient has no scale known a priori, and an extra pass to find it costs more than this HBM-bound kernel gains: those launches stay
-// on x3 (the packed fragments carry both formats).
-static int conv16_x3_impl(const float* in0, int C0, const unsigned short* wx16, const float* bias, const float* pro0,
-                          int pro_relu, float* out0, float* stats, float* gram_partial, const float* mask_ref, int B, int H,
-                          int W, int Cout, int relu_out, int in_is_grad, const unsigned* in_amax, void* stream,
-                          const ConvExtras& ex = ConvExtras()) {
-  const float* const bn_ss = ex.bn.ss; const float* const bn_mean = ex.bn.mean;
-  WTPSE_REQUIRE(in0 && wx16 && out0 && B > 0 && H > 0 && W > 0 && C0 > 0 && C0 <= 16 && Cout > 0 && Cout <= 16);
-  WTPSE_REQUIRE(!(stats && relu_out) && !(gram_partial && (Cout != 16 || relu_out)));
-  WTPSE_REQUIRE((((uintptr_t)wx16) & 15) == 0);
-  const bool bnb = bn_mean != nullptr;
-  WTPSE_REQUIRE(bnb || !(stats && mask_ref));
-  WTPSE_REQUIRE(!bnb || (mask_ref && stats && bn_ss && !bias && !relu_out && !gram_partial));
-  WTPSE_REQUIRE(!(ex.out_amax && (mask_ref || bnb)));
-  WTPSE_REQUIRE(tails_ok(ex.tail, ex.ftail, bnb, stats, gram_partial));
-  ConvArgs a;
-  a.tail = ex.tail;
-  a.ftail = ex.ftail;
-  a.in0 = in0; a.in1 = nullptr; a.wp = reinterpret_cast<const float*>(wx16); a.bias = bias; a.pro0 = pro0; a.pro1 = nullptr;
-  a.out0 = out0; a.out1 = nullptr; a.stats = stats; a.mask = mask_ref; a.gram = gram_partial;
-  a.bn_ss = bn_ss; a.bn_mean = bn_mean; a.bn_relu = ex.bn.relu; a.bn_c0 = 0; a.bn_c1 = bnb ? Cout : 0;
-  a.B = B; a.H = H; a.W = W; a.C0 = C0; a.C1 = 0; a.Cin = C0; a.CinP = 16;
-  a.Cout = Cout; a.CoutP = 16; a.Csplit = Cout; a.pro_relu = pro_relu; a.relu_out = relu_out;
-  a.tiles_x = a.tiles_y = 0;
-  a.in_amax = in_amax; a.in_scale = X3_FWD_SCALE; a.out_amax = ex.out_amax;
-  hipStream_t st = (hipStream_t)stream;
-  if (g_x3_terms == 2 && (!in_is_grad || in_amax)) {
-    if (bnb) return launch_fwd<3, 4, false, 2>(a, st);
-    if (mask_ref) return launch_fwd<3, 4, false, 1>(a, st);
-    return launch_fwd<3, 4, false, 0>(a, st);
-  }
-  if (bnb) return launch_fwd<3, 3, false, 2>(a, st);
-  if (mask_ref) return launch_fwd<3, 3, false, 1>(a, st);
-  return launch_fwd<3, 3, false, 0>(a, st);
-}
-
+// The 16-channel 3x3 layers in the x3 arithmetic (conv_launch_fwd).  Everything optional: bias, prologue, ReLU, BatchNorm (sum, sum^2)
+// partials `stats`, Gram partials `gram_partial` (Cout == 16), ReLU mask `mask_ref`, or — with bn_mean — the BatchNorm-backward epilogue
+// of wtpse_dgrad_bnb over all output channels (mask_ref = that layer's raw conv output).
 extern "C" int wtpse_conv16_x3(const float* in0, int C0, const unsigned short* wx16, const float* bias, const float* pro0,
                                int pro_relu, float* out0, float* stats, float* gram_partial, const float* mask_ref,
                                const float* bn_ss, const float* bn_mean, int bn_relu, int B, int H, int W, int Cout, int relu_out,
                                int in_is_grad, const unsigned* in_amax, unsigned* out_amax, void* stream) {
-  ConvExtras ex; ex.bn = BnbArgs{bn_ss, bn_mean, bn_relu, 0, 0}; ex.out_amax = out_amax;
-  return conv16_x3_impl(in0, C0, wx16, bias, pro0, pro_relu, out0, stats, gram_partial, mask_ref, B, H, W, Cout, relu_out,
-                        in_is_grad, in_amax, stream, ex);
+  ConvCall c;
+  c.in0 = in0; c.C0 = C0; c.w = wx16; c.bias = bias; c.pro0 = pro0; c.pro_relu = pro_relu; c.out0 = out0; c.Csplit = Cout;
+  c.stats = stats; c.gram = gram_partial; c.mask_ref = mask_ref; c.in_amax0 = in_amax; c.in_is_grad = in_is_grad; c.out_amax = out_amax;
+  c.bn.ss = bn_ss; c.bn.mean = bn_mean; c.bn.relu = bn_relu; c.bn.c1 = Cout;
+  c.B = B; c.H = H; c.W = W; c.Cout = Cout; c.ksize = 3; c.relu_out = relu_out;
+  return conv_run(c, CONV_C16, (hipStream_t)stream);
 }
 
-// ---- wtpse_dgrad_bnb / wtpse_dgrad_x3_bnb / wtpse_conv16_x3(bn_mean) whose launch ALSO finishes the statistics: the last
-// workgroups fold the partials (common.h: bnb_tail) and leave (k1, k2, k3) in `coef`, dgamma / dbeta (+)= in place, so that the
-// BatchNorm backward is this launch + wtpse_bn_bwd_apply_coef.  layout: 0 fp32 (`wd`), 1 x3, 2 the 16-channel x3 fragments.
-// ---- a forward convolution in front of a train-mode BatchNorm whose launch ALSO finishes the statistics (common.h: bnf_tail):
-// wtpse_conv_fwd / wtpse_conv_fwd_x3 / wtpse_conv16_x3 with `stats` + wtpse_bn_finalize in one launch.  layout as below.
+// A forward convolution in front of a train-mode BatchNorm whose launch ALSO finishes the statistics (common.h: bnf_tail):
+// wtpse_conv_fwd / wtpse_conv_fwd_x3 / wtpse_conv16_x3 with `stats` + wtpse_bn_finalize in one launch.  layout: 0 fp32 (`wf`),
+// 1 x3, 2 the 16-channel x3 fragments.
 extern "C" int wtpse_conv_fwd_bnf(const float* in0, int C0, const float* in1, int C1, const void* wpacked, int layout,
                                   const float* bias, const float* pro0, const float* pro1, int pro_relu, float* out0, float* stats,
                                   const float* gamma, const float* beta, float* running_mean, float* running_var,
@@ -852,48 +816,45 @@ extern "C" int wtpse_conv_fwd_bnf(const float* in0, int C0, const float* in1, in
                                   float* save_invstd, double* partial2, unsigned* tickets, int B, int H, int W, int Cout, int ksize,
                                   const unsigned* in_amax0, const unsigned* in_amax1, unsigned* act_amax, void* stream) {
   WTPSE_REQUIRE(stats && gamma && beta && scale_shift && save_mean && save_invstd && partial2 && tickets);
-  WTPSE_REQUIRE(layout >= 0 && layout <= 2);
-  ConvExtras ex;
-  BnfTail& t = ex.ftail;
+  ConvCall c;
+  c.in0 = in0; c.C0 = C0; c.in1 = in1; c.C1 = C1; c.w = wpacked; c.bias = bias; c.pro0 = pro0; c.pro1 = pro1; c.pro_relu = pro_relu;
+  c.out0 = out0; c.Csplit = Cout; c.stats = stats; c.in_amax0 = in_amax0; c.in_amax1 = in_amax1;
+  BnfTail& t = c.ftail;
   t.partial2 = partial2; t.tickets = tickets; t.gamma = gamma; t.beta = beta; t.rmean = running_mean; t.rvar = running_var;
   t.nbt = num_batches; t.momentum = momentum; t.eps = eps; t.scale_shift = scale_shift; t.save_mean = save_mean;
   t.save_invstd = save_invstd; t.act_amax = act_amax;
-  if (layout == 1)
-    return conv_fwd_x3_ftail(in0, C0, in1, C1, static_cast<const unsigned short*>(wpacked), bias, pro0, pro1, pro_relu, out0,
-                             stats, &t, B, H, W, Cout, ksize, in_amax0, in_amax1, stream);
-  if (layout == 2) {
-    WTPSE_REQUIRE(ksize == 3 && !in1 && C1 == 0 && !pro1);
-    return conv16_x3_impl(in0, C0, static_cast<const unsigned short*>(wpacked), bias, pro0, pro_relu, out0, stats, nullptr, nullptr,
-                          B, H, W, Cout, 0, 0, in_amax0, stream, ex);
-  }
-  return conv_fwd_impl(in0, C0, in1, C1, static_cast<const float*>(wpacked), bias, pro0, pro1, pro_relu, out0, nullptr, Cout, stats,
-                       B, H, W, Cout, ksize, 0, nullptr, nullptr, stream, ex);
+  c.B = B; c.H = H; c.W = W; c.Cout = Cout; c.ksize = ksize;
+  return conv_run(c, layout, (hipStream_t)stream);
 }
 
 extern "C" int wtpse_bnb_tail_partial2(int nblk, int Cout) { return bnb_tail_groups(nblk) * bnb_tail_ctot(Cout) * 2; }
 extern "C" int wtpse_bnb_tail_tickets(int nblk, int Cout) { return bnb_tail_t2off(nblk, Cout) + (Cout + 15) / 16; }
+
+// wtpse_dgrad_bnb / wtpse_dgrad_x3_bnb / wtpse_conv16_x3(bn_mean) whose launch ALSO finishes the statistics: the last workgroups
+// fold the partials (common.h: bnb_tail) and leave (k1, k2, k3) in `coef`, dgamma / dbeta (+)= in place, so that the BatchNorm
+// backward is this launch + wtpse_bn_bwd_apply_coef.  layout: 0 fp32 (`wd`), 1 x3, 2 the 16-channel x3 fragments.  The body of both
+// entry points: `c` holds the data gradient and the tail as given, without or with tail.dbias.
+static int dgrad_bnb_coef(ConvCall c, int layout, void* stream) {
+  const BnbTail& t = c.tail;
+  WTPSE_REQUIRE(c.mask_ref && c.bn.ss && c.bn.mean && c.stats && t.gamma && t.invstd && t.coef && t.dgamma && t.dbeta && t.partial2 &&
+                t.tickets);
+  c.in_is_grad = 1;
+  return conv_run(c, layout, (hipStream_t)stream);
+}
 
 extern "C" int wtpse_dgrad_bnb_coef(const float* dy, int C, const void* wpacked, int layout, float* out0, float* out1, int Csplit,
                                     const float* bn_y, const float* bn_ss, const float* bn_mean, int bn_relu, int bn_c0, int bn_c1,
                                     float* stats, const float* gamma, const float* invstd, float* coef, float* dgamma,
                                     float* dbeta, int accumulate, double* partial2, unsigned* tickets, int B, int H, int W,
                                     int Cout, int ksize, const unsigned* in_amax, void* stream) {
-  WTPSE_REQUIRE(bn_y && bn_ss && bn_mean && stats && gamma && invstd && coef && dgamma && dbeta && partial2 && tickets);
-  WTPSE_REQUIRE(layout >= 0 && layout <= 2);
-  ConvExtras ex; ex.bn = BnbArgs{bn_ss, bn_mean, bn_relu, bn_c0, bn_c1};
-  BnbTail& t = ex.tail;
+  ConvCall c;
+  c.in0 = dy; c.C0 = C; c.w = wpacked; c.out0 = out0; c.out1 = out1; c.Csplit = Csplit; c.stats = stats; c.mask_ref = bn_y;
+  c.bn.ss = bn_ss; c.bn.mean = bn_mean; c.bn.relu = bn_relu; c.bn.c0 = bn_c0; c.bn.c1 = bn_c1; c.in_amax0 = in_amax;
+  BnbTail& t = c.tail;
   t.partial2 = partial2; t.tickets = tickets; t.gamma = gamma; t.invstd = invstd; t.coef = coef; t.dgamma = dgamma; t.dbeta = dbeta;
   t.accumulate = accumulate;
-  if (layout == 1)
-    return dgrad_x3_bnb_tail(dy, C, static_cast<const unsigned short*>(wpacked), out0, out1, Csplit, bn_y, bn_ss, bn_mean,
-                             bn_relu, bn_c0, bn_c1, stats, &t, B, H, W, Cout, ksize, in_amax, stream);
-  if (layout == 2) {
-    WTPSE_REQUIRE(ksize == 3 && !out1 && Csplit == Cout && bn_c0 == 0 && bn_c1 == Cout);
-    return conv16_x3_impl(dy, C, static_cast<const unsigned short*>(wpacked), nullptr, nullptr, 0, out0, stats, nullptr, bn_y, B, H, W,
-                          Cout, 0, 1, in_amax, stream, ex);
-  }
-  return conv_fwd_impl(dy, C, nullptr, 0, static_cast<const float*>(wpacked), nullptr, nullptr, nullptr, 0, out0, out1, Csplit, stats,
-                       B, H, W, Cout, ksize, 0, bn_y, nullptr, stream, ex);
+  c.B = B; c.H = H; c.W = W; c.Cout = Cout; c.ksize = ksize;
+  return dgrad_bnb_coef(c, layout, stream);
 }
 
 // wtpse_dgrad_bnb_coef into a BatchNorm on frozen (running) statistics: bn_mean / invstd = the running mean and 1 / sqrt(var + eps);
@@ -904,22 +865,15 @@ extern "C" int wtpse_dgrad_bnb_coef_frozen(const float* dy, int C, const void* w
                                            float* dgamma, float* dbeta, float* dbias, int accumulate, double* partial2,
                                            unsigned* tickets, int B, int H, int W, int Cout, int ksize, const unsigned* in_amax,
                                            void* stream) {
-  WTPSE_REQUIRE(bn_y && bn_ss && bn_mean && stats && gamma && invstd && coef && dgamma && dbeta && dbias && partial2 && tickets);
-  WTPSE_REQUIRE(layout >= 0 && layout <= 2);
-  ConvExtras ex; ex.bn = BnbArgs{bn_ss, bn_mean, bn_relu, bn_c0, bn_c1};
-  BnbTail& t = ex.tail;
+  WTPSE_REQUIRE(dbias);
+  ConvCall c;
+  c.in0 = dy; c.C0 = C; c.w = wpacked; c.out0 = out0; c.out1 = out1; c.Csplit = Csplit; c.stats = stats; c.mask_ref = bn_y;
+  c.bn.ss = bn_ss; c.bn.mean = bn_mean; c.bn.relu = bn_relu; c.bn.c0 = bn_c0; c.bn.c1 = bn_c1; c.in_amax0 = in_amax;
+  BnbTail& t = c.tail;
   t.partial2 = partial2; t.tickets = tickets; t.gamma = gamma; t.invstd = invstd; t.coef = coef; t.dgamma = dgamma; t.dbeta = dbeta;
   t.dbias = dbias; t.accumulate = accumulate;
-  if (layout == 1)
-    return dgrad_x3_bnb_tail(dy, C, static_cast<const unsigned short*>(wpacked), out0, out1, Csplit, bn_y, bn_ss, bn_mean,
-                             bn_relu, bn_c0, bn_c1, stats, &t, B, H, W, Cout, ksize, in_amax, stream);
-  if (layout == 2) {
-    WTPSE_REQUIRE(ksize == 3 && !out1 && Csplit == Cout && bn_c0 == 0 && bn_c1 == Cout);
-    return conv16_x3_impl(dy, C, static_cast<const unsigned short*>(wpacked), nullptr, nullptr, 0, out0, stats, nullptr, bn_y, B, H, W,
-                          Cout, 0, 1, in_amax, stream, ex);
-  }
-  return conv_fwd_impl(dy, C, nullptr, 0, static_cast<const float*>(wpacked), nullptr, nullptr, nullptr, 0, out0, out1, Csplit, stats,
-                       B, H, W, Cout, ksize, 0, bn_y, nullptr, stream, ex);
+  c.B = B; c.H = H; c.W = W; c.Cout = Cout; c.ksize = ksize;
+  return dgrad_bnb_coef(c, layout, stream);
 }
 
 // Weight fragments of the 16-channel x3 / x2h path, all convs of a network in one launch.  desc: n_desc x 8 ints {w_off, Cout, Cin,
@@ -982,11 +936,12 @@ extern "C" int wtpse_pack_conv16_x3(const float* params, const int* desc, int n_
 extern "C" int wtpse_conv_fwd_gram(const float* in0, int C0, const float* wpacked, const float* bias, const float* pro0,
                                    int pro_relu, float* out0, float* gram_partial, int B, int H, int W, int Cout, int relu_out,
                                    unsigned* out_amax, void* stream) {
-  WTPSE_REQUIRE(gram_partial && Cout == 16);
-  WTPSE_REQUIRE(!relu_out);     // the Gram epilogue works on the accumulators before the ReLU clamp: it describes the stored map only without one
-  ConvExtras ex; ex.out_amax = out_amax;
-  return conv_fwd_impl(in0, C0, nullptr, 0, wpacked, bias, pro0, nullptr, pro_relu, out0, nullptr, Cout, nullptr, B, H, W, Cout, 3,
-                       relu_out, nullptr, gram_partial, stream, ex);
+  WTPSE_REQUIRE(gram_partial);
+  ConvCall c;
+  c.in0 = in0; c.C0 = C0; c.w = wpacked; c.bias = bias; c.pro0 = pro0; c.pro_relu = pro_relu; c.out0 = out0; c.Csplit = Cout;
+  c.gram = gram_partial; c.out_amax = out_amax;
+  c.B = B; c.H = H; c.W = W; c.Cout = Cout; c.ksize = 3; c.relu_out = relu_out;
+  return conv_run(c, CONV_FP32, (hipStream_t)stream);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1349,16 +1304,26 @@ void wgrad_reduce_launch2(const float* slab, int ksplit, int n, float* dw, int a
                      slab_b, n_b, db);
 }
 
+// conv_wgrad_k: the tiles of the forward kernels; MB couts x (ngroups groups of cg cins) per workgroup along x
+struct WgradGeometry {
+  Tiling t;
+  int MB, cg, ngroups;
+};
+static WgradGeometry wgrad_geometry(int B, int H, int W, int Cin, int Cout) {
+  WgradGeometry g;
+  g.t = conv_tiling(B, H, W);
+  g.MB = Cout > 16 ? 32 : 16;
+  g.cg = Cin < g.MB ? Cin : g.MB;
+  g.ngroups = ceil_div(Cin, g.cg);   // a ragged last group re-reads valid planes; its slots are never stored
+  return g;
+}
+
 extern "C" int wtpse_wgrad_ksplit(int B, int H, int W, int Cin, int Cout) {
-  const int TW = W <= 16 ? 16 : 32, TH = 256 / TW;
-  const int ntiles = B * ceil_div(W, TW) * ceil_div(H, TH);
-  const bool p32 = Cout > 16;
-  const int MB = p32 ? 32 : 16;
-  const int cg = Cin < MB ? Cin : MB;
-  const int nx = ceil_div(Cout, MB) * ceil_div(Cin, cg);
+  const WgradGeometry g = wgrad_geometry(B, H, W, Cin, Cout);
+  const int nx = ceil_div(Cout, g.MB) * g.ngroups;
   int ks = 512 / nx;   // ~2 workgroups per CU (LDS-limited residency of the 32-wide path)
   if (ks < 1) ks = 1;
-  if (ks > ntiles) ks = ntiles;
+  if (ks > g.t.tiles) ks = g.t.tiles;
   return ks;
 }
 
@@ -1369,21 +1334,20 @@ extern "C" int wtpse_conv_wgrad(const float* dy, const float* x0, int C0, const 
   WTPSE_REQUIRE(ksize == 1 || ksize == 3);
   WTPSE_REQUIRE((C1 == 0) == (x1 == nullptr));
   WTPSE_REQUIRE((dbias == nullptr) == (dbias_slab == nullptr));
-  const bool p32 = Cout > 16;
   WgradArgs a;
   a.dy = dy; a.x0 = x0; a.x1 = x1; a.pro0 = pro0; a.pro1 = pro1; a.slab = slab; a.dbias = dbias_slab;
   a.B = B; a.H = H; a.W = W; a.C0 = C0; a.C1 = C1; a.Cin = C0 + C1; a.Cout = Cout; a.pro_relu = pro_relu;
-  const int MB = p32 ? 32 : 16;
-  const int taps = ksize * ksize;
-  a.cg = a.Cin < MB ? a.Cin : MB;
-  a.ngroups = ceil_div(a.Cin, a.cg);   // a ragged last group re-reads valid planes; its slots are never stored
+  const WgradGeometry g = wgrad_geometry(B, H, W, a.Cin, Cout);
+  const int MB = g.MB, taps = ksize * ksize;
+  const bool p32 = MB == 32;
+  a.cg = g.cg;
+  a.ngroups = g.ngroups;
   WTPSE_REQUIRE(C1 == 0 || C0 % 16 == 0);   // a 16-channel half group must not straddle the two inputs
   a.nblk = ceil_div(a.cg * taps, MB);
-  const bool narrow = W <= 16;
-  const int TW = narrow ? 16 : 32, TH = 256 / TW;
-  a.tiles_x = ceil_div(W, TW);
-  a.tiles_y = ceil_div(H, TH);
-  a.ntiles = B * a.tiles_x * a.tiles_y;
+  const bool narrow = g.t.TW == 16;
+  a.tiles_x = g.t.tiles_x;
+  a.tiles_y = g.t.tiles_y;
+  a.ntiles = g.t.tiles;
   WTPSE_REQUIRE(ksplit <= a.ntiles);
   hipStream_t st = (hipStream_t)stream;
   dim3 grid((unsigned)(ceil_div(Cout, MB) * a.ngroups), (unsigned)ksplit);

@@ -126,7 +126,7 @@ extern "C" int wtpse_x3_small_wide(int on) {
 static bool x3_small_tiles(int B, int H, int W, int CoutP, bool mt2) {
   if (mt2) return false;
   if (W > 16) return g_x3_small_wide != 0 && W % 32 == 0;
-  return B * ceil_div(H, 16) * ceil_div(W, 16) * (CoutP / 32) < 512;
+  return conv_tiling(B, H, W).tiles * (CoutP / 32) < 512;
 }
 
 // 3x3 launches take conv_x3r_k (register-fed weights) unless WTPSE_X3R=0 / wtpse_x3r_enable(0): the two kernels give bitwise the
@@ -154,8 +154,7 @@ extern "C" int wtpse_x3_xcd(int on) {
 extern "C" int wtpse_tuning_state(void) { return g_x3_terms | (g_x3r << 4) | (g_x3_xcd << 8) | (g_x3_small_wide << 12); }
 
 static bool x3_mt2(int B, int H, int W, int CoutP) {
-  const int TW = W <= 16 ? 16 : 32, TH = 256 / TW;
-  const int tiles = B * ceil_div(W, TW) * ceil_div(H, TH);
+  const int tiles = conv_tiling(B, H, W).tiles;
   bool mt2 = (CoutP % 64 == 0) && tiles * (CoutP / 64) >= 512;
   // tuning override 1 | 2, read ONCE per process: the size queries (stats blocks) and the launches must agree on the tiling, also
   // when a recorded launch plan replays the launches later
@@ -173,60 +172,43 @@ static bool x3_mt2(int B, int H, int W, int CoutP) {
 // up2.conv1 -8..-10 %: profiles/r04_microbench_x3.txt).
 static int g_x3_half_min = [] { const char* e = getenv("WTPSE_X3_HALF"); if (e && e[0] == '0') return 0;
                                 const char* m = getenv("WTPSE_X3_HALF_MIN"); const int v = m ? atoi(m) : 256; return v > 0 ? v : 256; }();
-static bool x3_half(int B, int H, int W, int CoutP, int ksize) {
-  if (ksize != 3 || g_x3_half_min == 0 || g_x3r == 0 || CoutP % 64 != 0 || x3_mt2(B, H, W, CoutP)) return false;
-  const int TW = W <= 16 ? 16 : 32, TH = 128 / TW;
-  return B * ceil_div(W, TW) * ceil_div(H, TH) * (CoutP / 64) >= g_x3_half_min;
+static bool x3_half(int B, int H, int W, int CoutP, int ksize, bool mt2) {
+  if (ksize != 3 || g_x3_half_min == 0 || g_x3r == 0 || CoutP % 64 != 0 || mt2) return false;
+  return conv_tiling(B, H, W, 128).tiles * (CoutP / 64) >= g_x3_half_min;
+}
+
+// The tiling of a launch, for the size query and the launcher alike (they must agree, also when a recorded plan replays the launch).
+X3Tiling x3_tiling(int B, int H, int W, int Cout, int ksize) {
+  const int CoutP = (Cout + 31) & ~31;
+  const bool mt2 = x3_mt2(B, H, W, CoutP);
+  X3Tiling g;
+  g.half = x3_half(B, H, W, CoutP, ksize, mt2) ? 1 : 0;
+  g.small = !g.half && x3_small_tiles(B, H, W, CoutP, mt2) ? 1 : 0;
+  g.mt = (mt2 || g.half) ? 2 : 1;
+  g.px = (g.half || g.small) ? 128 : 256;
+  g.t = conv_tiling(B, H, W, g.px);
+  return g;
 }
 
 // workgroups along x of a wtpse_conv_fwd_x3 launch = rows of its `stats` partials
-extern "C" int wtpse_conv_x3_stats_blocks(int B, int H, int W, int Cout, int ksize) {
-  const int CoutP = (Cout + 31) & ~31;
-  const bool small = x3_half(B, H, W, CoutP, ksize) || x3_small_tiles(B, H, W, CoutP, x3_mt2(B, H, W, CoutP));
-  const int TW = W <= 16 ? 16 : 32, TH = (small ? 128 : 256) / TW;
-  return B * ceil_div(W, TW) * ceil_div(H, TH);
-}
+extern "C" int wtpse_conv_x3_stats_blocks(int B, int H, int W, int Cout, int ksize) { return x3_tiling(B, H, W, Cout, ksize).t.tiles; }
 
-static int conv_x3_impl(const float* in0, int C0, const float* in1, int C1, const unsigned short* wpacked,
-                        const float* bias, const float* pro0, const float* pro1, int pro_relu, float* out0, float* out1,
-                        int Csplit, float* stats, int B, int H, int W, int Cout, int ksize, int relu_out,
-                        const float* mask_ref, const float* bn_ss, const float* bn_mean, int bn_relu, int bn_c0, int bn_c1,
-                        const unsigned* in_amax, void* stream, BnbTail tail = bnb_tail_none(), BnfTail ftail = bnf_tail_none(),
-                        const unsigned* in_amax1 = nullptr, unsigned* out_amax = nullptr) {
-  WTPSE_REQUIRE(in0 && wpacked && out0 && B > 0 && H > 0 && W > 0 && C0 > 0 && C1 >= 0 && Cout > 0);
-  WTPSE_REQUIRE(!(in_amax1 && !in1) && !(out_amax && (mask_ref || bn_mean)));
-  WTPSE_REQUIRE(ksize == 1 || ksize == 3);
-  WTPSE_REQUIRE((C1 == 0) == (in1 == nullptr));
-  WTPSE_REQUIRE(Csplit > 0 && Csplit <= Cout && ((Csplit == Cout) == (out1 == nullptr)));
-  WTPSE_REQUIRE(Csplit == Cout || Csplit % 16 == 0);
-  WTPSE_REQUIRE(!(stats && relu_out));
-  const bool bnb = bn_mean != nullptr;
-  WTPSE_REQUIRE(bnb || !(stats && mask_ref));
-  WTPSE_REQUIRE(bnb || !(mask_ref && out1));
-  WTPSE_REQUIRE(!bnb || (mask_ref && stats && bn_ss && !bias && !relu_out && bn_c0 >= 0 && bn_c0 < bn_c1 && bn_c1 <= Cout &&
-                         bn_c0 % 16 == 0 && (bn_c1 % 16 == 0 || bn_c1 == Cout)));
-  WTPSE_REQUIRE(C1 == 0 || C0 % 16 == 0);
-
+// The launcher of conv_x3_k / conv_x3r_k (conv_run, conv.hip, has checked the call).
+int conv_launch_x3(const ConvCall& c, hipStream_t st) {
+  const bool bnb = c.bn.mean != nullptr;
   ConvX3Args a;
-  a.in0 = in0; a.in1 = in1; a.wx = wpacked; a.bias = bias; a.pro0 = pro0; a.pro1 = pro1; a.out0 = out0; a.out1 = out1;
-  a.stats = stats; a.mask = mask_ref;
-  a.in_amax = in_amax; a.in_amax1 = in_amax1; a.in_scale = X3_FWD_SCALE; a.out_amax = out_amax;
-  a.bn_ss = bn_ss; a.bn_mean = bn_mean; a.bn_relu = bn_relu; a.bn_c0 = bnb ? bn_c0 : 0; a.bn_c1 = bnb ? bn_c1 : 0;
-  WTPSE_REQUIRE(!tail.tickets || (bnb && tail.partial2 && tail.gamma && tail.invstd && tail.coef && tail.dgamma && tail.dbeta));
-  a.tail = tail;
-  WTPSE_REQUIRE(!ftail.tickets || (!bnb && stats && ftail.partial2 && ftail.gamma && ftail.beta && ftail.scale_shift && ftail.save_mean &&
-                                   ftail.save_invstd && (ftail.rmean == nullptr) == (ftail.rvar == nullptr)));
-  a.ftail = ftail;
-  a.B = B; a.H = H; a.W = W; a.C0 = C0; a.C1 = C1; a.Cin = C0 + C1; a.CinP = (a.Cin + 15) & ~15;
-  a.Cout = Cout; a.CoutP = (Cout + 31) & ~31; a.Csplit = Csplit; a.pro_relu = pro_relu; a.relu_out = relu_out;
+  a.in0 = c.in0; a.in1 = c.in1; a.wx = static_cast<const unsigned short*>(c.w); a.bias = c.bias; a.pro0 = c.pro0; a.pro1 = c.pro1;
+  a.out0 = c.out0; a.out1 = c.out1; a.stats = c.stats; a.mask = c.mask_ref;
+  a.in_amax = c.in_amax0; a.in_amax1 = c.in_amax1; a.in_scale = X3_FWD_SCALE; a.out_amax = c.out_amax;
+  a.bn_ss = c.bn.ss; a.bn_mean = c.bn.mean; a.bn_relu = c.bn.relu; a.bn_c0 = bnb ? c.bn.c0 : 0; a.bn_c1 = bnb ? c.bn.c1 : 0;
+  a.tail = c.tail;
+  a.ftail = c.ftail;
+  a.B = c.B; a.H = c.H; a.W = c.W; a.C0 = c.C0; a.C1 = c.C1; a.Cin = c.C0 + c.C1; a.CinP = (a.Cin + 15) & ~15;
+  a.Cout = c.Cout; a.CoutP = (c.Cout + 31) & ~31; a.Csplit = c.Csplit; a.pro_relu = c.pro_relu; a.relu_out = c.relu_out;
   a.tiles_x = a.tiles_y = 0;
-  hipStream_t st = (hipStream_t)stream;
-  const bool mt2 = x3_mt2(B, H, W, a.CoutP);
-  WTPSE_REQUIRE(a.CinP <= (mt2 ? 512 : 256));            // prologue coefficients staged in LDS (conv_x3_k: PRO_MAX)
   X3Launch L;
-  L.ksize = ksize; L.mt2 = mt2 ? 1 : 0; L.half = x3_half(B, H, W, a.CoutP, ksize) ? 1 : 0;
-  L.small = x3_small_tiles(B, H, W, a.CoutP, mt2) ? 1 : 0;
-  L.epi = bnb ? 2 : mask_ref ? 1 : 0; L.x3r = g_x3r; L.xcd = g_x3_xcd;
+  L.g = x3_tiling(c.B, c.H, c.W, c.Cout, c.ksize);
+  L.ksize = c.ksize; L.epi = bnb ? 2 : c.mask_ref ? 1 : 0; L.x3r = g_x3r; L.xcd = g_x3_xcd;
   return g_x3_terms == 1 ? x3_dispatch_t1(a, L, st) : g_x3_terms == 2 ? x3_dispatch_t2(a, L, st) : x3_dispatch_t3(a, L, st);
 }
 
@@ -237,8 +219,12 @@ extern "C" int wtpse_conv_fwd_x3(const float* in0, int C0, const float* in1, int
                                  int Csplit, float* stats, int B, int H, int W, int Cout, int ksize, int relu_out,
                                  const float* mask_ref, const unsigned* in_amax, const unsigned* in_amax1, unsigned* out_amax,
                                  void* stream) {
-  return conv_x3_impl(in0, C0, in1, C1, wpacked, bias, pro0, pro1, pro_relu, out0, out1, Csplit, stats, B, H, W, Cout, ksize,
-                      relu_out, mask_ref, nullptr, nullptr, 0, 0, 0, in_amax, stream, bnb_tail_none(), bnf_tail_none(), in_amax1, out_amax);
+  ConvCall c;
+  c.in0 = in0; c.C0 = C0; c.in1 = in1; c.C1 = C1; c.w = wpacked; c.bias = bias; c.pro0 = pro0; c.pro1 = pro1; c.pro_relu = pro_relu;
+  c.out0 = out0; c.out1 = out1; c.Csplit = Csplit; c.stats = stats; c.mask_ref = mask_ref;
+  c.in_amax0 = in_amax; c.in_amax1 = in_amax1; c.out_amax = out_amax;
+  c.B = B; c.H = H; c.W = W; c.Cout = Cout; c.ksize = ksize; c.relu_out = relu_out;
+  return conv_run(c, CONV_X3, (hipStream_t)stream);
 }
 
 // Data gradient that also performs the first half of the BatchNorm backward of the layer it flows into (include/wtpse_hip.h).
@@ -246,26 +232,11 @@ extern "C" int wtpse_dgrad_x3_bnb(const float* dy, int C, const unsigned short* 
                                   const float* bn_y, const float* bn_ss, const float* bn_mean, int bn_relu, int bn_c0, int bn_c1,
                                   float* stats, int B, int H, int W, int Cout, int ksize, const unsigned* in_amax, void* stream) {
   WTPSE_REQUIRE(bn_y && bn_ss && bn_mean && stats);
-  return conv_x3_impl(dy, C, nullptr, 0, wpacked, nullptr, nullptr, nullptr, 0, out0, out1, Csplit, stats, B, H, W, Cout, ksize, 0,
-                      bn_y, bn_ss, bn_mean, bn_relu, bn_c0, bn_c1, in_amax, stream);
-}
-
-// wtpse_conv_fwd_bnf (conv.hip), x3 layout
-int conv_fwd_x3_ftail(const float* in0, int C0, const float* in1, int C1, const unsigned short* wpacked, const float* bias,
-                      const float* pro0, const float* pro1, int pro_relu, float* out0, float* stats, const BnfTail* ftail, int B,
-                      int H, int W, int Cout, int ksize, const unsigned* in_amax0, const unsigned* in_amax1, void* stream) {
-  WTPSE_REQUIRE(ftail && stats);
-  return conv_x3_impl(in0, C0, in1, C1, wpacked, bias, pro0, pro1, pro_relu, out0, nullptr, Cout, stats, B, H, W, Cout, ksize, 0,
-                      nullptr, nullptr, nullptr, 0, 0, 0, in_amax0, stream, bnb_tail_none(), *ftail, in_amax1);
-}
-
-// wtpse_dgrad_bnb_coef (conv.hip), x3 layout
-int dgrad_x3_bnb_tail(const float* dy, int C, const unsigned short* wpacked, float* out0, float* out1, int Csplit,
-                      const float* bn_y, const float* bn_ss, const float* bn_mean, int bn_relu, int bn_c0, int bn_c1, float* stats,
-                      const BnbTail* tail, int B, int H, int W, int Cout, int ksize, const unsigned* in_amax, void* stream) {
-  WTPSE_REQUIRE(bn_y && bn_ss && bn_mean && stats && tail);
-  return conv_x3_impl(dy, C, nullptr, 0, wpacked, nullptr, nullptr, nullptr, 0, out0, out1, Csplit, stats, B, H, W, Cout, ksize, 0,
-                      bn_y, bn_ss, bn_mean, bn_relu, bn_c0, bn_c1, in_amax, stream, *tail);
+  ConvCall c;
+  c.in0 = dy; c.C0 = C; c.w = wpacked; c.out0 = out0; c.out1 = out1; c.Csplit = Csplit; c.stats = stats; c.mask_ref = bn_y;
+  c.bn.ss = bn_ss; c.bn.mean = bn_mean; c.bn.relu = bn_relu; c.bn.c0 = bn_c0; c.bn.c1 = bn_c1; c.in_amax0 = in_amax;
+  c.B = B; c.H = H; c.W = W; c.Cout = Cout; c.ksize = ksize;
+  return conv_run(c, CONV_X3, (hipStream_t)stream);
 }
 
 // ================================================================================================
@@ -543,19 +514,29 @@ static bool wgrad_x3_tw16(int W) {
   return !tw32;
 }
 
+// conv_wgrad_x3_k: blk x blk channels per workgroup (quadrants: 64 on 64-pixel tiles, else 32 on 128-pixel tiles)
+struct WgradX3Geometry {
+  Tiling t;
+  int q, blk;
+};
+static WgradX3Geometry wgrad_x3_geometry(int B, int H, int W, int Cin, int Cout) {
+  WgradX3Geometry g;
+  g.q = wgrad_x3_quadrants(Cin, Cout) ? 1 : 0;
+  g.blk = g.q ? 64 : 32;
+  g.t = make_tiling(B, H, W, wgrad_x3_tw16(W), g.q ? 64 : 128);
+  return g;
+}
+
 extern "C" int wtpse_wgrad_x3_ksplit(int B, int H, int W, int Cin, int Cout) {
-  const bool q = wgrad_x3_quadrants(Cin, Cout);
-  const int TW = wgrad_x3_tw16(W) ? 16 : 32, TH = (q ? 64 : 128) / TW;
-  const int ntiles = B * ceil_div(W, TW) * ceil_div(H, TH);
-  const int blk = q ? 64 : 32;
-  const int nx = (Cout / blk) * (Cin / blk);
+  const WgradX3Geometry g = wgrad_x3_geometry(B, H, W, Cin, Cout);
+  const int nx = (Cout / g.blk) * (Cin / g.blk);
   int target = 512;    // two workgroups per CU
   // tuning override, read once per process and range-checked (the slab buffer is sized from this query)
   static const int wgs_override = [] { const char* e = getenv("WTPSE_X3_WGS"); const int v = e ? atoi(e) : 0; return (v >= 1 && v <= 65536) ? v : 0; }();
   if (wgs_override) target = wgs_override;
   int ks = target / nx;
   if (ks < 1) ks = 1;
-  if (ks > ntiles) ks = ntiles;
+  if (ks > g.t.tiles) ks = g.t.tiles;
   return ks;
 }
 
@@ -567,19 +548,17 @@ extern "C" int wtpse_conv_wgrad_x3(const float* dy, const float* x0, int C0, con
   WTPSE_REQUIRE((C1 == 0) == (x1 == nullptr));
   const int Cin = C0 + C1;
   WTPSE_REQUIRE(wtpse_wgrad_x3_supported(Cin, Cout, ksize, C1 ? C0 : 8));
-  const bool q = wgrad_x3_quadrants(Cin, Cout);
+  const WgradX3Geometry g = wgrad_x3_geometry(B, H, W, Cin, Cout);
+  const bool q = g.q != 0, narrow = g.t.TW == 16;
   WgradX3Args a;
   a.dy = dy; a.x0 = x0; a.x1 = x1; a.pro0 = pro0; a.pro1 = pro1; a.slab = slab;
   a.B = B; a.H = H; a.W = W; a.C0 = C0; a.C1 = C1; a.Cin = Cin; a.Cout = Cout; a.pro_relu = pro_relu;
-  const bool narrow = wgrad_x3_tw16(W);
-  const int TW = narrow ? 16 : 32, TH = (q ? 64 : 128) / TW;
-  a.tiles_x = ceil_div(W, TW);
-  a.tiles_y = ceil_div(H, TH);
-  a.ntiles = B * a.tiles_x * a.tiles_y;
+  a.tiles_x = g.t.tiles_x;
+  a.tiles_y = g.t.tiles_y;
+  a.ntiles = g.t.tiles;
   WTPSE_REQUIRE(ksplit <= a.ntiles);
-  const int blk = q ? 64 : 32;
-  a.nci = Cin / blk;
-  dim3 grid((unsigned)((Cout / blk) * a.nci), (unsigned)ksplit);
+  a.nci = Cin / g.blk;
+  dim3 grid((unsigned)((Cout / g.blk) * a.nci), (unsigned)ksplit);
   hipStream_t st = (hipStream_t)stream;
   if (q) {
     if (narrow) hipLaunchKernelGGL((conv_wgrad_x3_k<3, 4, true>), grid, dim3(256), 0, st, a);

@@ -993,10 +993,8 @@ __global__ __launch_bounds__(256, 2) void conv_x3r_k(ConvX3Args a) {
 // ------------------------------------------------------------------------------------------------
 // Launch side of one TERMS value (instantiated in conv_x3_t<TERMS>.hip).
 struct X3Launch {
+  X3Tiling g;       // x3_tiling (conv_x3.hip)
   int ksize;        // 1 | 3
-  int mt2;          // 64-channel blocks (x3_mt2, conv_x3.hip)
-  int half;         // 64-channel blocks on 128-pixel tiles (x3_half)
-  int small;        // 32-channel blocks on 128-pixel tiles (x3_small_tiles)
   int epi;          // 0 plain, 1 ReLU mask, 2 BatchNorm-backward statistics
   int x3r;          // wtpse_x3r_enable(): 0 conv_x3_k everywhere, 1 conv_x3r_k for the 64-channel blocks of 3x3 layers, 2 for every 3x3 layer
   int xcd;          // XCD-aware workgroup order
@@ -1005,12 +1003,10 @@ struct X3Launch {
 template <int KS, int MT, int EPI, int TERMS>
 static int launch_x3(const ConvX3Args& a, const X3Launch& L, hipStream_t st) {
   ConvX3Args args = a;
-  const bool narrow = a.W <= 16;
-  const bool half = L.half != 0, small = MT == 1 && L.small != 0;
-  const int TW = narrow ? 16 : 32, TH = ((small || half) ? 128 : 256) / TW;
-  args.tiles_x = ceil_div(a.W, TW);
-  args.tiles_y = ceil_div(a.H, TH);
-  dim3 grid((unsigned)(a.B * args.tiles_x * args.tiles_y), (unsigned)ceil_div(a.CoutP, 32 * MT));
+  const bool narrow = L.g.t.TW == 16, half = L.g.half != 0, small = L.g.small != 0;
+  args.tiles_x = L.g.t.tiles_x;
+  args.tiles_y = L.g.t.tiles_y;
+  dim3 grid((unsigned)L.g.t.tiles, (unsigned)ceil_div(a.CoutP, 32 * MT));
   args.xcd_tiles = (L.xcd && grid.x % 8 == 0 && (long long)grid.x * grid.y >= 64) ? (int)grid.x / 8 : 0;
   const bool in_launch = tail_in_launch((long long)grid.x * grid.y);     // else: the stand-alone finalize kernel behind the launch
   if (!in_launch) args.tail.tickets = args.ftail.tickets = nullptr;
@@ -1054,16 +1050,14 @@ static int launch_x3(const ConvX3Args& a, const X3Launch& L, hipStream_t st) {
     hipLaunchKernelGGL((conv_x3_k<KS, MT, 4, EPI, 2, TERMS>), grid, dim3(256), 0, st, args);
   else
     hipLaunchKernelGGL((conv_x3_k<KS, MT, 5, EPI, 2, TERMS>), grid, dim3(256), 0, st, args);
-  int rc = wtpse_status();
-  if (rc == 0 && !in_launch)
-    rc = tail_after_launch(a.tail, a.ftail, a.stats, (int)grid.x, a.Cout, a.bn_c0, a.bn_c1, a.bn_mean, (long long)a.B * a.H * a.W, st);
-  return rc;
+  const int rc = wtpse_status();
+  return rc == 0 && !in_launch ? tail_after_launch(a, (int)grid.x, st) : rc;
 }
 
 template <int TERMS>
 static int x3_dispatch(const ConvX3Args& a, const X3Launch& L, hipStream_t st) {
 #define X3E(KS, M) (L.epi == 2 ? launch_x3<KS, M, 2, TERMS>(a, L, st) : L.epi == 1 ? launch_x3<KS, M, 1, TERMS>(a, L, st) : launch_x3<KS, M, 0, TERMS>(a, L, st))
-  if (L.ksize == 3) return (L.mt2 || L.half) ? X3E(3, 2) : X3E(3, 1);
-  return L.mt2 ? X3E(1, 2) : X3E(1, 1);
+  if (L.ksize == 3) return L.g.mt == 2 ? X3E(3, 2) : X3E(3, 1);
+  return L.g.mt == 2 ? X3E(1, 2) : X3E(1, 1);
 #undef X3E
 }

@@ -358,15 +358,11 @@ def dgrad_bnb(dy, wpacked_ptr, layout, cout, ksize, bn_y, bn_ss, bn_mean, bn_rel
         coef = torch.empty((c1 - c0, 3), dtype=torch.float32, device=dy.device)
         partial2 = torch.empty(L.query("wtpse_bnb_tail_partial2", nblk, cout), dtype=torch.float64, device=dy.device)
         tickets, tview = _tickets(L.query("wtpse_bnb_tail_tickets", nblk, cout), dy.device)
-        if len(tail) == 5:
-            _ticket_call(tview, "wtpse_dgrad_bnb_coef_frozen", ptr(dy), C, wpacked_ptr, layout, ptr(out0), ptr(out1), csplit, ptr(bn_y),
-                         ptr(bn_ss), ptr(bn_mean), int(bool(bn_relu)), c0, c1, ptr(stats), ptr(gamma), ptr(invstd), ptr(coef),
-                         ptr(dgamma), ptr(dbeta), ptr(tail[4]), 0, ptr(partial2), tickets, B, H, W, cout, ksize, ptr(in_amax),
-                         stream_ptr())
-            return out0, out1, stats, coef
-        _ticket_call(tview, "wtpse_dgrad_bnb_coef", ptr(dy), C, wpacked_ptr, layout, ptr(out0), ptr(out1), csplit, ptr(bn_y), ptr(bn_ss),
-               ptr(bn_mean), int(bool(bn_relu)), c0, c1, ptr(stats), ptr(gamma), ptr(invstd), ptr(coef), ptr(dgamma), ptr(dbeta), 0,
-               ptr(partial2), tickets, B, H, W, cout, ksize, ptr(in_amax), stream_ptr())
+        frozen = len(tail) == 5
+        args = [ptr(dy), C, wpacked_ptr, layout, ptr(out0), ptr(out1), csplit, ptr(bn_y), ptr(bn_ss), ptr(bn_mean), int(bool(bn_relu)),
+                c0, c1, ptr(stats), ptr(gamma), ptr(invstd), ptr(coef), ptr(dgamma), ptr(dbeta)] + ([ptr(tail[4])] if frozen else [])
+        _ticket_call(tview, "wtpse_dgrad_bnb_coef_frozen" if frozen else "wtpse_dgrad_bnb_coef", *args, 0, ptr(partial2), tickets,
+                     B, H, W, cout, ksize, ptr(in_amax), stream_ptr())
         return out0, out1, stats, coef
     if layout == 2:
         L.call("wtpse_conv16_x3", ptr(dy), C, wpacked_ptr, 0, 0, 0, ptr(out0), ptr(stats), 0, ptr(bn_y), ptr(bn_ss), ptr(bn_mean),
