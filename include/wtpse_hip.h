@@ -466,6 +466,43 @@ int wtpse_resample_u8(const unsigned char* in, unsigned char* out, const int* bo
 int wtpse_input_finish(const unsigned char* img, const unsigned char* od, const int* xidx, const int* yidx, float* image,
                        float* od_out, float* oc_out, int N, int S, void* stream);
 
+/* ---- training augmentations on the cropped uint8 sample (csrc/augment.hip; custom_transforms.py:22-132,204-217,310-327) ----
+ * The optional stage between the crop and wtpse_input_finish: RandomRotate, RandomFlip, elastic_transform,
+ * add_salt_pepper_noise, adjust_light, eraser, in that order, bit for bit (the host restatement is
+ * input_pipeline.augment_host).  All fp64 arithmetic below is single IEEE adds and multiplies in a fixed order, never fused. */
+/* out[i] = uniform double in [0, 1) number `pos + i` of the Philox4x32-10 stream `seed` (the generator of wtpse_randn): counter
+ * (pos + i) >> 1, key = seed; an even number takes the block's words (0, 1), an odd one (2, 3); value = ((a >> 5) * 2^26 +
+ * (b >> 6)) * 2^-53.  A number depends only on (seed, pos + i): a call continued at pos + n extends the same stream. */
+int wtpse_uniform_f64(double* out, long long n, unsigned long long seed, unsigned long long pos, void* stream);
+/* One pass of scipy.ndimage.gaussian_filter(mode="constant", cval=0) over `planes` fields of S x S doubles, along axis 0 (rows;
+ * axis = 0) or axis 1 (axis = 1).  w [radius + 1]: the kernel's centre and one half (it is symmetric), from the host.  Per
+ * output, in correlate1d's order: acc = x[0] * w[0]; for j = radius .. 1: acc += (x[-j] + x[+j]) * w[j]; outside the field x = 0.
+ * dst plane p = post * acc.  Source plane of p: src_index NULL: p; else field p % 2 of sample src_index[p / 2] in a [.][2][S][S]
+ * array (only the samples whose elastic coin fired are launched).  pre != 0: x = src * 2 - 1 (the uniform field of
+ * custom_transforms.py:111).  The strip, its halo and w are staged in LDS ((65 + 2 * radius) * 16 + radius + 1 doubles, at most
+ * 64 KiB): radius <= 216.  src != dst. */
+int wtpse_aug_blur(const double* src, double* dst, const double* w, const int* src_index, int radius, int planes, int S, int axis,
+                   int pre, double post, void* stream);
+/* RandomRotate + RandomFlip + the materialisation of the cropped disc mask, one index gather.  img [N][S][S][3] uint8 (scaled and
+ * cropped), od [N][S][S] uint8 read through xidx / yidx [N][S] as in wtpse_input_finish; code [N]: bits 0-1 = k (rotation by
+ * k * 90 degrees counter-clockwise, Image.rotate on a square picture), bit 2 = FLIP_LEFT_RIGHT, bit 3 = FLIP_TOP_BOTTOM (applied
+ * after the rotation, left-right first).  -> img_out [N][S][S][3], mask_out [N][S][S]. */
+int wtpse_aug_geometry(const unsigned char* img, const unsigned char* od, const int* xidx, const int* yidx, const int* code,
+                       unsigned char* img_out, unsigned char* mask_out, int N, int S, void* stream);
+/* elastic_transform's map_coordinates(order=1): sample n with slot[n] < 0 is copied; otherwise pixel (r, c) reads at
+ * (r + disp[slot][0][r][c], c + disp[slot][1][r][c]), disp [.][2][S][S] fp64.  Image: a coordinate outside [0, S-1] on either axis
+ * gives 0 (mode="constant"); mask: coordinates are clamped to [0, S-1] (mode="nearest").  Value = (1-tx) * ((1-ty) * g00 + ty * g01)
+ * + tx * ((1-ty) * g10 + ty * g11) with t = coordinate - floor(coordinate), stored as floor(value + 0.5) (scipy's uint8 output). */
+int wtpse_aug_warp(const unsigned char* img, const unsigned char* mask, const double* disp, const int* slot, unsigned char* img_out,
+                   unsigned char* mask_out, int N, int S, void* stream);
+/* add_salt_pepper_noise, adjust_light and eraser on img [N][S][S][3] uint8, in place.  pts: pixel offsets (row * S + column) of all
+ * samples' noise points, sample n owns pts[pt_off[n] .. pt_off[n+1]) and sets all three channels of each to pt_val[n] (salt: 1,
+ * as the reference writes it; pepper: 0); lut [N][256]: the gamma table (identity: none); rect [N][5] = (top, left, h, w, fill),
+ * h = 0: none.  A pixel ends as fill inside the rectangle, lut[pt_val] on a noise point, lut[pixel] elsewhere.  pts may be NULL
+ * when pt_off[N] = 0; max_pts >= the largest point count of a sample. */
+int wtpse_aug_photometric(unsigned char* img, const unsigned char* lut, const int* rect, const int* pts, const int* pt_off,
+                          const int* pt_val, int max_pts, int N, int S, void* stream);
+
 /* ---- validation back half (csrc/postprocess.hip) --------------------------------------------------- */
 /* utils.postprocessing (utils.py:267-329) bit for bit: logit [B][h][w] fp32 -> out [B][h][w] uint8 = the largest 8-connected
  * component of sigmoid(logit) > threshold (ties: the first in raster order), holes (background not 4-connected to the border)

@@ -41,6 +41,15 @@ __device__ __forceinline__ float wave_xor_sum(float v, int mask_hi) {
 
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 
+// One round of Philox4x32 (randn_k in pointwise.hip, uniform_f64_k in augment.hip); the callers bump the key between rounds.
+__device__ __forceinline__ void philox_round(uint32_t& c0, uint32_t& c1, uint32_t& c2, uint32_t& c3, uint32_t k0, uint32_t k1) {
+  const uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u;
+  uint32_t hi0 = __umulhi(M0, c0), lo0 = M0 * c0;
+  uint32_t hi1 = __umulhi(M1, c2), lo1 = M1 * c2;
+  uint32_t n0 = hi1 ^ c1 ^ k0, n1 = lo1, n2 = hi0 ^ c3 ^ k1, n3 = lo0;
+  c0 = n0; c1 = n1; c2 = n2; c3 = n3;
+}
+
 // The logistic function as the reference's od_pred / post-processing thresholds see it (roi_k, postprocess.hip).
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
 

@@ -710,13 +710,7 @@ __global__ __launch_bounds__(64) void loss_log_k(const float* s0, const float* s
 }
 
 // ------------------------------------------------------------------------------------------------ Philox4x32-10 -> N(0,1)
-__device__ __forceinline__ void philox_round(uint32_t& c0, uint32_t& c1, uint32_t& c2, uint32_t& c3, uint32_t k0, uint32_t k1) {
-  const uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u;
-  uint32_t hi0 = __umulhi(M0, c0), lo0 = M0 * c0;
-  uint32_t hi1 = __umulhi(M1, c2), lo1 = M1 * c2;
-  uint32_t n0 = hi1 ^ c1 ^ k0, n1 = lo1, n2 = hi0 ^ c3 ^ k1, n3 = lo0;
-  c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-}
+// (philox_round: common.h)
 // element i of the stream (seed, offset) depends only on (seed, offset + i/4): any sharding of the rows
 // over ranks reproduces the single-device stream when each rank passes its global element offset
 // offset_dev (optional): device counter added to `offset` (the stream position lives in device memory so that a

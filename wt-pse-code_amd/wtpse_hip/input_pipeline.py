@@ -10,6 +10,11 @@ What stays on the host: PNG decoding and the random draws.  The reference draws 
 (`seed = random.random()`, two `random.uniform(1, 1.5)`, two `random.randint` for the crop); `draw()` makes the same draws
 in the same order from any `random.Random`-like generator, so a seeded run crops exactly like the reference.
 
+Optional augmentation stage (`Augment`, `draw_augment`, `augment_host`; csrc/augment.hip): the reference's RandomRotate,
+RandomFlip, elastic_transform, add_salt_pepper_noise, adjust_light and eraser (custom_transforms.py:310-327,204-217,87-132,22-43,
+45-55,58-85), in that order, between the crop and the normalisation.  Again the draws are made on the host, in the reference's
+order, and the pixels are produced on the GPU, bit for bit; `augment_host` is the numpy specification of the device stage.
+
 The coefficient tables are Pillow's (src/libImaging/Resample.c precompute_coeffs + normalize_coeffs_8bpc; Geometry.c
 ImagingScaleAffine for NEAREST), computed here with the same double-precision operations in the same order.
 """
@@ -83,6 +88,162 @@ def draw(rng, size=256):
     return nw, nh, rng.randint(0, nw - size), rng.randint(0, nh - size)
 
 
+class Augment:
+    """Which of the six training augmentations run, in the reference's order: rotate (RandomRotate), flip (RandomFlip), elastic
+    (elastic_transform), salt_pepper (add_salt_pepper_noise), light (adjust_light), erase (eraser).  A disabled one draws nothing.
+
+    rotate_degree: the reference draws its angle ONCE, in RandomRotate's constructor (`randint(1, 4) * 90`, custom_transforms.py:
+    312), so a whole run rotates by one angle or not at all; 90 / 180 / 270 / 360 reproduce that.  The default "random" draws
+    `randint(1, 4) * 90` per sample, right after a coin that fired — a deliberate deviation from the reference (no reference output
+    exists for it; it is pinned against `augment_host` only)."""
+
+    def __init__(self, rotate=True, rotate_degree="random", flip=True, elastic=True, salt_pepper=True, light=True, erase=True):
+        if rotate_degree not in ("random", 90, 180, 270, 360):
+            raise ValueError("rotate_degree must be 'random', 90, 180, 270 or 360, got %r" % (rotate_degree,))
+        self.rotate, self.rotate_degree, self.flip, self.elastic = bool(rotate), rotate_degree, bool(flip), bool(elastic)
+        self.salt_pepper, self.light, self.erase = bool(salt_pepper), bool(light), bool(erase)
+
+
+def gamma_table(gamma):
+    """adjust_light's table (custom_transforms.py:51-52), element by element in double precision as the reference builds it."""
+    inv = 1.0 / gamma
+    return np.array([((i / 255.0) ** inv) * 255 for i in np.arange(0, 256)]).astype(np.uint8)
+
+
+def draw_augment(py_rng, np_rng, size, aug):
+    """The random draws of the enabled augmentations for ONE sample, in the reference's order, from `py_rng` (where the reference
+    uses the `random` module) and `np_rng` (where it uses `np.random`): a `random.Random(s)` and a `RandomState(s)` reproduce a run
+    that seeded the two global generators with s.  -> plain data:
+        k        quarter turns counter-clockwise, 0..3 (0: no rotation, or 360 degrees)
+        flip_lr, flip_tb, elastic   flags
+        sp       None or (value, rows, cols): the noise points; value 1 = salt — the reference writes 1, not 255, into the uint8
+                 image (custom_transforms.py:37), kept — or 0 = pepper.  The third coordinate array (channels) the reference draws
+                 and never uses is drawn and dropped.
+        lut      None or adjust_light's 256-entry uint8 table
+        rect     None or (top, left, h, w, fill): the eraser's rectangle after its rejection loop, fill = uniform(0, 255) truncated"""
+    S = int(size)
+    d = {"k": 0, "flip_lr": False, "flip_tb": False, "elastic": False, "sp": None, "lut": None, "rect": None}
+    if aug.rotate and py_rng.random() > 0.5:
+        degree = py_rng.randint(1, 4) * 90 if aug.rotate_degree == "random" else aug.rotate_degree
+        d["k"] = (degree // 90) % 4
+    if aug.flip:
+        d["flip_lr"] = py_rng.random() < 0.5
+        d["flip_tb"] = py_rng.random() < 0.5
+    if aug.elastic:
+        d["elastic"] = py_rng.random() > 0.5
+    if aug.salt_pepper:
+        n_px = S * S * 3
+        num_salt = np.ceil(0.004 * n_px * 0.2)
+        num_pepper = np.ceil(0.004 * n_px * (1.0 - 0.2))
+        seed = py_rng.random()
+        if seed > 0.5:
+            value, num = (1, num_salt) if seed > 0.75 else (0, num_pepper)
+            coords = [np_rng.randint(0, i - 1, int(num)) for i in (S, S, 3)]
+            d["sp"] = (value, coords[0].astype(np.int32), coords[1].astype(np.int32))
+    if aug.light and py_rng.random() > 0.5:
+        d["lut"] = gamma_table(py_rng.random() * 3 + 0.5)
+    if aug.erase and not py_rng.random() > 0.5:
+        while True:
+            s = np_rng.uniform(0.02, 0.06) * S * S
+            r = np_rng.uniform(0.3, 0.6)
+            w, h = int(np.sqrt(s / r)), int(np.sqrt(s * r))
+            left, top = np_rng.randint(0, S), np_rng.randint(0, S)
+            if left + w <= S and top + h <= S:
+                break
+        d["rect"] = (int(top), int(left), h, w, int(np_rng.uniform(0, 255)))
+    return d
+
+
+def gaussian_weights(sigma):
+    """scipy.ndimage.gaussian_filter's 1-D kernel for `sigma` (truncate = 4), with scipy's operations: -> (w [radius + 1] = the
+    centre and one half of the symmetric kernel, radius)."""
+    sigma = float(sigma)
+    radius = int(4.0 * sigma + 0.5)
+    x = np.arange(-radius, radius + 1)
+    phi = np.exp(-0.5 / (sigma * sigma) * x ** 2)
+    phi = phi / phi.sum()
+    return np.ascontiguousarray(phi[radius:]), radius
+
+
+def _blur_axis(x, w, axis):
+    """One pass of gaussian_filter(mode="constant", cval=0) along `axis` in correlate1d's summation order for a symmetric kernel:
+    acc = x[0] * w[0]; for j = radius .. 1: acc += (x[-j] + x[+j]) * w[j]."""
+    r, n = len(w) - 1, x.shape[axis]
+    pad = [(0, 0)] * x.ndim
+    pad[axis] = (r, r)
+    p = np.moveaxis(np.pad(x, pad), axis, -1)
+    acc = p[..., r:r + n] * w[0]
+    for j in range(r, 0, -1):
+        acc = acc + (p[..., r - j:r - j + n] + p[..., r + j:r + j + n]) * w[j]
+    return np.moveaxis(acc, -1, axis)
+
+
+def elastic_displacement(noise, size):
+    """noise [2,S,S] uniform doubles in [0,1) -> the two displacement fields of elastic_transform (custom_transforms.py:99-112):
+    gaussian_filter(noise * 2 - 1, 0.08 * S, mode="constant", cval=0) * (2 * S)."""
+    S = int(size)
+    w, _ = gaussian_weights(S * 0.08)
+    f = np.asarray(noise, np.float64) * 2 - 1
+    return _blur_axis(_blur_axis(f, w, 1), w, 2) * float(S * 2)
+
+
+def _bilinear(src, cx, cy):
+    """map_coordinates(order=1) at in-range coordinates, rounded into uint8 as scipy's uint8 output is: floor(v + 0.5)."""
+    S = src.shape[0]
+    fx, fy = np.floor(cx), np.floor(cy)
+    tx, ty = cx - fx, cy - fy
+    x0, y0 = fx.astype(np.int64), fy.astype(np.int64)
+    x1, y1 = np.minimum(x0 + 1, S - 1), np.minimum(y0 + 1, S - 1)          # reached with weight 0 only
+    g = src.astype(np.float64)
+    if g.ndim == 3:
+        tx, ty = tx[..., None], ty[..., None]
+    v = (1.0 - tx) * ((1.0 - ty) * g[x0, y0] + ty * g[x0, y1]) + tx * ((1.0 - ty) * g[x1, y0] + ty * g[x1, y1])
+    return np.floor(v + 0.5).astype(np.uint8)
+
+
+def augment_host(image_u8, mask_u8, aug_draw, noise=None):
+    """The specification of the device stage in numpy: image [S,S,3] uint8 and disc mask [S,S] uint8 (scaled and cropped), one
+    `draw_augment` result, noise [2,S,S] uniform doubles in [0,1) (needed when aug_draw["elastic"]) -> (image, mask) uint8.
+    Equal, bit for bit, to the reference's classes applied in the order rotate, flip, elastic, salt and pepper, light, erase with
+    'label' = the disc mask (tests/golden/augment.npz), and to what DeviceInputPipeline computes on the GPU."""
+    d = aug_draw
+    img, mask = np.asarray(image_u8), np.asarray(mask_u8)
+    S = img.shape[0]
+    assert img.shape == (S, S, 3) and mask.shape == (S, S) and img.dtype == np.uint8 and mask.dtype == np.uint8
+    if d["k"]:
+        img, mask = np.rot90(img, d["k"]), np.rot90(mask, d["k"])
+    if d["flip_lr"]:
+        img, mask = img[:, ::-1], mask[:, ::-1]
+    if d["flip_tb"]:
+        img, mask = img[::-1], mask[::-1]
+    if d["elastic"]:
+        disp = elastic_displacement(noise, S)
+        rows, cols = np.meshgrid(np.arange(S), np.arange(S), indexing="ij")
+        cx, cy = rows + disp[0], cols + disp[1]
+        last = float(S - 1)
+        inside = (cx >= 0.0) & (cx <= last) & (cy >= 0.0) & (cy <= last)
+        cxc, cyc = np.clip(cx, 0.0, last), np.clip(cy, 0.0, last)
+        img = np.where(inside[..., None], _bilinear(img, cxc, cyc), 0).astype(np.uint8)      # mode="constant": 0 outside
+        mask = _bilinear(mask, cxc, cyc)                                                     # mode="nearest": clamped
+    img = np.array(img)                                                                      # a writable copy
+    if d["sp"] is not None:
+        value, rows, cols = d["sp"]
+        img[rows, cols, :] = value
+    if d["lut"] is not None:
+        img = d["lut"][img]
+    if d["rect"] is not None:
+        top, left, h, w, fill = d["rect"]
+        img[top:top + h, left:left + w, :] = fill
+    return img, np.ascontiguousarray(mask)
+
+
+def device_uniform(n, seed, pos, device="cuda"):
+    """n uniform doubles in [0,1): numbers pos .. pos + n - 1 of the Philox4x32-10 stream `seed` (wtpse_uniform_f64)."""
+    out = torch.empty(int(n), dtype=torch.float64, device=device)
+    ops.lib().call("wtpse_uniform_f64", out.data_ptr(), int(n), int(seed), int(pos), ops.stream_ptr())
+    return out
+
+
 def _dev_u8(a, device):
     t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))
     if t.dtype != torch.uint8:
@@ -96,9 +257,18 @@ def _dev_i32(a, device):
 
 class DeviceInputPipeline:
     """batch = pipeline(images, disc_masks, draws): images [H,W,3] uint8 and disc masks [H,W] uint8 per sample (numpy or
-    torch, host or device; sizes may differ between samples), draws = [draw(rng, size) per sample]."""
+    torch, host or device; sizes may differ between samples), draws = [draw(rng, size) per sample].
 
-    def __init__(self, size=256, device="cuda"):
+    aug_draws = [draw_augment(py_rng, np_rng, size, aug) per sample] switches the augmentation stage on (None, the default: the
+    stage does not exist).  The elastic transform's uniform fields come from the device generator — stream `noise_seed`, running
+    position `noise_pos` (2 * S * S numbers per sample whose elastic coin fired; run state, see trainer.FundusBatches) — unless
+    `noise` [N,2,S,S] fp64 in [0,1) is given (rows of samples without an elastic transform are not read).  The reference draws
+    these fields from an unseeded RandomState(None) (custom_transforms.py:108), which nothing can reproduce: the fields are this
+    pipeline's own, the arithmetic on them is scipy's."""
+
+    def __init__(self, size=256, device="cuda", noise_seed=0):
+        self.noise_seed, self.noise_pos = int(noise_seed), 0
+        self._gauss = None
         self.size = int(size)
         self.device = torch.device(device)
         if self.device.type != "cuda":
@@ -119,10 +289,63 @@ class DeviceInputPipeline:
                        0 if tab is None else tab.data_ptr(), ksize, N, H, W, C, L, int(vertical), ops.stream_ptr())
         return out
 
-    def __call__(self, images, disc_masks, draws):
+    def _augment(self, img, od1, xidx, yidx, aug_draws, noise):
+        """img [N,S,S,3] uint8 (cropped), od1 [N,S,S,1] uint8 behind the index tables -> (img, mask [N,S,S]) uint8 augmented."""
+        S, dev, call, st = self.size, self.device, ops.lib().call, ops.stream_ptr()
+        N = img.shape[0]
+        code = _dev_i32([d["k"] | (4 if d["flip_lr"] else 0) | (8 if d["flip_tb"] else 0) for d in aug_draws], dev)
+        out = torch.empty_like(img)
+        mask = torch.empty((N, S, S), dtype=torch.uint8, device=dev)
+        call("wtpse_aug_geometry", img.data_ptr(), od1.data_ptr(), xidx.data_ptr(), yidx.data_ptr(), code.data_ptr(), out.data_ptr(),
+             mask.data_ptr(), N, S, st)
+        img = out
+        active = [i for i, d in enumerate(aug_draws) if d["elastic"]]
+        if active:
+            na = len(active)
+            if self._gauss is None:
+                w, radius = gaussian_weights(S * 0.08)
+                self._gauss = (torch.from_numpy(w).to(dev), radius)
+            w, radius = self._gauss
+            if noise is None:
+                u, index = device_uniform(na * 2 * S * S, self.noise_seed, self.noise_pos, dev), None
+                self.noise_pos += na * 2 * S * S
+            else:
+                u = noise if isinstance(noise, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(noise, dtype=np.float64))
+                if tuple(u.shape) != (N, 2, S, S) or u.dtype != torch.float64:
+                    raise ValueError("noise must be [%d,2,%d,%d] float64, got %s %s" % (N, S, S, tuple(u.shape), u.dtype))
+                u, index = u.to(dev).contiguous(), _dev_i32(active, dev)
+            tmp = torch.empty((na, 2, S, S), dtype=torch.float64, device=dev)
+            disp = torch.empty_like(tmp)
+            call("wtpse_aug_blur", u.data_ptr(), tmp.data_ptr(), w.data_ptr(), 0 if index is None else index.data_ptr(), radius,
+                 na * 2, S, 0, 1, 1.0, st)
+            call("wtpse_aug_blur", tmp.data_ptr(), disp.data_ptr(), w.data_ptr(), 0, radius, na * 2, S, 1, 0, float(2 * S), st)
+            slot = np.full(N, -1, np.int32)
+            slot[active] = np.arange(na)
+            out, mask2 = torch.empty_like(img), torch.empty_like(mask)
+            slot = _dev_i32(slot, dev)
+            call("wtpse_aug_warp", img.data_ptr(), mask.data_ptr(), disp.data_ptr(), slot.data_ptr(), out.data_ptr(), mask2.data_ptr(), N, S, st)
+            img, mask = out, mask2
+        if any(d["sp"] is not None or d["lut"] is not None or d["rect"] is not None for d in aug_draws):
+            ident = np.arange(256, dtype=np.uint8)
+            lut = np.stack([ident if d["lut"] is None else np.asarray(d["lut"], np.uint8) for d in aug_draws])
+            rect = np.array([(0, 0, 0, 0, 0) if d["rect"] is None else d["rect"] for d in aug_draws], np.int32)
+            pts = [np.zeros(0, np.int32) if d["sp"] is None else d["sp"][1].astype(np.int32) * S + d["sp"][2].astype(np.int32)
+                   for d in aug_draws]
+            off = np.concatenate([[0], np.cumsum([len(p) for p in pts])]).astype(np.int32)
+            val = [0 if d["sp"] is None else int(d["sp"][0]) for d in aug_draws]
+            max_pts = max(len(p) for p in pts)
+            # every table stays referenced until the launch is queued: a temporary's block would be handed to the next allocation
+            # and overwritten by its copy before the kernel reads it
+            dpts = _dev_i32(np.concatenate(pts), dev) if max_pts else None
+            lut, rect, off, val = torch.from_numpy(lut).to(dev), _dev_i32(rect, dev), _dev_i32(off, dev), _dev_i32(val, dev)
+            call("wtpse_aug_photometric", img.data_ptr(), lut.data_ptr(), rect.data_ptr(), 0 if dpts is None else dpts.data_ptr(),
+                 off.data_ptr(), val.data_ptr(), max_pts, N, S, st)
+        return img, mask
+
+    def __call__(self, images, disc_masks, draws, aug_draws=None, noise=None):
         S, dev = self.size, self.device
         N = len(images)
-        assert len(disc_masks) == N and len(draws) == N
+        assert len(disc_masks) == N and len(draws) == N and (aug_draws is None or len(aug_draws) == N)
         # ---- Resize(S): bicubic, horizontal pass then vertical pass, batched over samples of one input size
         img1 = torch.empty((N, S, S, 3), dtype=torch.uint8, device=dev)
         od1 = torch.empty((N, S, S, 1), dtype=torch.uint8, device=dev)
@@ -159,6 +382,10 @@ class DeviceInputPipeline:
         od = torch.empty((N, 1, S, S), dtype=torch.float32, device=dev)
         oc = torch.empty((N, 1, S, S), dtype=torch.float32, device=dev)
         xidx, yidx = _dev_i32(np.stack(xi), dev), _dev_i32(np.stack(yi), dev)
+        if aug_draws is not None:
+            # the augmentation stage leaves the mask cropped: input_finish reads it through identity tables
+            img2, od1 = self._augment(img2, od1, xidx, yidx, aug_draws, noise)
+            xidx = yidx = torch.arange(S, dtype=torch.int32, device=dev).repeat(N, 1).contiguous()
         ops.lib().call("wtpse_input_finish", img2.data_ptr(), od1.data_ptr(), xidx.data_ptr(), yidx.data_ptr(), image.data_ptr(),
                        od.data_ptr(), oc.data_ptr(), N, S, ops.stream_ptr())
         return image, od, oc

@@ -72,10 +72,18 @@ class FundusBatches:
     from the `random.Random` again (custom_transforms.py:342-346), one sample after the other as the reference's loader does.
     The reference shuffles its domain list in place, so every shuffle starts from the order the previous one left: that order
     (`order`: positions into the datasets as they were given) is run state — `state()` / `load_state()`, which TrainRun's
-    checkpoints carry — and a feed built anew from the same datasets in the same order continues a run where it stopped."""
+    checkpoints carry — and a feed built anew from the same datasets in the same order continues a run where it stopped.
 
-    def __init__(self, datasets, batch_size, device, size=256):
+    augment: an `input_pipeline.Augment` switches the device-side augmentation stage on (None: off, and everything here is as it
+    was).  The reference's loader transforms a sample right after it has drawn its index, so with augmentations — whose noise points
+    and eraser draw from the numpy generator too — the draws interleave per sample: index, crop, augmentations.  The elastic
+    transform's uniform fields come from the device Philox stream `noise_seed` (TrainRun sets it to the run seed: `set_seed`) at a
+    running position, which is feed state as well: `state()` carries it as "noise_pos", and a state saved before the field existed
+    loads with position 0."""
+
+    def __init__(self, datasets, batch_size, device, size=256, augment=None, pipe=None):
         from .input_pipeline import DeviceInputPipeline
+        self.augment = augment
         self.datasets = list(datasets)
         self.order = list(range(len(self.datasets)))
         # Trainer.py:1011: per_domain_batch = batch_size // source_domain_num — a batch holds domains * per_domain samples
@@ -85,7 +93,7 @@ class FundusBatches:
         if self.per_domain < 1:
             raise ValueError("batch_size %d is smaller than the number of source domains (%d)" % (batch_size, len(self.datasets)))
         self.size = int(size)
-        self.pipe = DeviceInputPipeline(size, device)
+        self.pipe = DeviceInputPipeline(size, device) if pipe is None else pipe     # pipe: a ready pipeline of the same size
 
     def __len__(self):
         """Trainer.py:1013-1014: iterations per epoch = total samples // batch size."""
@@ -93,19 +101,36 @@ class FundusBatches:
 
     def __call__(self, py_rng, np_rng):
         from .fundus_data import multi_batch
-        from .input_pipeline import draw
+        from .input_pipeline import draw, draw_augment
         py_rng.shuffle(self.order)
-        images, masks = multi_batch([self.datasets[i] for i in self.order], self.per_domain, np_rng)
-        return self.pipe(images, masks, [draw(py_rng, self.size) for _ in images])
+        if self.augment is None:
+            images, masks = multi_batch([self.datasets[i] for i in self.order], self.per_domain, np_rng)
+            return self.pipe(images, masks, [draw(py_rng, self.size) for _ in images])
+        images, masks, draws, aug_draws = [], [], [], []
+        for i in self.order:
+            for _ in range(self.per_domain):
+                img, mask = multi_batch([self.datasets[i]], 1, np_rng)
+                images += img
+                masks += mask
+                draws.append(draw(py_rng, self.size))
+                aug_draws.append(draw_augment(py_rng, np_rng, self.size, self.augment))
+        return self.pipe(images, masks, draws, aug_draws)
+
+    def set_seed(self, seed):
+        """The seed of the elastic transform's noise stream (TrainRun calls this with the run seed)."""
+        self.pipe.noise_seed = int(seed)
 
     def state(self):
-        return {"order": list(self.order)}
+        if self.augment is None:
+            return {"order": list(self.order)}
+        return {"order": list(self.order), "noise_pos": int(self.pipe.noise_pos)}
 
     def load_state(self, state):
         order = [int(i) for i in state["order"]]
         if sorted(order) != list(range(len(self.datasets))):
             raise ValueError("the saved domain order %s is not a permutation of this feed's %d datasets" % (order, len(self.datasets)))
         self.order = order
+        self.pipe.noise_pos = int(state.get("noise_pos", 0))
 
 
 def _py_state_to_lists(state):
@@ -132,7 +157,9 @@ class TrainRun:
     next_batch(py_rng, np_rng) -> (image [B,3,H,W], target_od [B,1,H,W], target_oc [B,1,H,W]) device fp32; the run owns the two
     host generators (`random.Random(seed)`: crop draws and the per-iteration shuffle of the domain list; `numpy.random.
     RandomState(seed)`: sample indices) and hands them to every call.  A feed that keeps state of its own between calls exposes it
-    as `state()` -> plain data / `load_state(state)` (`FundusBatches`: the order of its domain list); checkpoints carry it, so a
+    as `state()` -> plain data / `load_state(state)` (`FundusBatches`: the order of its domain list and, with augmentations, the
+    position of its noise stream); a feed that draws device noise of its own exposes `set_seed(seed)`, which the constructor
+    calls with the run seed (`FundusBatches`: the elastic transform's stream); checkpoints carry the state, so a
     resumed run draws what the uninterrupted one would.
     lr: the four base rates (od, od_shape, oc, oc_shape) or one for all.  lr_schedule: None (the reference's default: its call of
     lr_update is commented out, Trainer.py:1040) or "reference" (`reference_lr` after every epoch, from the next epoch on).
@@ -158,6 +185,8 @@ class TrainRun:
         self.graph, self.betas = graph, tuple(float(b) for b in betas)
         self.freeze_bn = bool(freeze_bn)
         self.py_rng, self.np_rng = random.Random(self.seed), np.random.RandomState(self.seed)
+        if hasattr(next_batch, "set_seed"):            # a feed with a device noise stream of its own (FundusBatches with augment=)
+            next_batch.set_seed(self.seed)
         device = next(model_od.parameters()).device
         self.log = LossLog(device, TrainStep.log_names(hparams))
         self.train_step = TrainStep(model_od, shape_od, model_oc, shape_oc, hparams, lr=self.base_lr, betas=betas, graph=graph, log=self.log,
