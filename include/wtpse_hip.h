@@ -465,6 +465,9 @@ int wtpse_resample_u8(const unsigned char* in, unsigned char* out, const int* bo
  * image [N][3][S][S] = img / 127.5 - 1, od_out [N][1][S][S] = (mask <= 200), oc_out = (mask <= 50). */
 int wtpse_input_finish(const unsigned char* img, const unsigned char* od, const int* xidx, const int* yidx, float* image,
                        float* od_out, float* oc_out, int N, int S, void* stream);
+/* wtpse_input_finish's image alone, for a sample that has no mask (wtpse_hip/segment.py): img [N][S][S][3] uint8 ->
+ * image [N][3][S][S] = img / 127.5 - 1 in fp32, two roundings. */
+int wtpse_image_finish(const unsigned char* img, float* image, int N, int S, void* stream);
 
 /* ---- training augmentations on the cropped uint8 sample (csrc/augment.hip; custom_transforms.py:22-132,204-217,310-327) ----
  * The optional stage between the crop and wtpse_input_finish: RandomRotate, RandomFlip, elastic_transform,
@@ -535,6 +538,22 @@ int wtpse_overlay(const float* img, const unsigned char* pred_od, const unsigned
 /* The test feed's labels at their original size (fundus_dataloader.py:112-134): mask [n] uint8 grey levels ->
  * od [n] = (mask <= 200), oc [n] = (mask <= 50), fp32. */
 int wtpse_label_thresholds(const unsigned char* mask, float* od, float* oc, long long n, void* stream);
+
+/* ---- segmenting unlabelled images (csrc/measure.hip, csrc/overlay.hip; wtpse_hip/segment.py) --------------------------------- */
+/* wtpse_overlay without a ground truth: the same two pictures with nothing painted red, byte for byte what wtpse_overlay gives for
+ * all-zero gt_od / gt_oc, without its largest-component stage and its scratch.  wtpse_overlay_pred_ws: 0 (no workspace is needed) when
+ * wtpse_overlay supports the size, -1 otherwise.  img, original, overlay 4-byte aligned.  2 <= h, w <= 4096. */
+int wtpse_overlay_pred_ws(int B, int h, int w);
+int wtpse_overlay_pred(const float* img, const unsigned char* pred_od, const unsigned char* pred_oc, unsigned char* original,
+                       unsigned char* overlay, int B, int h, int w, void* stream);
+/* The dataset's grey-level label from two masks (uint8 [n], nonzero = object): out [n] = 0 where cup, else 128 where disc, else 255.
+ * The inverse of wtpse_label_thresholds: read back, oc = (cup != 0) and od = ((disc | cup) != 0). */
+int wtpse_label_map(const unsigned char* disc, const unsigned char* cup, unsigned char* out, long long n, void* stream);
+/* mask [B][h][w] uint8 -> rec [B][8] int64 = {area, top, bottom, left, right, sum_r, sum_c, 0} over the nonzero pixels: their count,
+ * the first / last row and column that hold one, and the sums of their row and column indices.  An empty mask: {0, h, -1, w, -1, 0, 0,
+ * 0}.  Integer arithmetic only (64-bit sums): exact, the same on every run, no host synchronisation.  rec 8-byte aligned.
+ * 1 <= h, w <= 4096. */
+int wtpse_mask_geometry(const unsigned char* mask, long long* rec, int B, int h, int w, void* stream);
 
 /* ---- small utilities ------------------------------------------------------------------------------------------- */
 int wtpse_relu_mask(const float* dz, const float* ref, float* dy, int accumulate, long long n, void* stream);

@@ -50,6 +50,9 @@ __device__ __forceinline__ unsigned ov_bits(unsigned od, unsigned oc, unsigned g
 }
 
 // gf [2][B][h][w]: the filled ground-truth channels.  vec: w % 4 == 0 and every pointer aligned for 16-byte / 4-byte vector access.
+// GT = 0 (wtpse_overlay_pred): there is no ground truth — gf is not read (NULL) and bits 2 / 3 stay clear, which is what an all-zero
+// ground truth packs to, so nothing is painted red and every other byte is the GT = 1 kernel's.
+template <int GT>
 __global__ __launch_bounds__(256) void overlay_k(const float* __restrict__ img, const unsigned char* __restrict__ pred_od,
                                                  const unsigned char* __restrict__ pred_oc, const unsigned char* __restrict__ gf,
                                                  unsigned char* __restrict__ original, unsigned char* __restrict__ overlay, int B, int h,
@@ -61,8 +64,8 @@ __global__ __launch_bounds__(256) void overlay_k(const float* __restrict__ img, 
   const size_t plane = (size_t)h * w;
   const unsigned char* pd = pred_od + (size_t)b * plane;
   const unsigned char* pc = pred_oc + (size_t)b * plane;
-  const unsigned char* q0 = gf + (size_t)b * plane;
-  const unsigned char* q1 = gf + ((size_t)B + b) * plane;
+  const unsigned char* q0 = GT ? gf + (size_t)b * plane : nullptr;
+  const unsigned char* q1 = GT ? gf + ((size_t)B + b) * plane : nullptr;
 
   // ---- the packed mask tile: row h holds row 0 and column w holds column 0 (the -1 wrap), everything else outside is 0
   for (int idx = threadIdx.x; idx < OV_MH * OV_MG; idx += 256) {
@@ -75,7 +78,8 @@ __global__ __launch_bounds__(256) void overlay_k(const float* __restrict__ img, 
       const size_t ro = (size_t)ys * w;
       if (vec && x >= 0 && x + 3 < w) {
         const unsigned a = *reinterpret_cast<const unsigned*>(pd + ro + x), c = *reinterpret_cast<const unsigned*>(pc + ro + x);
-        const unsigned e = *reinterpret_cast<const unsigned*>(q0 + ro + x), f = *reinterpret_cast<const unsigned*>(q1 + ro + x);
+        const unsigned e = GT ? *reinterpret_cast<const unsigned*>(q0 + ro + x) : 0u;
+        const unsigned f = GT ? *reinterpret_cast<const unsigned*>(q1 + ro + x) : 0u;
 #pragma unroll
         for (int k = 0; k < 4; ++k)
           packed |= ov_bits((a >> (8 * k)) & 255u, (c >> (8 * k)) & 255u, (e >> (8 * k)) & 255u, (f >> (8 * k)) & 255u,
@@ -86,7 +90,7 @@ __global__ __launch_bounds__(256) void overlay_k(const float* __restrict__ img, 
           const int xx = x + k;
           if (xx < 0 || xx > w) continue;
           const int xs = xx == w ? 0 : xx;
-          packed |= ov_bits(pd[ro + xs], pc[ro + xs], q0[ro + xs], q1[ro + xs], rb || xs == 0 || xs == w - 1) << (8 * k);
+          packed |= ov_bits(pd[ro + xs], pc[ro + xs], GT ? q0[ro + xs] : 0u, GT ? q1[ro + xs] : 0u, rb || xs == 0 || xs == w - 1) << (8 * k);
         }
       }
     }
@@ -278,8 +282,21 @@ extern "C" int wtpse_overlay(const float* img, const unsigned char* pred_od, con
   const int rc = wtpse_postprocess(logit, gf, ws, 0.5f, 2 * B, h, w, stream);
   if (rc) return rc;
   const int vec = (w & 3) == 0 && ov_aligned(img, 16) && ov_aligned(pred_od, 4) && ov_aligned(pred_oc, 4) && ov_aligned(gf, 4);
-  hipLaunchKernelGGL(overlay_k, dim3((unsigned)ceil_div(w, OV_TX), (unsigned)ceil_div(h, OV_TY), (unsigned)B), dim3(256), 0, st, img,
+  hipLaunchKernelGGL(overlay_k<1>, dim3((unsigned)ceil_div(w, OV_TX), (unsigned)ceil_div(h, OV_TY), (unsigned)B), dim3(256), 0, st, img,
                      pred_od, pred_oc, gf, original, overlay, B, h, w, vec);
+  return wtpse_status();
+}
+
+// No ground-truth stage, so no scratch: 0 words for a supported size, -1 otherwise (the sizes wtpse_overlay takes).
+extern "C" int wtpse_overlay_pred_ws(int B, int h, int w) { return ov_dims_ok(B, h, w) ? 0 : -1; }
+
+extern "C" int wtpse_overlay_pred(const float* img, const unsigned char* pred_od, const unsigned char* pred_oc, unsigned char* original,
+                                  unsigned char* overlay, int B, int h, int w, void* stream) {
+  WTPSE_REQUIRE(img && pred_od && pred_oc && original && overlay && wtpse_overlay_pred_ws(B, h, w) == 0);
+  WTPSE_REQUIRE(ov_aligned(img, 4) && ov_aligned(original, 4) && ov_aligned(overlay, 4));
+  const int vec = (w & 3) == 0 && ov_aligned(img, 16) && ov_aligned(pred_od, 4) && ov_aligned(pred_oc, 4);
+  hipLaunchKernelGGL(overlay_k<0>, dim3((unsigned)ceil_div(w, OV_TX), (unsigned)ceil_div(h, OV_TY), (unsigned)B), dim3(256), 0,
+                     (hipStream_t)stream, img, pred_od, pred_oc, (const unsigned char*)nullptr, original, overlay, B, h, w, vec);
   return wtpse_status();
 }
 

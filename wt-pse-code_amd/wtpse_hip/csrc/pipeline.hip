@@ -66,6 +66,20 @@ __global__ __launch_bounds__(256) void input_finish_k(const unsigned char* __res
   oc_out[(size_t)n * S * S + p] = m > 50 ? 0.f : 1.f;
 }
 
+// input_finish_k's image half alone (wtpse_hip/segment.py: an unlabelled image has no mask): img [N][S][S][3] u8 -> image [N][3][S][S].
+__global__ __launch_bounds__(256) void image_finish_k(const unsigned char* __restrict__ img, float* __restrict__ image, int S) {
+  const int n = blockIdx.y;
+  const int p = blockIdx.x * 256 + threadIdx.x;
+  if (p >= S * S) return;
+  const unsigned char* px = img + ((size_t)n * S * S + p) * 3;
+  float* dst = image + (size_t)n * 3 * S * S + p;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const float v = __fdiv_rn((float)px[c], 127.5f);        // the two roundings of input_finish_k
+    dst[(size_t)c * S * S] = v - 1.0f;
+  }
+}
+
 // See include/wtpse_hip.h for the contract.
 extern "C" int wtpse_resample_u8(const unsigned char* in, unsigned char* out, const int* bounds, const int* kk, const int* tab,
                                  int ksize, int N, int Hin, int Win, int C, int L, int vertical, void* stream) {
@@ -81,5 +95,12 @@ extern "C" int wtpse_input_finish(const unsigned char* img, const unsigned char*
   WTPSE_REQUIRE(img && od && xidx && yidx && image && od_out && oc_out && N > 0 && N < 65536 && S > 0);
   hipLaunchKernelGGL(input_finish_k, dim3((unsigned)((S * S + 255) / 256), (unsigned)N), dim3(256), 0, (hipStream_t)stream, img,
                      od, xidx, yidx, image, od_out, oc_out, S);
+  return wtpse_status();
+}
+
+extern "C" int wtpse_image_finish(const unsigned char* img, float* image, int N, int S, void* stream) {
+  WTPSE_REQUIRE(img && image && N > 0 && N < 65536 && S > 0 && S <= 16384);
+  hipLaunchKernelGGL(image_finish_k, dim3((unsigned)((S * S + 255) / 256), (unsigned)N), dim3(256), 0, (hipStream_t)stream, img,
+                     image, S);
   return wtpse_status();
 }

@@ -18,16 +18,34 @@ order, and the pixels are produced on the GPU, bit for bit; `augment_host` is th
 The coefficient tables are Pillow's (src/libImaging/Resample.c precompute_coeffs + normalize_coeffs_8bpc; Geometry.c
 ImagingScaleAffine for NEAREST), computed here with the same double-precision operations in the same order.
 """
+import math
+
 import numpy as np
 import torch
 
 from . import ops
 
 PRECISION_BITS = 22
-_FILTER_SUPPORT = {"bilinear": 1.0, "bicubic": 2.0}
+_FILTER_SUPPORT = {"bilinear": 1.0, "bicubic": 2.0, "lanczos": 3.0}
+
+
+def _sinc(x):
+    if x == 0.0:
+        return 1.0
+    x = x * math.pi
+    return math.sin(x) / x
+
+
+def _lanczos(x):
+    """Resample.c lanczos_filter: sinc(x) * sinc(x / 3) on -3 <= x < 3.  One coefficient at a time through math.sin — libm's sine,
+    the one Pillow's C calls; a vectorised sine may differ from it in the last bit, which a rounded 22-bit coefficient can show."""
+    flat = [_sinc(v) * _sinc(v / 3) if -3.0 <= v < 3.0 else 0.0 for v in x.ravel().tolist()]
+    return np.array(flat, np.float64).reshape(x.shape)
 
 
 def _filter(name, x):
+    if name == "lanczos":
+        return _lanczos(x)
     x = np.abs(x)
     if name == "bilinear":
         return np.where(x < 1.0, 1.0 - x, 0.0)

@@ -1002,21 +1002,30 @@ def seg_metrics(mask, label):
 def overlay(img, pred_od, pred_oc, gt_od, gt_oc):
     """The pictures of the reference's test program on the device (csrc/overlay.hip; test_run.overlay_host byte for byte):
     img [B,3,h,w] fp32 (normalised, at the label size), pred_od / pred_oc [B,1,h,w] uint8 (postprocess_masks), gt_od / gt_oc
-    [B,1,h,w] uint8 labels 0 / 1 -> (original, overlay), each uint8 [B,h,w,3]."""
+    [B,1,h,w] uint8 labels 0 / 1 -> (original, overlay), each uint8 [B,h,w,3].  gt_od = gt_oc = None: no ground truth
+    (wtpse_overlay_pred) — the pictures an all-zero ground truth gives, without its largest-component stage."""
     _chk(img, "img")
     if img.dim() != 4 or img.shape[1] != 3:
         raise ValueError("img must be [B,3,h,w] (got %s)" % (tuple(img.shape),))
     B, _, h, w = img.shape
-    for t, name in ((pred_od, "pred_od"), (pred_oc, "pred_oc"), (gt_od, "gt_od"), (gt_oc, "gt_oc")):
+    if (gt_od is None) != (gt_oc is None):
+        raise ValueError("gt_od and gt_oc are given together or both None")
+    masks = ((pred_od, "pred_od"), (pred_oc, "pred_oc"))
+    if gt_od is not None:
+        masks += ((gt_od, "gt_od"), (gt_oc, "gt_oc"))
+    for t, name in masks:
         _chk_dev(t, name, torch.uint8)
         if tuple(t.shape) != (B, 1, h, w) or t.device != img.device:
             raise ValueError("%s %s (%s) does not match img %s (%s)" % (name, tuple(t.shape), t.device, tuple(img.shape), img.device))
     L = lib()
-    words = L.query("wtpse_overlay_ws", B, h, w)
-    if words <= 0:
+    words = L.query("wtpse_overlay_ws" if gt_od is not None else "wtpse_overlay_pred_ws", B, h, w)
+    if words < 0 or (words == 0 and gt_od is not None):
         raise ValueError("overlay: unsupported size %s (2 <= h, w <= 4096)" % (tuple(img.shape),))
     original = torch.empty((B, h, w, 3), dtype=torch.uint8, device=img.device)
     over = torch.empty((B, h, w, 3), dtype=torch.uint8, device=img.device)
+    if gt_od is None:
+        L.call("wtpse_overlay_pred", ptr(img), ptr(pred_od), ptr(pred_oc), ptr(original), ptr(over), B, h, w, stream_ptr())
+        return original, over
     ws = workspace("overlay", words, img.device)
     L.call("wtpse_overlay", ptr(img), ptr(pred_od), ptr(pred_oc), ptr(gt_od), ptr(gt_oc), ptr(original), ptr(over), ptr(ws), B, h, w,
            stream_ptr())
@@ -1031,3 +1040,43 @@ def label_thresholds(mask):
     oc = torch.empty(mask.shape, dtype=torch.float32, device=mask.device)
     lib().call("wtpse_label_thresholds", ptr(mask), ptr(od), ptr(oc), mask.numel(), stream_ptr())
     return od, oc
+
+
+# ----------------------------------------------------------------------------------------------- segmenting unlabelled images
+def image_finish(img_u8):
+    """[N,S,S,3] uint8 on the device -> [N,3,S,S] fp32 = img / 127.5 - 1 (two roundings): wtpse_input_finish's image, no mask."""
+    t = img_u8
+    if not (t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and t.dim() == 4 and t.shape[3] == 3 and t.shape[1] == t.shape[2]):
+        raise ValueError("img_u8 must be a contiguous [N,S,S,3] uint8 tensor in device memory (got %s, %s, %s)"
+                         % (tuple(t.shape), t.device, t.dtype))
+    N, S = t.shape[0], t.shape[1]
+    image = torch.empty((N, 3, S, S), dtype=torch.float32, device=t.device)
+    lib().call("wtpse_image_finish", ptr(t), ptr(image), N, S, stream_ptr())
+    return image
+
+
+def label_map(disc, cup):
+    """Two uint8 masks [B,1,h,w] (nonzero = object) -> the grey-level label uint8 [B,1,h,w]: 0 where cup, else 128 where disc, else
+    255 (segment.label_map_host byte for byte; label_thresholds reads it back)."""
+    _chk_dev(disc, "disc", torch.uint8)
+    _chk_dev(cup, "cup", torch.uint8)
+    if disc.shape != cup.shape or disc.device != cup.device:
+        raise ValueError("disc %s and cup %s differ in shape or device" % (tuple(disc.shape), tuple(cup.shape)))
+    out = torch.empty(disc.shape, dtype=torch.uint8, device=disc.device)
+    lib().call("wtpse_label_map", ptr(disc), ptr(cup), ptr(out), disc.numel(), stream_ptr())
+    return out
+
+
+GEOMETRY_FIELDS = ("area", "top", "bottom", "left", "right", "sum_r", "sum_c", "reserved")
+
+
+def mask_geometry(mask):
+    """uint8 masks [B,1,h,w] on the device -> records [B,8] int64 (fields GEOMETRY_FIELDS) over the nonzero pixels; an empty mask:
+    (0, h, -1, w, -1, 0, 0, 0).  segment.mask_geometry_host exactly; segment.measure finishes a pair of them."""
+    _chk_dev(mask, "mask", torch.uint8)
+    B, _, h, w = mask.shape
+    if not (1 <= B < 8192 and 1 <= h <= 4096 and 1 <= w <= 4096):
+        raise ValueError("mask_geometry: unsupported size %s (1 <= h, w <= 4096)" % (tuple(mask.shape),))
+    rec = torch.empty((B, 8), dtype=torch.int64, device=mask.device)
+    lib().call("wtpse_mask_geometry", ptr(mask), ptr(rec), B, h, w, stream_ptr())
+    return rec

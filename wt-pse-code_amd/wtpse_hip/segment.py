@@ -1,0 +1,316 @@
+"""Segmenting unlabelled images: a trained checkpoint and any folder of region-of-interest crops — no ground truth, no naming rule,
+any mix of sizes — through both stages, and per image the segmentation as a label file, the contours on the picture and the
+cup-to-disc ratios.  The test run (test_run.py) scores a labelled split; this is the path for images that have no label.
+
+    python -m wtpse_hip.segment --images DIR --checkpoint C --out O [--batch-size 9] [--no-overlay]
+
+    O/mask/<stem>.png        mode 'L', the image's own size, grey levels 0 (cup) / 128 (disc) / 255 (background): the dataset's
+                             label encoding — FundusTree and FundusTestBatches read it as a label
+    O/overlay/<stem>.png     the contours on the resized network input: disc-or-cup green, cup blue (--no-overlay: not written)
+    O/measurements.csv       CSV_COLUMNS, one row per image
+    O/summary.json           n, n_empty_disc, n_empty_cup and the means of the three ratios over the images where they are defined
+
+Front (`Segmenter.front`): the decoded uint8 images go to the GPU as they are; the LANCZOS resize to 256 x 256 — FundusTree's
+Image.resize((S, S), Image.LANCZOS), bit for bit — is two passes of wtpse_resample_u8 with `resample_table(..., "lanczos")`, batched
+over the images of one size, a pass whose axis already has the target length skipped as Pillow skips it; wtpse_image_finish
+normalises.  A network batch is `batch_size` consecutive images whatever their sizes: the networks only see 256 x 256.
+
+Back (`Segmenter.back`): per native size, both logit maps resized bilinearly (ops.resize_bilinear), ops.postprocess_masks,
+ops.label_map, ops.mask_geometry and — on the network input resized bilinearly to the native size, the test run's picture —
+ops.overlay without a ground truth.  Everything a size group produces comes back in ONE device -> host copy.
+
+Host specifications beside the device path: `label_map_host`, `mask_geometry_host`; `measure` finishes a table row from the two
+geometry records in float64.  The ratios: vcdr = cup height / disc height and hcdr = cup width / disc width of the bounding boxes,
+acdr = cup area / disc area; nan when the disc is empty, 0.0 when only the cup is.  The cup is NOT clipped to the disc: the table
+reports what the post-processing produced.
+"""
+import json
+import os
+
+import numpy as np
+import torch
+
+from . import ops
+from . import validate as V
+from .input_pipeline import DeviceInputPipeline, _dev_i32, resample_table
+
+EXTENSIONS = (".png", ".jpg", ".jpeg", ".bmp", ".tif", ".tiff")
+INT_COLUMNS = ("height", "width", "disc_area", "cup_area", "disc_top", "disc_bottom", "disc_left", "disc_right",
+               "cup_top", "cup_bottom", "cup_left", "cup_right")
+FLOAT_COLUMNS = ("disc_cy", "disc_cx", "cup_cy", "cup_cx", "vcdr", "hcdr", "acdr")
+CSV_COLUMNS = ("index", "name") + INT_COLUMNS + FLOAT_COLUMNS
+RATIOS = ("vcdr", "hcdr", "acdr")
+
+
+# ---- the host specifications ----------------------------------------------------------------------------------------------
+def label_map_host(disc, cup):
+    """Two masks (nonzero = object) -> uint8 grey levels: 0 where cup, else 128 where disc, else 255.  The inverse of
+    test_run.label_thresholds_host: read back, oc == (cup != 0) and od == ((disc | cup) != 0)."""
+    disc, cup = np.asarray(disc) != 0, np.asarray(cup) != 0
+    return np.where(cup, 0, np.where(disc, 128, 255)).astype(np.uint8)
+
+
+def mask_geometry_host(mask):
+    """[..., h, w] masks -> int64 [..., 8] = (area, top, bottom, left, right, sum_r, sum_c, 0) over the nonzero pixels; an empty mask:
+    (0, h, -1, w, -1, 0, 0, 0).  ops.mask_geometry's records."""
+    mask = np.asarray(mask) != 0
+    h, w = mask.shape[-2:]
+    out = np.zeros(mask.shape[:-2] + (8,), np.int64)
+    for idx in np.ndindex(*mask.shape[:-2]):
+        r, c = np.nonzero(mask[idx])
+        if len(r):
+            out[idx] = (len(r), r.min(), r.max(), c.min(), c.max(), r.astype(np.int64).sum(), c.astype(np.int64).sum(), 0)
+        else:
+            out[idx] = (0, h, -1, w, -1, 0, 0, 0)
+    return out
+
+
+def _ratio(num, den):
+    return float("nan") if den == 0 else float(np.float64(num) / np.float64(den))
+
+
+def measure(rec_disc, rec_cup, h, w):
+    """The two geometry records of one image -> its table row without index and name (INT_COLUMNS as int, FLOAT_COLUMNS as float)."""
+    d, c = [int(v) for v in rec_disc], [int(v) for v in rec_cup]
+    row = {"height": int(h), "width": int(w), "disc_area": d[0], "cup_area": c[0]}
+    ext = {}
+    for name, r in (("disc", d), ("cup", c)):
+        row.update({name + "_top": r[1], name + "_bottom": r[2], name + "_left": r[3], name + "_right": r[4]})
+        ext[name] = (r[2] - r[1] + 1, r[4] - r[3] + 1) if r[0] else (0, 0)
+        row[name + "_cy"], row[name + "_cx"] = _ratio(r[5], r[0]), _ratio(r[6], r[0])
+    row["vcdr"] = _ratio(ext["cup"][0], ext["disc"][0])
+    row["hcdr"] = _ratio(ext["cup"][1], ext["disc"][1])
+    row["acdr"] = _ratio(c[0], d[0])
+    return row
+
+
+def summarise(rows):
+    """-> {n, n_empty_disc, n_empty_cup, mean_vcdr, mean_hcdr, mean_acdr}: a mean over the rows where the ratio is defined, None
+    when there is none."""
+    out = {"n": len(rows), "n_empty_disc": sum(1 for r in rows if r["disc_area"] == 0),
+           "n_empty_cup": sum(1 for r in rows if r["cup_area"] == 0)}
+    for k in RATIOS:
+        vals = [r[k] for r in rows if r[k] == r[k]]
+        out["mean_" + k] = float(np.mean(np.array(vals, np.float64))) if vals else None
+    return out
+
+
+# ---- the table ------------------------------------------------------------------------------------------------------------
+def write_measurements(out_dir, rows, summary):
+    """rows: [{CSV_COLUMNS}] -> out_dir/measurements.csv (floats as repr: they read back to the same float64; nan as "nan") and
+    out_dir/summary.json (an undefined mean as null)."""
+    os.makedirs(out_dir, exist_ok=True)
+    with open(os.path.join(out_dir, "measurements.csv"), "w") as f:
+        f.write(",".join(CSV_COLUMNS) + "\n")
+        for r in rows:
+            name = str(r["name"])
+            if any(ch in name for ch in ',"\n'):
+                name = '"' + name.replace('"', '""') + '"'
+            f.write(",".join([str(int(r["index"])), name] + [str(int(r[k])) for k in INT_COLUMNS]
+                             + [repr(float(r[k])) for k in FLOAT_COLUMNS]) + "\n")
+    with open(os.path.join(out_dir, "summary.json"), "w") as f:
+        json.dump(summary, f, indent=1, sort_keys=True, allow_nan=False)
+        f.write("\n")
+
+
+def read_measurements(out_dir):
+    """-> (rows, summary) as write_measurements wrote them."""
+    import csv
+    with open(os.path.join(out_dir, "measurements.csv"), newline="") as f:
+        rows = [dict(r, index=int(r["index"]), **{k: int(r[k]) for k in INT_COLUMNS}, **{k: float(r[k]) for k in FLOAT_COLUMNS})
+                for r in csv.DictReader(f)]
+    with open(os.path.join(out_dir, "summary.json")) as f:
+        return rows, json.load(f)
+
+
+# ---- the feed -------------------------------------------------------------------------------------------------------------
+class ImageFolder:
+    """A directory — its files with one of EXTENSIONS, case-insensitive, sorted by file name — or an explicit list of paths, in its
+    order.  No naming rule, no mask.  `names[i]` is the output name of image i: its stem plus ".png"; two inputs with one stem raise
+    ValueError here, before anything runs."""
+
+    def __init__(self, path_or_list):
+        if isinstance(path_or_list, (str, os.PathLike)):
+            root = os.fspath(path_or_list)
+            files = sorted(f for f in os.listdir(root)
+                           if os.path.splitext(f)[1].lower() in EXTENSIONS and os.path.isfile(os.path.join(root, f)))
+            self.paths = [os.path.join(root, f) for f in files]
+        else:
+            self.paths = [os.fspath(p) for p in path_or_list]
+        self.names = [os.path.splitext(os.path.basename(p))[0] + ".png" for p in self.paths]
+        seen = {}
+        for p, n in zip(self.paths, self.names):
+            if n in seen:
+                raise ValueError("%s and %s would both be written as %s" % (seen[n], p, n))
+            seen[n] = p
+
+    def __len__(self):
+        return len(self.paths)
+
+    def load(self, i):
+        """-> [h,w,3] uint8, decoded as FundusTree decodes: Image.open(p).convert("RGB")."""
+        from PIL import Image
+        return np.array(Image.open(self.paths[i]).convert("RGB"))
+
+
+def _groups(sizes):
+    """{(h, w): [positions]} in order of first appearance."""
+    g = {}
+    for i, s in enumerate(sizes):
+        g.setdefault((int(s[0]), int(s[1])), []).append(i)
+    return g
+
+
+# ---- the driver -----------------------------------------------------------------------------------------------------------
+class Segmenter:
+    """run(folder) segments every image of an ImageFolder (or of what ImageFolder takes) in batches of `batch_size` consecutive
+    images and writes the files of the module docstring; -> the summary, `self.rows` keeps the table.  Eval mode for the duration, the
+    previous modes restored.  front / back are the two halves around validate.predict_pair."""
+
+    def __init__(self, model, model_shape, model_oc, model_shape_oc, out_dir, batch_size=9, overlay=True, size=256):
+        if int(batch_size) < 1:
+            raise ValueError("batch_size must be positive")
+        self.nets = [model, model_shape, model_oc, model_shape_oc]
+        self.out_dir, self.batch_size, self.overlay, self.size = out_dir, int(batch_size), bool(overlay), int(size)
+        self._pipe, self._tables, self.rows = None, {}, []
+
+    def _lanczos_pass(self, src, vertical):
+        """One pass of Pillow's LANCZOS resize to `size` along the width (vertical = False) or the height of src [N,H,W,3] uint8:
+        DeviceInputPipeline's resampling launch with the "lanczos" table of the axis' length."""
+        in_size = src.shape[1] if vertical else src.shape[2]
+        if self._pipe is None or self._pipe.device != src.device:
+            self._pipe, self._tables = DeviceInputPipeline(self.size, src.device), {}
+        t = self._tables.get(in_size)
+        if t is None:
+            b, k, ks = resample_table(in_size, self.size, "lanczos")
+            t = self._tables[in_size] = (_dev_i32(b, src.device), _dev_i32(k, src.device), ks)
+        return self._pipe._resample(src, t[0], t[1], None, t[2], self.size, vertical)
+
+    def front(self, images, device="cuda"):
+        """images: decoded [h,w,3] uint8 arrays of any sizes -> [B,3,S,S] fp32 on the device, in their order: FundusTree's LANCZOS
+        resize, then FundusTestBatches.host_sample's normalisation, bit for bit."""
+        S, dev = self.size, torch.device(device)
+        if dev.type != "cuda":
+            raise RuntimeError("the segmentation front runs on the GPU only (no CPU fallback)")
+        if dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        images = [np.ascontiguousarray(im) for im in images]
+        for im in images:
+            if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3:
+                raise ValueError("images must be decoded [h,w,3] uint8 arrays (got %s %s)" % (im.shape, im.dtype))
+        groups = _groups([im.shape[:2] for im in images])
+        small = torch.empty((len(images), S, S, 3), dtype=torch.uint8, device=dev)
+        for (H, W), idx in groups.items():
+            t = torch.from_numpy(np.stack([images[i] for i in idx])).to(dev)
+            if W != S:
+                t = self._lanczos_pass(t, False)
+            if H != S:
+                t = self._lanczos_pass(t, True)
+            if len(groups) == 1:
+                small = t
+            else:
+                small[torch.tensor(idx, device=dev)] = t
+        return ops.image_finish(small.contiguous())
+
+    def back(self, image, logits_od, logits_oc, sizes):
+        """image [B,3,S,S] (the network input) and the two logit maps [B,1,S,S] on the device, sizes = [(h, w)] per image ->
+        (label maps [h,w] uint8, overlays [h,w,3] uint8 or None, rows = `measure` dicts), lists in the images' order."""
+        B, S = image.shape[0], self.size
+        if len(sizes) != B or tuple(logits_od.shape) != (B, 1, S, S) or tuple(logits_oc.shape) != (B, 1, S, S):
+            raise ValueError("back: %d sizes, logits %s / %s for an image batch %s"
+                             % (len(sizes), tuple(logits_od.shape), tuple(logits_oc.shape), tuple(image.shape)))
+        labels, overlays, rows = [None] * B, [None] * B, [None] * B
+        groups = _groups(sizes)
+        for (h, w), idx in groups.items():
+            n = len(idx)
+            if len(groups) == 1:
+                img, lod, loc = image.contiguous(), logits_od.contiguous(), logits_oc.contiguous()
+            else:
+                sel = torch.tensor(idx, device=image.device)
+                img, lod, loc = image[sel], logits_od[sel], logits_oc[sel]
+            if (h, w) != (S, S):
+                lod, loc = ops.resize_bilinear(lod, (h, w)), ops.resize_bilinear(loc, (h, w))
+            masks = ops.postprocess_masks(torch.cat((lod, loc), 0))
+            disc, cup = masks[:n], masks[n:]
+            blob = [ops.mask_geometry(masks).view(torch.uint8).reshape(-1), ops.label_map(disc, cup).reshape(-1)]
+            if self.overlay:
+                if (h, w) != (S, S):
+                    img = ops.resize_bilinear(img, (h, w))              # the test run's picture (test_visulization.py:231-232)
+                blob.append(ops.overlay(img, disc, cup, None, None)[1].reshape(-1))
+            host = torch.cat(blob).cpu().numpy()                       # the one copy
+            rec = host[:2 * n * 64].view(np.int64).reshape(2 * n, 8)
+            off = 2 * n * 64
+            lm = host[off:off + n * h * w].reshape(n, h, w)
+            off += n * h * w
+            ov = host[off:off + n * h * w * 3].reshape(n, h, w, 3) if self.overlay else None
+            for j, i in enumerate(idx):
+                labels[i], rows[i] = lm[j], measure(rec[j], rec[n + j], h, w)
+                overlays[i] = ov[j] if self.overlay else None
+        return labels, overlays, rows
+
+    def write(self, names, labels, overlays, rows):
+        """One batch of `back` results -> O/mask and O/overlay under `names`; the rows join `self.rows` with their index and name."""
+        from PIL import Image
+        for sub in ("mask",) + (("overlay",) if self.overlay else ()):
+            os.makedirs(os.path.join(self.out_dir, sub), exist_ok=True)
+        for name, lm, ov, row in zip(names, labels, overlays, rows):
+            Image.fromarray(lm, "L").save(os.path.join(self.out_dir, "mask", name))
+            if ov is not None:
+                Image.fromarray(ov).save(os.path.join(self.out_dir, "overlay", name))
+            self.rows.append(dict(row, index=len(self.rows) + 1, name=name))
+
+    def finish(self):
+        """-> the summary of `self.rows`, written with them (measurements.csv, summary.json)."""
+        summary = summarise(self.rows)
+        write_measurements(self.out_dir, self.rows, summary)
+        return summary
+
+    def run(self, folder):
+        if not isinstance(folder, ImageFolder):
+            folder = ImageFolder(folder)
+        device = next(self.nets[0].parameters()).device
+        modes = [n.training for n in self.nets]
+        for n in self.nets:
+            n.eval()
+        self.rows = []
+        try:
+            for first in range(0, len(folder), self.batch_size):
+                idx = range(first, min(first + self.batch_size, len(folder)))
+                images = [folder.load(i) for i in idx]
+                image = self.front(images, device)
+                pred, pred_oc = V.predict_pair(*self.nets, image)
+                self.write([folder.names[i] for i in idx], *self.back(image, pred, pred_oc, [im.shape[:2] for im in images]))
+        finally:
+            for n, mode in zip(self.nets, modes):
+                n.train(mode)
+        return self.finish()
+
+
+# ---- command line -----------------------------------------------------------------------------------------------------------
+def main(argv=None):
+    import argparse
+    from .test_run import build_networks, load_checkpoint
+    ap = argparse.ArgumentParser(prog="python -m wtpse_hip.segment", description=__doc__.split("\n\n")[0])
+    ap.add_argument("--images", required=True, help="a directory of region-of-interest crops (%s)" % " ".join(EXTENSIONS))
+    ap.add_argument("--checkpoint", required=True, help="checkpoint_<epoch>.pth.tar as validate.Validator saves it")
+    ap.add_argument("--out", required=True)
+    ap.add_argument("--batch-size", type=int, default=9)
+    ap.add_argument("--no-overlay", action="store_true", help="write the masks and the table only")
+    args = ap.parse_args(argv)
+    if not torch.cuda.is_available():
+        raise SystemExit("wtpse_hip.segment needs the GPU: the networks have no CPU path")
+    folder = ImageFolder(args.images)
+    if len(folder) < 1:
+        raise SystemExit("no image (%s) under %s" % (" ".join(EXTENSIONS), args.images))
+    device = "cuda:0"
+    torch.cuda.set_device(0)
+    nets = build_networks(device)
+    load_checkpoint(args.checkpoint, *nets)
+    summary = Segmenter(*nets, out_dir=args.out, batch_size=args.batch_size, overlay=not args.no_overlay).run(folder)
+    torch.cuda.synchronize()
+    print(json.dumps(summary, sort_keys=True))
+    return 0
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())
