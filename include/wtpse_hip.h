@@ -555,6 +555,31 @@ int wtpse_label_map(const unsigned char* disc, const unsigned char* cup, unsigne
  * 1 <= h, w <= 4096. */
 int wtpse_mask_geometry(const unsigned char* mask, long long* rec, int B, int h, int w, void* stream);
 
+/* ---- sampled shape latents (csrc/uncertainty.hip; uncertainty.shape_samples_host is the fp64 specification) --------------------
+ * K draws of the student's latent and everything behind it in one launch.  Per image b, pixel p and sample k:
+ *   z = mu + scale * exp(logvar / 2) * eps[b,k,p]         (a non-finite exp(logvar / 2) counts as 0, as in the student's sampling)
+ *   a = sigmoid(w * z + b)                                 wb = device {w, b}: the attention layer
+ *   logit = (coef + a) * sum_c wout[c] * emb[b,c,p] + bout[0] (+ wz[0] * z: the latent's own weight of a cat_shape head, else NULL)
+ *   prob = sigmoid(logit)
+ * (the channel sum is taken once per pixel, outside the K loop: fuse[c] = coef * emb[c] + a * emb[c] is never formed) and
+ *   mean [B,HW] = the mean of the K probabilities, std_ [B,HW] = their population standard deviation (running Welford update: K equal
+ *   samples give exactly 0), votes [B,HW] uint8 = #{k: prob > threshold}, logits [B,K,HW] = logit (NULL: not stored).
+ * eps[b,k,p] is element offset + (b * K + k) * HW + p of the wtpse_randn stream `seed`, drawn in the kernel, or noise[b,k,p] when
+ * noise ([B,K,HW]) is given: wtpse_randn(noise, B * K * HW, seed, offset) makes the two bit for bit the same.
+ * 1 <= K <= 64, 1 <= CE <= 16, HW % 4 == 0, offset % 4 == 0 (a lane owns four pixels = one Philox block per sample), scale >= 0;
+ * emb, mu, logvar, noise, mean, std_, logits 16-byte aligned, votes 4-byte aligned. */
+int wtpse_shape_samples(const float* emb, int CE, const float* mu, const float* logvar, const float* wb, float coef,
+                        const float* wout, const float* bout, const float* wz, float scale, int K, unsigned long long seed,
+                        unsigned long long offset, const float* noise, float threshold, float* mean, float* std_,
+                        unsigned char* votes, float* logits, int B, int HW, void* stream);
+
+/* What wtpse_shape_samples would have left had every sampled logit been multiplied by a {0,1} map first (the cup's logits times
+ * od_pred, validate.predict_pair): where ref[b,p] <= 0 (or NaN), logits[b,k,p] = 0 for every k, mean = 0.5 (sigmoid(0)), std_ = 0 and
+ * votes = 0 (threshold >= 0.5 is the caller's premise); the other pixels are left as they are.  ref, mean, std_ [B,HW], logits
+ * [B,K,HW] or NULL; HW % 4 == 0, the same alignments. */
+int wtpse_shape_samples_mask(const float* ref, float* mean, float* std_, unsigned char* votes, float* logits, int K, int B, int HW,
+                             void* stream);
+
 /* ---- small utilities ------------------------------------------------------------------------------------------- */
 int wtpse_relu_mask(const float* dz, const float* ref, float* dy, int accumulate, long long n, void* stream);
 int wtpse_axpy(float* dst, const float* src, float alpha, long long n, void* stream);

@@ -178,6 +178,44 @@ class WT_PSE(E.HipNet, E.UNetBody):
             out, _ = E._conv(self.outc[0], self._outc_input(fuse, z))
             return out, pre
 
+    def predict_samples(self, learn_x_network, inputs_all, n_samples, seed=0, offset=0, scale=1.0, noise=None, want_logits=False,
+                        image_stride=None):
+        """predict() plus n_samples draws of the student's latent, z_k = mu + scale * exp(logvar / 2) * eps_k (the teacher's
+        reparameterisation, reference algorithms.py:1068-1075; predict() is z = mu), each pushed through the attention, the fusion and
+        the output convolution by ONE launch behind the single pass of the two U-Nets (ops.shape_samples).  eps[b,k] comes from the
+        ops.randn stream `seed` at offset + (b * n_samples + k) * H * W (image_stride: see ops.shape_samples), or from noise
+        [B,n_samples,H,W].  -> uncertainty.ShapeSamples: mean, std, votes over the samples' sigmoids (votes: sigmoid > 0.75), the
+        samples' logits when asked for, and predict()'s own (logit, pre), bitwise."""
+        from wtpse_hip.uncertainty import ShapeSamples
+        if not self.hparams['shape_prior']:
+            raise ValueError("predict_samples needs hparams['shape_prior']: without the shape network there is no latent to sample")
+        if self.n_classes != 1:
+            raise ValueError("predict_samples folds the output convolution into the sampling launch for n_classes = 1 (got %d)" % self.n_classes)
+        self.ensure_ready(repack=True)
+        if self.two_step:
+            inputs, wt_in = self._as_input(inputs_all[0]), self._as_input(inputs_all[1])
+        else:
+            inputs = wt_in = self._as_input(inputs_all)
+        training = self.training
+        coef = float(self.hparams['shape_attention_coeffient'])
+        wb = self.attention_layer.layer1.weight.data_ptr()
+        outc = self.outc[0]
+        with ops.fwd_scope(inputs.device):
+            emb = self._embedding(inputs, training, None)
+            learn_x_network.ensure_ready(repack=True)
+            w = E.deepwt_fwd(learn_x_network.wt_model, wt_in, want_tape=False)
+            z, fmap = learn_x_network._student_mu(E.Act(w.z2, None, True), learn_x_network.training, None, want_fmap=True)
+            logvar, _ = E.head_fwd(learn_x_network.logvar_prior, fmap, (0, 2, 4), False)
+            _, pre, _, fuse = ops.attn_fuse_fwd(z, wb, emb, coef, False, True, False)
+            out, _ = E._conv(outc, self._outc_input(fuse, z))
+        if noise is not None:
+            noise = self._as_input(noise)
+        wz = outc.weight.data_ptr() + 4 * self.feature_dim if self.cat_shape else 0
+        mean, std, votes, logits = ops.shape_samples(emb, z, logvar, wb, coef, outc.weight.data_ptr(), outc.bias.data_ptr(), wz,
+                                                     n_samples, seed, offset, scale, noise, 0.75, want_logits, image_stride)
+        return ShapeSamples(mean=mean, std=std, votes=votes, logits=logits, logit=out, pre=pre, n_samples=int(n_samples),
+                            seed=int(seed), offset=int(offset), scale=float(scale))
+
     def _outc_input(self, fuse, z):
         """cat_shape: torch.cat([fuse_embedding, z_posterior], 1) (algorithms.py:1253,1348).  This non-default branch
         materialises the 9-channel tensor (a device copy, no arithmetic): the two-pointer loader wants its first part in

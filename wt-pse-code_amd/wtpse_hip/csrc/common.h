@@ -41,13 +41,36 @@ __device__ __forceinline__ float wave_xor_sum(float v, int mask_hi) {
 
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 
-// One round of Philox4x32 (randn_k in pointwise.hip, uniform_f64_k in augment.hip); the callers bump the key between rounds.
+// One round of Philox4x32 (philox_normal4 below, uniform_f64_k in augment.hip); the callers bump the key between rounds.
 __device__ __forceinline__ void philox_round(uint32_t& c0, uint32_t& c1, uint32_t& c2, uint32_t& c3, uint32_t k0, uint32_t k1) {
   const uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u;
   uint32_t hi0 = __umulhi(M0, c0), lo0 = M0 * c0;
   uint32_t hi1 = __umulhi(M1, c2), lo1 = M1 * c2;
   uint32_t n0 = hi1 ^ c1 ^ k0, n1 = lo1, n2 = hi0 ^ c3 ^ k1, n3 = lo0;
   c0 = n0; c1 = n1; c2 = n2; c3 = n3;
+}
+
+// Philox4x32-10 block `ctr` of stream `seed` -> four standard normals (Box-Muller on the word pairs (0, 1) and (2, 3)): elements
+// 4 ctr .. 4 ctr + 3 of the stream wtpse_randn writes.  The one place the stream is defined: randn_k (pointwise.hip) and
+// shape_samples_k (uncertainty.hip) both draw through it, which is what makes their numbers bit for bit the same.
+__device__ __forceinline__ void philox_normal4(unsigned long long ctr, unsigned long long seed, float zv[4]) {
+  uint32_t c0 = (uint32_t)ctr, c1 = (uint32_t)(ctr >> 32), c2 = 0, c3 = 0;
+  uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    philox_round(c0, c1, c2, c3, k0, k1);
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  const float S = 2.3283064365386963e-10f;  // 2^-32
+  float u0 = ((float)c0 + 0.5f) * S, u1 = ((float)c1 + 0.5f) * S, u2 = ((float)c2 + 0.5f) * S, u3 = ((float)c3 + 0.5f) * S;
+  if (u0 >= 1.f) u0 = 0.99999994f;
+  if (u2 >= 1.f) u2 = 0.99999994f;
+  float r0 = sqrtf(-2.f * logf(u0)), r1 = sqrtf(-2.f * logf(u2));
+  zv[0] = r0 * cosf(6.283185307179586f * u1);
+  zv[1] = r0 * sinf(6.283185307179586f * u1);
+  zv[2] = r1 * cosf(6.283185307179586f * u3);
+  zv[3] = r1 * sinf(6.283185307179586f * u3);
 }
 
 // The logistic function as the reference's od_pred / post-processing thresholds see it (roi_k, postprocess.hip).

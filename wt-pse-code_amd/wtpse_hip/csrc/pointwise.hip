@@ -710,7 +710,7 @@ __global__ __launch_bounds__(64) void loss_log_k(const float* s0, const float* s
 }
 
 // ------------------------------------------------------------------------------------------------ Philox4x32-10 -> N(0,1)
-// (philox_round: common.h)
+// (philox_normal4: common.h)
 // element i of the stream (seed, offset) depends only on (seed, offset + i/4): any sharding of the rows
 // over ranks reproduces the single-device stream when each rank passes its global element offset
 // offset_dev (optional): device counter added to `offset` (the stream position lives in device memory so that a
@@ -721,22 +721,8 @@ __global__ __launch_bounds__(256) void randn_k(float* __restrict__ out, long lon
   long long q = (long long)blockIdx.x * 256 + threadIdx.x;  // one Philox block = 4 normals
   long long base = q * 4;
   if (base >= n) return;
-  unsigned long long ctr = offset / 4 + (unsigned long long)q;
-  uint32_t c0 = (uint32_t)ctr, c1 = (uint32_t)(ctr >> 32), c2 = 0, c3 = 0;
-  uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    philox_round(c0, c1, c2, c3, k0, k1);
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  const float S = 2.3283064365386963e-10f;  // 2^-32
-  float u0 = ((float)c0 + 0.5f) * S, u1 = ((float)c1 + 0.5f) * S, u2 = ((float)c2 + 0.5f) * S, u3 = ((float)c3 + 0.5f) * S;
-  if (u0 >= 1.f) u0 = 0.99999994f;
-  if (u2 >= 1.f) u2 = 0.99999994f;
-  float r0 = sqrtf(-2.f * logf(u0)), r1 = sqrtf(-2.f * logf(u2));
-  float zv[4] = {r0 * cosf(6.283185307179586f * u1), r0 * sinf(6.283185307179586f * u1),
-                 r1 * cosf(6.283185307179586f * u3), r1 * sinf(6.283185307179586f * u3)};
+  float zv[4];
+  philox_normal4(offset / 4 + (unsigned long long)q, seed, zv);
 #pragma unroll
   for (int k = 0; k < 4; ++k)
     if (base + k < n) out[base + k] = zv[k];

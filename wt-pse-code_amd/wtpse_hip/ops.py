@@ -862,6 +862,53 @@ def randn(shape, device, seed, offset=0, offset_dev=None):
     return out
 
 
+def shape_samples(emb, mu, logvar, wb_ptr, coef, wout_ptr, bout_ptr, wz_ptr, n_samples, seed=0, offset=0, scale=1.0, noise=None,
+                  threshold=0.75, want_logits=False, image_stride=None):
+    """K = n_samples draws of the latent and everything behind it in one launch (csrc/uncertainty.hip; uncertainty.shape_samples_host
+    is its specification): emb [B,CE,H,W], mu / logvar [B,1,H,W]; wb_ptr -> {w, b} of the attention layer, wout_ptr -> [CE] and
+    bout_ptr -> [1] of the output convolution, wz_ptr -> the latent's own weight (cat_shape) or 0.  eps[b,k] is the H*W elements
+    of the ops.randn stream `seed` from offset + (b*K + k)*H*W on, or noise[b,k] when noise [B,K,H,W] is given.
+    -> (mean, std [B,1,H,W] fp32, votes [B,1,H,W] uint8, logits [B,K,H,W] or None).
+    image_stride (elements, a multiple of 4): image b draws from offset + b*image_stride instead of offset + b*K*H*W — one launch per
+    image then, on views of the same tensors (the kernel's stream layout is dense)."""
+    _chk(emb, "emb"); _chk(mu, "mu"); _chk(logvar, "logvar"); _chk(noise, "noise")
+    B, CE, H, W = emb.shape
+    K, HW = int(n_samples), H * W
+    if mu.numel() != B * HW or logvar.numel() != B * HW:
+        raise ValueError("mu %s / logvar %s do not match emb %s" % (tuple(mu.shape), tuple(logvar.shape), tuple(emb.shape)))
+    if noise is not None and tuple(noise.shape) != (B, K, H, W):
+        raise ValueError("noise must be [B,K,H,W] = %s (got %s)" % ((B, K, H, W), tuple(noise.shape)))
+    dev = emb.device
+    mean = torch.empty((B, 1, H, W), dtype=torch.float32, device=dev)
+    std = torch.empty((B, 1, H, W), dtype=torch.float32, device=dev)
+    votes = torch.empty((B, 1, H, W), dtype=torch.uint8, device=dev)
+    logits = torch.empty((B, K, H, W), dtype=torch.float32, device=dev) if want_logits else None
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+
+    def launch(sl, off, nb):
+        v = lambda t: 0 if t is None else t[sl].data_ptr()
+        lib().call("wtpse_shape_samples", v(emb), CE, v(mu), v(logvar), wb_ptr, float(coef), wout_ptr, bout_ptr, wz_ptr, float(scale), K,
+                   seed, int(off), v(noise), float(threshold), v(mean), v(std), v(votes), v(logits), nb, HW, stream_ptr())
+
+    if image_stride is None or int(image_stride) == K * HW or B == 1:
+        launch(slice(0, B), offset, B)
+    else:
+        for b in range(B):
+            launch(slice(b, b + 1), int(offset) + b * int(image_stride), 1)
+    return mean, std, votes, logits
+
+
+def shape_samples_mask_(ref, mean, std, votes, logits=None):
+    """In place, what shape_samples would have left had every sampled logit been multiplied by the {0,1} map ref [B,1,H,W] first (the
+    cup's logits times od_pred): where ref <= 0, logits 0, mean 0.5, std 0, votes 0."""
+    _chk(ref, "ref"); _chk(mean, "mean"); _chk(std, "std"); _chk(logits, "logits")
+    B, _, H, W = mean.shape
+    K = 1 if logits is None else logits.shape[1]
+    if not (ref.numel() == mean.numel() == std.numel() == votes.numel() and votes.dtype == torch.uint8 and votes.is_contiguous()):
+        raise ValueError("shape_samples_mask_: ref, mean, std and votes (uint8) must be [B,1,H,W] of one size")
+    lib().call("wtpse_shape_samples_mask", ptr(ref), ptr(mean), ptr(std), ptr(votes), ptr(logits), K, B, H * W, stream_ptr())
+
+
 def counter_add(counter, inc):
     """*counter += inc on the current stream (device int32 or int64 scalar tensor)."""
     lib().call("wtpse_counter_add", ptr(counter), int(inc), int(counter.dtype == torch.int64), stream_ptr())

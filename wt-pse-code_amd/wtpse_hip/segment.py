@@ -2,13 +2,27 @@
 any mix of sizes — through both stages, and per image the segmentation as a label file, the contours on the picture and the
 cup-to-disc ratios.  The test run (test_run.py) scores a labelled split; this is the path for images that have no label.
 
-    python -m wtpse_hip.segment --images DIR --checkpoint C --out O [--batch-size 9] [--no-overlay]
+    python -m wtpse_hip.segment --images DIR --checkpoint C --out O [--batch-size 9] [--no-overlay] [--samples K --seed S --sample-scale X]
 
     O/mask/<stem>.png        mode 'L', the image's own size, grey levels 0 (cup) / 128 (disc) / 255 (background): the dataset's
                              label encoding — FundusTree and FundusTestBatches read it as a label
     O/overlay/<stem>.png     the contours on the resized network input: disc-or-cup green, cup blue (--no-overlay: not written)
     O/measurements.csv       CSV_COLUMNS, one row per image
     O/summary.json           n, n_empty_disc, n_empty_cup and the means of the three ratios over the images where they are defined
+
+With --samples K (Segmenter(samples=K); 0, the default, changes nothing and writes none of these) every image is also predicted under
+K sampled shape latents (uncertainty.py, validate.predict_pair_samples) from the same two U-Net passes:
+
+    O/uncertainty/<stem>.png the spread of the K predictions at the image's own size, RGB: R = round(255 min(1, 2 std_disc)), G the
+                             same for the cup, B = 0
+    O/uncertainty.csv        uncertainty.CSV_COLUMNS, one row per image: mean / std / 5th / 95th percentile of each ratio over the
+                             samples whose disc is not empty (n_defined of n_samples; nan when none is), the pixels the samples'
+                             votes disagree on and the mean spread per class
+    O/summary.json           gains n_samples and mean_vcdr_std (the mean of vcdr_std over the images where it is defined)
+
+The per-sample ratios are taken from the samples' masks at the network's 256 x 256 (post-processed like the deterministic ones; the
+ratios are scale-free), not at the native size.  The image at folder index i draws its 2 K S^2 normals from position 2 K S^2 i of the
+stream `seed` whatever the batch size (`Segmenter.sample_offsets`), so a folder segmented twice draws the same numbers.
 
 Front (`Segmenter.front`): the decoded uint8 images go to the GPU as they are; the LANCZOS resize to 256 x 256 — FundusTree's
 Image.resize((S, S), Image.LANCZOS), bit for bit — is two passes of wtpse_resample_u8 with `resample_table(..., "lanczos")`, batched
@@ -31,6 +45,7 @@ import numpy as np
 import torch
 
 from . import ops
+from . import uncertainty as U
 from . import validate as V
 from .input_pipeline import DeviceInputPipeline, _dev_i32, resample_table
 
@@ -167,9 +182,16 @@ class Segmenter:
     images and writes the files of the module docstring; -> the summary, `self.rows` keeps the table.  Eval mode for the duration, the
     previous modes restored.  front / back are the two halves around validate.predict_pair."""
 
-    def __init__(self, model, model_shape, model_oc, model_shape_oc, out_dir, batch_size=9, overlay=True, size=256):
+    def __init__(self, model, model_shape, model_oc, model_shape_oc, out_dir, batch_size=9, overlay=True, size=256, samples=0, seed=0,
+                 scale=1.0):
         if int(batch_size) < 1:
             raise ValueError("batch_size must be positive")
+        if not 0 <= int(samples) <= 64 or not float(scale) >= 0.0:
+            raise ValueError("samples must lie in 0..64 and scale must not be negative (got %r, %r)" % (samples, scale))
+        if 2 * int(batch_size) * int(samples) >= 8192:
+            raise ValueError("batch_size * samples must stay below 4096 (one set of post-processing launches per batch)")
+        self.samples, self.seed, self.scale = int(samples), int(seed), float(scale)
+        self.sample_rows, self.sample_offsets = [], []
         self.nets = [model, model_shape, model_oc, model_shape_oc]
         self.out_dir, self.batch_size, self.overlay, self.size = out_dir, int(batch_size), bool(overlay), int(size)
         self._pipe, self._tables, self.rows = None, {}, []
@@ -212,14 +234,16 @@ class Segmenter:
                 small[torch.tensor(idx, device=dev)] = t
         return ops.image_finish(small.contiguous())
 
-    def back(self, image, logits_od, logits_oc, sizes):
+    def back(self, image, logits_od, logits_oc, sizes, spread=None):
         """image [B,3,S,S] (the network input) and the two logit maps [B,1,S,S] on the device, sizes = [(h, w)] per image ->
-        (label maps [h,w] uint8, overlays [h,w,3] uint8 or None, rows = `measure` dicts), lists in the images' order."""
+        (label maps [h,w] uint8, overlays [h,w,3] uint8 or None, rows = `measure` dicts), lists in the images' order.
+        spread = (std_disc, std_cup) [B,1,S,S] fp32: resized to the native sizes like the logits, they ride in each size group's copy
+        and come back as a fourth list of [2,h,w] fp32 arrays."""
         B, S = image.shape[0], self.size
         if len(sizes) != B or tuple(logits_od.shape) != (B, 1, S, S) or tuple(logits_oc.shape) != (B, 1, S, S):
             raise ValueError("back: %d sizes, logits %s / %s for an image batch %s"
                              % (len(sizes), tuple(logits_od.shape), tuple(logits_oc.shape), tuple(image.shape)))
-        labels, overlays, rows = [None] * B, [None] * B, [None] * B
+        labels, overlays, rows, spreads = [None] * B, [None] * B, [None] * B, [None] * B
         groups = _groups(sizes)
         for (h, w), idx in groups.items():
             n = len(idx)
@@ -228,6 +252,10 @@ class Segmenter:
             else:
                 sel = torch.tensor(idx, device=image.device)
                 img, lod, loc = image[sel], logits_od[sel], logits_oc[sel]
+            if spread is not None:
+                sp = torch.cat((spread[0], spread[1]), 0) if len(groups) == 1 else torch.cat((spread[0][sel], spread[1][sel]), 0)
+                if (h, w) != (S, S):
+                    sp = ops.resize_bilinear(sp.contiguous(), (h, w))
             if (h, w) != (S, S):
                 lod, loc = ops.resize_bilinear(lod, (h, w)), ops.resize_bilinear(loc, (h, w))
             masks = ops.postprocess_masks(torch.cat((lod, loc), 0))
@@ -237,16 +265,51 @@ class Segmenter:
                 if (h, w) != (S, S):
                     img = ops.resize_bilinear(img, (h, w))              # the test run's picture (test_visulization.py:231-232)
                 blob.append(ops.overlay(img, disc, cup, None, None)[1].reshape(-1))
+            if spread is not None:
+                blob.append(sp.contiguous().view(torch.uint8).reshape(-1))
             host = torch.cat(blob).cpu().numpy()                       # the one copy
             rec = host[:2 * n * 64].view(np.int64).reshape(2 * n, 8)
             off = 2 * n * 64
             lm = host[off:off + n * h * w].reshape(n, h, w)
             off += n * h * w
             ov = host[off:off + n * h * w * 3].reshape(n, h, w, 3) if self.overlay else None
+            off += n * h * w * 3 if self.overlay else 0
+            sm = host[off:off + 8 * n * h * w].copy().view(np.float32).reshape(2, n, h, w) if spread is not None else None
             for j, i in enumerate(idx):
                 labels[i], rows[i] = lm[j], measure(rec[j], rec[n + j], h, w)
                 overlays[i] = ov[j] if self.overlay else None
-        return labels, overlays, rows
+                spreads[i] = sm[:, j] if spread is not None else None
+        return (labels, overlays, rows) if spread is None else (labels, overlays, rows, spreads)
+
+    def back_samples(self, disc, cup):
+        """The uncertainty.ShapeSamples of the two stages (with their [B,K,S,S] logits) -> per image the uncertainty.csv row without
+        index and name.  Both classes' B K sampled logit maps go through ops.postprocess_masks and ops.mask_geometry at the network
+        size in one set of launches; the records, the vote maps and the spread maps come back in one copy; `measure` per sample and
+        the statistics (uncertainty.ratio_statistics / map_statistics) are the host's."""
+        B, K, S = disc.logits.shape[0], disc.logits.shape[1], self.size
+        masks = ops.postprocess_masks(torch.cat((disc.logits.reshape(B * K, 1, S, S), cup.logits.reshape(B * K, 1, S, S)), 0))
+        blob = [ops.mask_geometry(masks).view(torch.uint8).reshape(-1), disc.votes.reshape(-1), cup.votes.reshape(-1),
+                torch.cat((disc.std, cup.std), 0).view(torch.uint8).reshape(-1)]
+        host = torch.cat(blob).cpu().numpy()
+        n = 2 * B * K * 64
+        rec = host[:n].view(np.int64).reshape(2, B, K, 8)
+        votes = host[n:n + 2 * B * S * S].reshape(2, B, S, S)
+        std = host[n + 2 * B * S * S:].copy().view(np.float32).reshape(2, B, S, S)
+        rows = []
+        for b in range(B):
+            row = U.ratio_statistics([measure(rec[0, b, k], rec[1, b, k], S, S) for k in range(K)])
+            for c, name in enumerate(("disc", "cup")):
+                row[name + "_disagree_px"], row[name + "_std_mean"] = U.map_statistics(votes[c, b], std[c, b], K)
+            rows.append(row)
+        return rows
+
+    def write_samples(self, names, spreads, rows):
+        """One batch of sampled results -> O/uncertainty under `names`; the rows join `self.sample_rows` with their index and name."""
+        from PIL import Image
+        os.makedirs(os.path.join(self.out_dir, "uncertainty"), exist_ok=True)
+        for name, sp, row in zip(names, spreads, rows):
+            Image.fromarray(U.std_picture(sp[0], sp[1])).save(os.path.join(self.out_dir, "uncertainty", name))
+            self.sample_rows.append(dict(row, index=len(self.sample_rows) + 1, name=name))
 
     def write(self, names, labels, overlays, rows):
         """One batch of `back` results -> O/mask and O/overlay under `names`; the rows join `self.rows` with their index and name."""
@@ -262,7 +325,12 @@ class Segmenter:
     def finish(self):
         """-> the summary of `self.rows`, written with them (measurements.csv, summary.json)."""
         summary = summarise(self.rows)
+        if self.samples:
+            vals = [r["vcdr_std"] for r in self.sample_rows if r["vcdr_std"] == r["vcdr_std"]]
+            summary.update(n_samples=self.samples, mean_vcdr_std=float(np.mean(np.array(vals, np.float64))) if vals else None)
         write_measurements(self.out_dir, self.rows, summary)
+        if self.samples:
+            U.write_csv(self.out_dir, self.sample_rows)
         return summary
 
     def run(self, folder):
@@ -272,14 +340,24 @@ class Segmenter:
         modes = [n.training for n in self.nets]
         for n in self.nets:
             n.eval()
-        self.rows = []
+        self.rows, self.sample_rows, self.sample_offsets = [], [], []
+        per_image = 2 * self.samples * self.size * self.size          # an image's share of the noise stream (predict_pair_samples)
         try:
             for first in range(0, len(folder), self.batch_size):
                 idx = range(first, min(first + self.batch_size, len(folder)))
                 images = [folder.load(i) for i in idx]
                 image = self.front(images, device)
-                pred, pred_oc = V.predict_pair(*self.nets, image)
-                self.write([folder.names[i] for i in idx], *self.back(image, pred, pred_oc, [im.shape[:2] for im in images]))
+                names, sizes = [folder.names[i] for i in idx], [im.shape[:2] for im in images]
+                if not self.samples:
+                    pred, pred_oc = V.predict_pair(*self.nets, image)
+                    self.write(names, *self.back(image, pred, pred_oc, sizes))
+                    continue
+                pred, pred_oc, disc, cup = V.predict_pair_samples(*self.nets, image, self.samples, self.seed, first * per_image, self.scale,
+                                                                  want_logits=True)
+                self.sample_offsets += [i * per_image for i in idx]
+                labels, overlays, rows, spreads = self.back(image, pred, pred_oc, sizes, (disc.std, cup.std))
+                self.write(names, labels, overlays, rows)
+                self.write_samples(names, spreads, self.back_samples(disc, cup))
         finally:
             for n, mode in zip(self.nets, modes):
                 n.train(mode)
@@ -296,6 +374,9 @@ def main(argv=None):
     ap.add_argument("--out", required=True)
     ap.add_argument("--batch-size", type=int, default=9)
     ap.add_argument("--no-overlay", action="store_true", help="write the masks and the table only")
+    ap.add_argument("--samples", type=int, default=0, help="K sampled shape latents per image: uncertainty/ and uncertainty.csv (0: none)")
+    ap.add_argument("--seed", type=int, default=0, help="the noise stream of --samples")
+    ap.add_argument("--sample-scale", type=float, default=1.0, help="multiplies the predicted standard deviation of the latent")
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("wtpse_hip.segment needs the GPU: the networks have no CPU path")
@@ -306,7 +387,8 @@ def main(argv=None):
     torch.cuda.set_device(0)
     nets = build_networks(device)
     load_checkpoint(args.checkpoint, *nets)
-    summary = Segmenter(*nets, out_dir=args.out, batch_size=args.batch_size, overlay=not args.no_overlay).run(folder)
+    summary = Segmenter(*nets, out_dir=args.out, batch_size=args.batch_size, overlay=not args.no_overlay, samples=args.samples,
+                        seed=args.seed, scale=args.sample_scale).run(folder)
     torch.cuda.synchronize()
     print(json.dumps(summary, sort_keys=True))
     return 0

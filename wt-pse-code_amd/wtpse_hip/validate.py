@@ -39,6 +39,31 @@ def predict_pair(model, model_shape, model_oc, model_shape_oc, data, label_size=
     return pred, pred_oc
 
 
+def predict_pair_samples(model, model_shape, model_oc, model_shape_oc, data, n_samples, seed=0, offset=0, scale=1.0, want_logits=False):
+    """predict_pair at the network size plus n_samples sampled predictions of each stage from the same two U-Net passes
+    (WT_PSE.predict_samples).  Stage 1 samples the disc; the ROI is built from the DETERMINISTIC disc logit exactly as predict_pair
+    builds it (a cup U-Net pass per sample is not run); stage 2 samples the cup on that ROI, and the cup's samples are multiplied by
+    od_pred as the deterministic cup logit is (outside it: logit 0, mean 0.5, std 0, no vote).
+    -> (pred, pred_oc, disc, cup): the pair bitwise predict_pair's, disc / cup the uncertainty.ShapeSamples of the two stages.
+
+    Stream layout: both stages draw from the ops.randn stream `seed`.  With N = n_samples * H * W, image b of the batch owns the
+    2 N elements from offset + 2 N b on: the disc's samples take the first N (sample k at + k H W), the cup's the second N.  An
+    image's numbers therefore depend on (seed, offset + 2 N b) alone, not on the batch it is in: a caller that walks a folder
+    passes offset = 2 N * (index of the batch's first image).  offset must be a multiple of 4."""
+    B, _, H, W = data.shape
+    N = int(n_samples) * H * W
+    with torch.no_grad():
+        disc = model.predict_samples(model_shape, data, n_samples, seed, int(offset), scale, None, want_logits, image_stride=2 * N)
+        pred = disc.logit
+        roi, od_pred = ops.roi(data.contiguous(), pred)
+        cup = model_oc.predict_samples(model_shape_oc, torch.stack((roi, roi), 0), n_samples, seed, int(offset) + N, scale, None,
+                                       want_logits, image_stride=2 * N)
+        pred_oc = ops.relu_mask(cup.logit, od_pred)
+        ops.shape_samples_mask_(od_pred, cup.mean, cup.std, cup.votes, cup.logits)
+        cup.logit = pred_oc
+    return pred, pred_oc, disc, cup
+
+
 def largest_fillhole(binary):
     """utils.get_largest_fillhole (utils.py:267-276): keep the largest 8-connected component (skimage.measure.label's
     default connectivity in 2-D), then fill holes."""
