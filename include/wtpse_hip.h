@@ -554,6 +554,21 @@ int wtpse_label_map(const unsigned char* disc, const unsigned char* cup, unsigne
  * 0}.  Integer arithmetic only (64-bit sums): exact, the same on every run, no host synchronisation.  rec 8-byte aligned.
  * 1 <= h, w <= 4096. */
 int wtpse_mask_geometry(const unsigned char* mask, long long* rec, int B, int h, int w, void* stream);
+/* Optic-disc morphometry (csrc/morphometry.hip; morphometry.profile_host is the specification, bit for bit): one pass over a pair of
+ * masks disc, cup [B][h][w] uint8 (nonzero = object) behind wtpse_mask_geometry's records geom [B][8] of the disc, read on the device.
+ * Centre in half-pixel units: c2y = (4 sum_r + area) / (2 area) (integer division: 2 * centroid rounded half up), c2x from sum_c.
+ * A pixel (x, y) has p = (2 x - c2x, c2y - 2 y) (py up the screen), r2 = |p|^2, and lies in the sector s of 0 .. N - 1 with
+ * cross(T[s], p) >= 0 > cross(T[s + 1], p), cross(a, p) = a.x p.y - a.y p.x in 64 bits; p = 0 lies in sector 0.  table [N + 1][2]
+ * int32 = T, the host's (morphometry.sector_table: 2^20 (cos, sin)(2 pi k / N), rounded); sector 0 starts at image-right, sectors run
+ * counter-clockwise on the screen.  No floating point.
+ *   profile [B][N][4] uint32 = {max r2 of the disc's pixels, max r2 of the cup's, disc pixels, cup pixels} per sector (the cup is not
+ *            clipped to the disc); all zero for an image whose disc is empty
+ *   moments [B][2][4] int64: row 0 the disc's {sum y^2, sum x^2, sum x y, c2y}, row 1 the cup's {.., .., .., c2x}; the sums are taken
+ *            for an empty disc too, the centre slots then stay 0
+ * Both are zeroed on the stream first.  Exact and the same on every run; no host synchronisation.  geom, moments 8-byte aligned.
+ * 1 <= B < 8192, 1 <= h, w <= 4096, 8 <= N <= 360 and N % 8 == 0. */
+int wtpse_onh_profile(const unsigned char* disc, const unsigned char* cup, const long long* geom, const int* table, unsigned* profile,
+                      long long* moments, int N, int B, int h, int w, void* stream);
 
 /* ---- sampled shape latents (csrc/uncertainty.hip; uncertainty.shape_samples_host is the fp64 specification) --------------------
  * K draws of the student's latent and everything behind it in one launch.  Per image b, pixel p and sample k:

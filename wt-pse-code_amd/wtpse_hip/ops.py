@@ -1127,3 +1127,39 @@ def mask_geometry(mask):
     rec = torch.empty((B, 8), dtype=torch.int64, device=mask.device)
     lib().call("wtpse_mask_geometry", ptr(mask), ptr(rec), B, h, w, stream_ptr())
     return rec
+
+
+# ----------------------------------------------------------------------------------------------- optic-disc morphometry
+PROFILE_FIELDS = ("disc_r2", "cup_r2", "disc_n", "cup_n")
+_SECTOR_TABLES = {}
+
+
+def onh_profile(disc, cup, geom_disc, N=24):
+    """Two uint8 masks [B,1,h,w] (nonzero = object) and the disc's mask_geometry records [B,8] int64, all on one device ->
+    (profile [B,N,4] int32 holding uint32 bits, fields PROFILE_FIELDS per angular sector around the disc's centroid; moments [B,2,4]
+    int64 = per mask (sum y^2, sum x^2, sum x y, .) with the centre 2 cy / 2 cx in the disc's / the cup's fourth slot).
+    morphometry.profile_host exactly (view the profile as uint32 on the host); morphometry.finish finishes a row.  The sector table
+    (morphometry.sector_table) is kept on the device per (device, N)."""
+    from . import morphometry as M
+    _chk_dev(disc, "disc", torch.uint8)
+    _chk_dev(cup, "cup", torch.uint8)
+    N = M.check_sectors(N)
+    B, _, h, w = disc.shape
+    if disc.shape != cup.shape or disc.device != cup.device:
+        raise ValueError("disc %s and cup %s differ in shape or device" % (tuple(disc.shape), tuple(cup.shape)))
+    g = geom_disc
+    if not (torch.is_tensor(g) and g.is_cuda and g.dtype == torch.int64 and g.is_contiguous() and tuple(g.shape) == (B, 8)
+            and g.device == disc.device):
+        raise ValueError("geom_disc must be the contiguous [%d,8] int64 records of the discs on %s (got %s, %s, %s)"
+                         % (B, disc.device, tuple(g.shape) if torch.is_tensor(g) else type(g), getattr(g, "device", None),
+                            getattr(g, "dtype", None)))
+    if not (1 <= B < 8192 and 1 <= h <= 4096 and 1 <= w <= 4096):
+        raise ValueError("onh_profile: unsupported size %s (B < 8192, 1 <= h, w <= 4096)" % (tuple(disc.shape),))
+    key = (disc.device, N)
+    table = _SECTOR_TABLES.get(key)
+    if table is None:
+        table = _SECTOR_TABLES[key] = torch.from_numpy(M.sector_table(N)).to(disc.device)
+    profile = torch.empty((B, N, 4), dtype=torch.int32, device=disc.device)
+    moments = torch.empty((B, 2, 4), dtype=torch.int64, device=disc.device)
+    lib().call("wtpse_onh_profile", ptr(disc), ptr(cup), ptr(g), ptr(table), ptr(profile), ptr(moments), N, B, h, w, stream_ptr())
+    return profile, moments

@@ -3,6 +3,7 @@ any mix of sizes — through both stages, and per image the segmentation as a la
 cup-to-disc ratios.  The test run (test_run.py) scores a labelled split; this is the path for images that have no label.
 
     python -m wtpse_hip.segment --images DIR --checkpoint C --out O [--batch-size 9] [--no-overlay] [--samples K --seed S --sample-scale X]
+                                [--morphometry [--sectors N] [--eye right|left]]
 
     O/mask/<stem>.png        mode 'L', the image's own size, grey levels 0 (cup) / 128 (disc) / 255 (background): the dataset's
                              label encoding — FundusTree and FundusTestBatches read it as a label
@@ -24,6 +25,17 @@ The per-sample ratios are taken from the samples' masks at the network's 256 x 2
 ratios are scale-free), not at the native size.  The image at folder index i draws its 2 K S^2 normals from position 2 K S^2 i of the
 stream `seed` whatever the batch size (`Segmenter.sample_offsets`), so a folder segmented twice draws the same numbers.
 
+With --morphometry (Segmenter(morphometry=True, sectors=N, eye=E); off, the default, changes nothing and writes none of these) every
+pair of native-size masks also goes through ops.onh_profile (morphometry.py: ellipse fits, the rim width per angular sector, ISNT):
+
+    O/morphometry.csv        morphometry.MORPH_COLUMNS, one row per image
+    O/rim_profile.csv        index, name, rim_000 .. rim_{N-1}: the rim width per sector in pixels at the image's own size
+    O/summary.json           gains sectors, mean_vcdr_ellipse, mean_rim_min_rel and, with --eye, n_isnt_violations
+    O/morphometry_uncertainty.csv   with --samples K as well: morphometry.STAT_COLUMNS and the per-sector spread of the relative rim
+                             width over the K sampled masks (at the network's 256 x 256, like uncertainty.csv)
+
+measurements.csv and CSV_COLUMNS are the same with and without it.
+
 Front (`Segmenter.front`): the decoded uint8 images go to the GPU as they are; the LANCZOS resize to 256 x 256 — FundusTree's
 Image.resize((S, S), Image.LANCZOS), bit for bit — is two passes of wtpse_resample_u8 with `resample_table(..., "lanczos")`, batched
 over the images of one size, a pass whose axis already has the target length skipped as Pillow skips it; wtpse_image_finish
@@ -44,6 +56,7 @@ import os
 import numpy as np
 import torch
 
+from . import morphometry as M
 from . import ops
 from . import uncertainty as U
 from . import validate as V
@@ -177,13 +190,24 @@ def _groups(sizes):
 
 
 # ---- the driver -----------------------------------------------------------------------------------------------------------
+class BackResult:
+    """What Segmenter.back_result returns: per-image lists in the images' order — labels, overlays (entries None without overlay),
+    rows (`measure`), spreads (None unless a spread was passed) and morph (`morphometry.finish` rows; None with morphometry off)."""
+    __slots__ = ("labels", "overlays", "rows", "spreads", "morph")
+
+    def __init__(self, labels, overlays, rows, spreads=None, morph=None):
+        self.labels, self.overlays, self.rows, self.spreads, self.morph = labels, overlays, rows, spreads, morph
+
+
 class Segmenter:
     """run(folder) segments every image of an ImageFolder (or of what ImageFolder takes) in batches of `batch_size` consecutive
     images and writes the files of the module docstring; -> the summary, `self.rows` keeps the table.  Eval mode for the duration, the
     previous modes restored.  front / back are the two halves around validate.predict_pair."""
 
     def __init__(self, model, model_shape, model_oc, model_shape_oc, out_dir, batch_size=9, overlay=True, size=256, samples=0, seed=0,
-                 scale=1.0):
+                 scale=1.0, morphometry=False, sectors=24, eye=None):
+        self.morphometry, self.sectors, self.eye = bool(morphometry), M.check_sectors(sectors), M.check_eye(eye)
+        self.morph_rows, self.morph_sample_rows = [], []
         if int(batch_size) < 1:
             raise ValueError("batch_size must be positive")
         if not 0 <= int(samples) <= 64 or not float(scale) >= 0.0:
@@ -238,12 +262,19 @@ class Segmenter:
         """image [B,3,S,S] (the network input) and the two logit maps [B,1,S,S] on the device, sizes = [(h, w)] per image ->
         (label maps [h,w] uint8, overlays [h,w,3] uint8 or None, rows = `measure` dicts), lists in the images' order.
         spread = (std_disc, std_cup) [B,1,S,S] fp32: resized to the native sizes like the logits, they ride in each size group's copy
-        and come back as a fourth list of [2,h,w] fp32 arrays."""
+        and come back as a fourth list of [2,h,w] fp32 arrays.  The first fields of `back_result`, whatever the switches."""
+        r = self.back_result(image, logits_od, logits_oc, sizes, spread)
+        return (r.labels, r.overlays, r.rows) if spread is None else (r.labels, r.overlays, r.rows, r.spreads)
+
+    def back_result(self, image, logits_od, logits_oc, sizes, spread=None):
+        """`back` as one BackResult: labels, overlays, rows, spreads (None without `spread`) and morph — with morphometry on,
+        ops.onh_profile runs on each size group's masks, its two records ride in the group's one copy, and morph is the list of the
+        images' `morphometry.finish` rows; None when it is off."""
         B, S = image.shape[0], self.size
         if len(sizes) != B or tuple(logits_od.shape) != (B, 1, S, S) or tuple(logits_oc.shape) != (B, 1, S, S):
             raise ValueError("back: %d sizes, logits %s / %s for an image batch %s"
                              % (len(sizes), tuple(logits_od.shape), tuple(logits_oc.shape), tuple(image.shape)))
-        labels, overlays, rows, spreads = [None] * B, [None] * B, [None] * B, [None] * B
+        labels, overlays, rows, spreads, morph = [None] * B, [None] * B, [None] * B, [None] * B, [None] * B
         groups = _groups(sizes)
         for (h, w), idx in groups.items():
             n = len(idx)
@@ -260,13 +291,16 @@ class Segmenter:
                 lod, loc = ops.resize_bilinear(lod, (h, w)), ops.resize_bilinear(loc, (h, w))
             masks = ops.postprocess_masks(torch.cat((lod, loc), 0))
             disc, cup = masks[:n], masks[n:]
-            blob = [ops.mask_geometry(masks).view(torch.uint8).reshape(-1), ops.label_map(disc, cup).reshape(-1)]
+            geom = ops.mask_geometry(masks)
+            blob = [geom.view(torch.uint8).reshape(-1), ops.label_map(disc, cup).reshape(-1)]
             if self.overlay:
                 if (h, w) != (S, S):
                     img = ops.resize_bilinear(img, (h, w))              # the test run's picture (test_visulization.py:231-232)
                 blob.append(ops.overlay(img, disc, cup, None, None)[1].reshape(-1))
             if spread is not None:
                 blob.append(sp.contiguous().view(torch.uint8).reshape(-1))
+            if self.morphometry:
+                blob.extend(t.view(torch.uint8).reshape(-1) for t in ops.onh_profile(disc, cup, geom[:n], self.sectors))
             host = torch.cat(blob).cpu().numpy()                       # the one copy
             rec = host[:2 * n * 64].view(np.int64).reshape(2 * n, 8)
             off = 2 * n * 64
@@ -275,44 +309,70 @@ class Segmenter:
             ov = host[off:off + n * h * w * 3].reshape(n, h, w, 3) if self.overlay else None
             off += n * h * w * 3 if self.overlay else 0
             sm = host[off:off + 8 * n * h * w].copy().view(np.float32).reshape(2, n, h, w) if spread is not None else None
+            off += 8 * n * h * w if spread is not None else 0
+            if self.morphometry:
+                N = self.sectors
+                prof = host[off:off + 16 * n * N].copy().view(np.uint32).reshape(n, N, 4)
+                mom = host[off + 16 * n * N:off + 16 * n * N + 64 * n].copy().view(np.int64).reshape(n, 2, 4)
+                mrows = M.finish_batch(rec, mom, prof, h, w, self.eye)
             for j, i in enumerate(idx):
                 labels[i], rows[i] = lm[j], measure(rec[j], rec[n + j], h, w)
                 overlays[i] = ov[j] if self.overlay else None
                 spreads[i] = sm[:, j] if spread is not None else None
-        return (labels, overlays, rows) if spread is None else (labels, overlays, rows, spreads)
+                morph[i] = mrows[j] if self.morphometry else None
+        return BackResult(labels, overlays, rows, spreads if spread is not None else None, morph if self.morphometry else None)
 
     def back_samples(self, disc, cup):
         """The uncertainty.ShapeSamples of the two stages (with their [B,K,S,S] logits) -> per image the uncertainty.csv row without
         index and name.  Both classes' B K sampled logit maps go through ops.postprocess_masks and ops.mask_geometry at the network
         size in one set of launches; the records, the vote maps and the spread maps come back in one copy; `measure` per sample and
         the statistics (uncertainty.ratio_statistics / map_statistics) are the host's."""
+        return self.back_samples_result(disc, cup)[0]
+
+    def back_samples_result(self, disc, cup):
+        """-> (the rows of `back_samples`, morph): with morphometry on, the same 2 B K masks go through ops.onh_profile, its records
+        ride in that copy, and morph is per image `morphometry.sample_statistics` of its K samples; None when it is off."""
         B, K, S = disc.logits.shape[0], disc.logits.shape[1], self.size
         masks = ops.postprocess_masks(torch.cat((disc.logits.reshape(B * K, 1, S, S), cup.logits.reshape(B * K, 1, S, S)), 0))
-        blob = [ops.mask_geometry(masks).view(torch.uint8).reshape(-1), disc.votes.reshape(-1), cup.votes.reshape(-1),
+        geom = ops.mask_geometry(masks)
+        blob = [geom.view(torch.uint8).reshape(-1), disc.votes.reshape(-1), cup.votes.reshape(-1),
                 torch.cat((disc.std, cup.std), 0).view(torch.uint8).reshape(-1)]
+        if self.morphometry:
+            blob.extend(t.view(torch.uint8).reshape(-1) for t in ops.onh_profile(masks[:B * K], masks[B * K:], geom[:B * K], self.sectors))
         host = torch.cat(blob).cpu().numpy()
         n = 2 * B * K * 64
         rec = host[:n].view(np.int64).reshape(2, B, K, 8)
         votes = host[n:n + 2 * B * S * S].reshape(2, B, S, S)
-        std = host[n + 2 * B * S * S:].copy().view(np.float32).reshape(2, B, S, S)
+        end = n + 10 * B * S * S
+        std = host[n + 2 * B * S * S:end].copy().view(np.float32).reshape(2, B, S, S)
         rows = []
         for b in range(B):
             row = U.ratio_statistics([measure(rec[0, b, k], rec[1, b, k], S, S) for k in range(K)])
             for c, name in enumerate(("disc", "cup")):
                 row[name + "_disagree_px"], row[name + "_std_mean"] = U.map_statistics(votes[c, b], std[c, b], K)
             rows.append(row)
-        return rows
+        if not self.morphometry:
+            return rows, None
+        N = self.sectors
+        prof = host[end:end + 16 * B * K * N].copy().view(np.uint32).reshape(B, K, N, 4)
+        mom = host[end + 16 * B * K * N:].copy().view(np.int64).reshape(B, K, 2, 4)
+        return rows, [M.sample_statistics([M.finish(rec[0, b, k], rec[1, b, k], mom[b, k], prof[b, k], S, S, self.eye) for k in range(K)])
+                      for b in range(B)]
 
-    def write_samples(self, names, spreads, rows):
-        """One batch of sampled results -> O/uncertainty under `names`; the rows join `self.sample_rows` with their index and name."""
+    def write_samples(self, names, spreads, rows, morph=None):
+        """One batch of sampled results -> O/uncertainty under `names`; the rows join `self.sample_rows` with their index and name (the
+        morphometry statistics, when given, `self.morph_sample_rows`)."""
         from PIL import Image
         os.makedirs(os.path.join(self.out_dir, "uncertainty"), exist_ok=True)
         for name, sp, row in zip(names, spreads, rows):
             Image.fromarray(U.std_picture(sp[0], sp[1])).save(os.path.join(self.out_dir, "uncertainty", name))
             self.sample_rows.append(dict(row, index=len(self.sample_rows) + 1, name=name))
+        for name, row in zip(names, morph or ()):
+            self.morph_sample_rows.append(dict(row, index=len(self.morph_sample_rows) + 1, name=name))
 
-    def write(self, names, labels, overlays, rows):
-        """One batch of `back` results -> O/mask and O/overlay under `names`; the rows join `self.rows` with their index and name."""
+    def write(self, names, labels, overlays, rows, morph=None):
+        """One batch of `back` results -> O/mask and O/overlay under `names`; the rows join `self.rows` with their index and name (the
+        morphometry rows, when given, `self.morph_rows`)."""
         from PIL import Image
         for sub in ("mask",) + (("overlay",) if self.overlay else ()):
             os.makedirs(os.path.join(self.out_dir, sub), exist_ok=True)
@@ -321,6 +381,8 @@ class Segmenter:
             if ov is not None:
                 Image.fromarray(ov).save(os.path.join(self.out_dir, "overlay", name))
             self.rows.append(dict(row, index=len(self.rows) + 1, name=name))
+        for name, row in zip(names, morph or ()):
+            self.morph_rows.append(dict(row, index=len(self.morph_rows) + 1, name=name))
 
     def finish(self):
         """-> the summary of `self.rows`, written with them (measurements.csv, summary.json)."""
@@ -328,9 +390,15 @@ class Segmenter:
         if self.samples:
             vals = [r["vcdr_std"] for r in self.sample_rows if r["vcdr_std"] == r["vcdr_std"]]
             summary.update(n_samples=self.samples, mean_vcdr_std=float(np.mean(np.array(vals, np.float64))) if vals else None)
+        if self.morphometry:
+            summary.update(M.summarise(self.morph_rows, self.eye), sectors=self.sectors)
         write_measurements(self.out_dir, self.rows, summary)
         if self.samples:
             U.write_csv(self.out_dir, self.sample_rows)
+        if self.morphometry:
+            M.write_csv(self.out_dir, self.morph_rows)
+            if self.samples:
+                M.write_uncertainty_csv(self.out_dir, self.morph_sample_rows)
         return summary
 
     def run(self, folder):
@@ -341,6 +409,7 @@ class Segmenter:
         for n in self.nets:
             n.eval()
         self.rows, self.sample_rows, self.sample_offsets = [], [], []
+        self.morph_rows, self.morph_sample_rows = [], []
         per_image = 2 * self.samples * self.size * self.size          # an image's share of the noise stream (predict_pair_samples)
         try:
             for first in range(0, len(folder), self.batch_size):
@@ -350,14 +419,15 @@ class Segmenter:
                 names, sizes = [folder.names[i] for i in idx], [im.shape[:2] for im in images]
                 if not self.samples:
                     pred, pred_oc = V.predict_pair(*self.nets, image)
-                    self.write(names, *self.back(image, pred, pred_oc, sizes))
+                    r = self.back_result(image, pred, pred_oc, sizes)
+                    self.write(names, r.labels, r.overlays, r.rows, r.morph)
                     continue
                 pred, pred_oc, disc, cup = V.predict_pair_samples(*self.nets, image, self.samples, self.seed, first * per_image, self.scale,
                                                                   want_logits=True)
                 self.sample_offsets += [i * per_image for i in idx]
-                labels, overlays, rows, spreads = self.back(image, pred, pred_oc, sizes, (disc.std, cup.std))
-                self.write(names, labels, overlays, rows)
-                self.write_samples(names, spreads, self.back_samples(disc, cup))
+                r = self.back_result(image, pred, pred_oc, sizes, (disc.std, cup.std))
+                self.write(names, r.labels, r.overlays, r.rows, r.morph)
+                self.write_samples(names, r.spreads, *self.back_samples_result(disc, cup))
         finally:
             for n, mode in zip(self.nets, modes):
                 n.train(mode)
@@ -377,7 +447,11 @@ def main(argv=None):
     ap.add_argument("--samples", type=int, default=0, help="K sampled shape latents per image: uncertainty/ and uncertainty.csv (0: none)")
     ap.add_argument("--seed", type=int, default=0, help="the noise stream of --samples")
     ap.add_argument("--sample-scale", type=float, default=1.0, help="multiplies the predicted standard deviation of the latent")
+    ap.add_argument("--morphometry", action="store_true", help="ellipse fits, rim profile and ISNT: morphometry.csv, rim_profile.csv")
+    ap.add_argument("--sectors", type=int, default=24, help="angular sectors of the rim profile: a multiple of 8 in 8..360")
+    ap.add_argument("--eye", choices=("right", "left"), default=None, help="which eye the crops show: fills nasal / temporal / isnt")
     args = ap.parse_args(argv)
+    M.check_sectors(args.sectors)
     if not torch.cuda.is_available():
         raise SystemExit("wtpse_hip.segment needs the GPU: the networks have no CPU path")
     folder = ImageFolder(args.images)
@@ -388,7 +462,8 @@ def main(argv=None):
     nets = build_networks(device)
     load_checkpoint(args.checkpoint, *nets)
     summary = Segmenter(*nets, out_dir=args.out, batch_size=args.batch_size, overlay=not args.no_overlay, samples=args.samples,
-                        seed=args.seed, scale=args.sample_scale).run(folder)
+                        seed=args.seed, scale=args.sample_scale, morphometry=args.morphometry, sectors=args.sectors,
+                        eye=args.eye).run(folder)
     torch.cuda.synchronize()
     print(json.dumps(summary, sort_keys=True))
     return 0
