@@ -570,6 +570,29 @@ int wtpse_mask_geometry(const unsigned char* mask, long long* rec, int B, int h,
 int wtpse_onh_profile(const unsigned char* disc, const unsigned char* cup, const long long* geom, const int* table, unsigned* profile,
                       long long* moments, int N, int B, int h, int w, void* stream);
 
+/* ---- calibration against labels (csrc/calibration.hip; calibration.hist_host is the specification, bit for bit) ----------------
+ * One pass over a probability map prob, a spread map spread (NULL: every spread is 0) and a label (nonzero = object, as
+ * wtpse_seg_metrics takes it; y = 1 for an object pixel, else 0), all [B][h][w] fp32, optionally restricted to the pixels where
+ * region [B][h][w] uint8 is nonzero (NULL: every pixel).  rec [B][WTPSE_CAL_REC] uint32, zeroed on the stream first, is per image
+ *   hist_p [WTPSE_CAL_BINS + 1][2], then hist_s [WTPSE_CAL_BINS + 1][2], then tail [4].
+ * Per pixel, in this order:
+ *   region == 0                   tail[0 + y] += 1; the pixel is not scored (its prob and spread are not looked at)
+ *   prob or spread is NaN         tail[2] += 1; the pixel is not scored
+ *   otherwise                     tail[3] += 1 and, with
+ *                                   q = (int)rintf(min(max(prob, 0), 1) * 1024.f)        0 .. 1024 (+-inf clamp like any other value)
+ *                                   u = (int)rintf(min(max(spread, 0), 0.5f) * 2048.f)   0 .. 1024
+ *                                   e = ((prob > threshold) != y)                        the unclamped, unquantised prob
+ *                                 hist_p[q][y] += 1 and hist_s[u][e] += 1
+ * Both products are exact in fp32 (a power of two times a value of at most 1) and rintf rounds half to even: numpy.rint on float32 is
+ * the same function.  Integer arithmetic only — a count is at most h w <= 2^24 — exact and the same on every run; no host
+ * synchronisation; no alignment or width premise beyond the element types' own.  hist_p summed over both columns and hist_s summed over
+ * both columns each total tail[3]; the four tail counts total h w.
+ * 1 <= B < 8192, 1 <= h, w <= 4096. */
+#define WTPSE_CAL_BINS 1024
+#define WTPSE_CAL_REC (2 * (WTPSE_CAL_BINS + 1) * 2 + 4)
+int wtpse_calibration_hist(const float* prob, const float* spread, const float* label, const unsigned char* region, float threshold,
+                           unsigned* rec, int B, int h, int w, void* stream);
+
 /* ---- sampled shape latents (csrc/uncertainty.hip; uncertainty.shape_samples_host is the fp64 specification) --------------------
  * K draws of the student's latent and everything behind it in one launch.  Per image b, pixel p and sample k:
  *   z = mu + scale * exp(logvar / 2) * eps[b,k,p]         (a non-finite exp(logvar / 2) counts as 0, as in the student's sampling)

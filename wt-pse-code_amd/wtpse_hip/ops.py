@@ -1163,3 +1163,30 @@ def onh_profile(disc, cup, geom_disc, N=24):
     moments = torch.empty((B, 2, 4), dtype=torch.int64, device=disc.device)
     lib().call("wtpse_onh_profile", ptr(disc), ptr(cup), ptr(g), ptr(table), ptr(profile), ptr(moments), N, B, h, w, stream_ptr())
     return profile, moments
+
+
+# ----------------------------------------------------------------------------------------------- calibration against labels
+CAL_BINS = 1024
+CAL_REC = 2 * (CAL_BINS + 1) * 2 + 4
+
+
+def calibration_hist(prob, spread, label, region=None, threshold=0.75):
+    """prob, label [B,1,h,w] fp32 (label: nonzero = object), spread the same or None (every spread 0), region [B,1,h,w] uint8 or None
+    (every pixel), all on one device -> records [B, CAL_REC] int32 holding uint32 bits: hist_p [CAL_BINS + 1, 2], hist_s
+    [CAL_BINS + 1, 2], tail [4] (include/wtpse_hip.h).  calibration.hist_host exactly (view the records as uint32 on the host);
+    calibration.split_record names the parts."""
+    _chk_dev(prob, "prob", torch.float32)
+    _chk_dev(label, "label", torch.float32)
+    for t, name, dtype in ((spread, "spread", torch.float32), (region, "region", torch.uint8)):
+        if t is not None:
+            _chk_dev(t, name, dtype)
+    for t, name in ((label, "label"), (spread, "spread"), (region, "region")):
+        if t is not None and (t.shape != prob.shape or t.device != prob.device):
+            raise ValueError("prob %s (%s) and %s %s (%s) differ in shape or device" % (tuple(prob.shape), prob.device, name, tuple(t.shape), t.device))
+    B, _, h, w = prob.shape
+    if not (1 <= B < 8192 and 1 <= h <= 4096 and 1 <= w <= 4096):
+        raise ValueError("calibration_hist: unsupported size %s (B < 8192, 1 <= h, w <= 4096)" % (tuple(prob.shape),))
+    rec = torch.empty((B, CAL_REC), dtype=torch.int32, device=prob.device)
+    lib().call("wtpse_calibration_hist", ptr(prob), ptr(spread) if spread is not None else 0, ptr(label),
+               ptr(region) if region is not None else 0, float(threshold), ptr(rec), B, h, w, stream_ptr())
+    return rec
