@@ -618,6 +618,27 @@ int wtpse_shape_samples(const float* emb, int CE, const float* mu, const float* 
 int wtpse_shape_samples_mask(const float* ref, float* mean, float* std_, unsigned char* votes, float* logits, int K, int B, int HW,
                              void* stream);
 
+/* ---- test-time views (csrc/views.hip; wtpse_hip/views.py holds the definition and views.merge_host, the specification) ----------
+ * A view code c in 0..7 acts on a square plane a as numpy states it: t = a.T if c & 4; rows of t reversed if c & 2; then columns
+ * reversed if c & 1 (0 identity, 1 horizontal flip, 2 vertical flip, 3 half turn, 4..7 the transposing ones).  `codes` is a HOST array
+ * of V ints, read during the call.
+ * x [N][S][S] fp32 planes -> out [V][N][S][S]: plane n of view v is the view codes[v] of x[n], bit for bit (a pure permutation).
+ * 1 <= V <= 8, every code in 0..7, N >= 1, S % 4 == 0 (square planes only: the transposing views need them); x, out 16-byte
+ * aligned and distinct. */
+int wtpse_dihedral_views(const float* x, float* out, const int* codes, int V, int N, int S, void* stream);
+
+/* The fused merge.  logits [V][B][K][S][S]: K logit maps per view and image, each in its view's own frame.  With s = v * K + k:
+ *   logits_out [B][V*K][S][S]  map s = the inverse view of logits[v][b][k] (a pure permutation); NULL: not stored
+ *   mean, std_ [B][S][S]       mean and population standard deviation of the V K values sigmoid(logit_s) of a pixel, by a running
+ *                              Welford update in order of s (equal samples give exactly 0)
+ *   votes [B][S][S] uint8      #{s: sigmoid(logit_s) > threshold}
+ *   mean_logit [B][S][S]       the float32 sum of the un-viewed logits in order of s (starting from the first; one addition each),
+ *                              times 1.f / (float)(V K): bit for bit views.merge_host's; NULL: not stored
+ * One pass, no atomics, results independent of the grid.  1 <= V <= 8, every code in 0..7, K >= 1, V * K <= 64, B >= 1, S % 4 == 0;
+ * logits, logits_out, mean, std_, mean_logit 16-byte aligned, votes 4-byte aligned; no output may overlap the input. */
+int wtpse_views_merge(const float* logits, const int* codes, int V, int B, int K, int S, float threshold, float* logits_out,
+                      float* mean, float* std_, unsigned char* votes, float* mean_logit, void* stream);
+
 /* ---- small utilities ------------------------------------------------------------------------------------------- */
 int wtpse_relu_mask(const float* dz, const float* ref, float* dy, int accumulate, long long n, void* stream);
 int wtpse_axpy(float* dst, const float* src, float alpha, long long n, void* stream);

@@ -2,14 +2,15 @@
 `segment --samples K` can be trusted, per `--sample-scale` (calibration.py holds the arithmetic; this is the driver).
 
     python -m wtpse_hip.calibration_run --data-dir D --datasetTest 3 --checkpoint C --out O
-           [--samples 16] [--scales 0,0.5,1,2] [--bins 16] [--seed 0] [--batch-size 9]
+           [--samples 16] [--scales 0,0.5,1,2] [--bins 16] [--seed 0] [--batch-size 9] [--views none|id|hflip|flips|d4|<codes>]
 
     O/calibration.csv     calibration.CALIBRATION_COLUMNS: one row per scale and structure (disc, cup); the ratio columns
                           (<ratio>_coverage, vcdr_spearman, n_defined) on the cup row, nan (n_defined 0) on the disc row and at scale 0
     O/reliability.csv     scale, structure, bin, lo, hi, n, mean_conf, frac_pos
     O/risk_coverage.csv   scale, structure, level (pixel|image), coverage, risk; no rows at scale 0 (nothing to sort by)
     O/per_image.csv       calibration.PER_IMAGE_COLUMNS: one row per scale and image
-    O/summary.json        n, scales, samples, bins, and per structure the scale with the lowest NLL and the one with the lowest ECE
+    O/summary.json        n, scales, samples, bins, and per structure the scale with the lowest NLL and the one with the lowest ECE;
+                          with --views also views, the code list
 
 Scale 0 is the deterministic row: prob = sigmoid of validate.predict_pair's logits at the label size, no spread (every scored pixel sits
 in spread bin 0; the spread columns are nan), the U-Nets are not sampled.  A scale s > 0 runs validate.predict_pair_samples with
@@ -28,6 +29,12 @@ ops.mask_geometry records of the label masks and of the deterministic post-proce
 label's and the prediction's ratios).  The Dice columns are validate.batch_metrics(..., "device") — what test_run writes; the
 per-sample ratios are Segmenter.back_samples', which keeps its own copy.
 
+With --views (CalibrationRun(views=...); views.parse names the sets; none, the default, changes nothing) both predictions go through
+validate.predict_pair_views: the Dice columns, the cup's region and the ratios come from the merged logits, and EVERY scale is a
+sampled row — at scale 0 each of the V views contributes its deterministic prediction (V samples), at a scale s > 0 its K samples
+(V K samples; the image at index i draws from position 2 V K S^2 i); prob is the mean and spread the standard deviation over the
+merged samples, so scale 0 has spread columns and risk-coverage rows as well.
+
 Image-level numbers on the cup row: <ratio>_coverage = the fraction of images whose label ratio lies inside [p05, p95] of the samples
 (a 5-to-95 interval claims 0.9), n_defined the images where vcdr's three values exist, vcdr_spearman the rank correlation of vcdr_std
 with |vcdr_pred - vcdr_label|.  The image risk-coverage curve keeps the images with the smallest vcdr_std; risk = 1 - mean Dice (of
@@ -42,6 +49,7 @@ import torch
 from . import calibration as C
 from . import ops
 from . import validate as V
+from . import views as VW
 from .segment import Segmenter, measure
 from .test_run import FundusTestBatches, build_networks, load_checkpoint
 
@@ -54,13 +62,17 @@ class CalibrationRun:
     records (uint32 [n, 2, REC]: disc, cup), `self.rows` the per-image table, `self.table` calibration.csv's rows.  Eval mode for the
     duration, the previous modes restored."""
 
-    def __init__(self, model, model_shape, model_oc, model_shape_oc, out_dir, samples=16, scales=(0.0, 0.5, 1.0, 2.0), bins=16, seed=0):
+    def __init__(self, model, model_shape, model_oc, model_shape_oc, out_dir, samples=16, scales=(0.0, 0.5, 1.0, 2.0), bins=16, seed=0,
+                 views=None):
         self.nets = [model, model_shape, model_oc, model_shape_oc]
         self.out_dir, self.samples, self.seed = out_dir, int(samples), int(seed)
         self.scales, self.bins = C.parse_scales(scales), C.check_bins(bins)
         if not 1 <= self.samples <= 64:
             raise ValueError("samples must lie in 1..64 (got %r)" % (samples,))
-        self.records, self.rows, self.table, self._seg = {}, [], [], None
+        self.views = VW.parse(views)
+        if self.views is not None and len(self.views) * self.samples > VW.MAX_MAPS:
+            raise ValueError("views * samples must not exceed %d (got %d x %d)" % (VW.MAX_MAPS, len(self.views), self.samples))
+        self.records, self.rows, self.table, self._seg, self._det = {}, [], [], None, None
 
     def _records(self, prob, spread, label, region, extra=()):
         """One launch for both structures, one copy -> (uint32 [2 B, REC], the extra int64 tensors' host copies)."""
@@ -74,19 +86,33 @@ class CalibrationRun:
         return host[:n].copy().view(np.uint32).reshape(tuple(rec.shape)), out
 
     def predict_pair(self, image):
-        """The deterministic prediction at the network size -> (pred, pred_oc): validate.predict_pair."""
-        return V.predict_pair(*self.nets, image)
+        """The deterministic prediction at the network size -> (pred, pred_oc): validate.predict_pair, or with views the merged pair
+        of validate.predict_pair_views (whose V per-view predictions are kept for scale 0)."""
+        if self.views is None:
+            return V.predict_pair(*self.nets, image)
+        pred, pred_oc, disc, cup = V.predict_pair_views(*self.nets, image, self.views)
+        self._det = (image, disc, cup)
+        return pred, pred_oc
 
     def predict_samples(self, image, scale, first):
         """The sampled prediction of a batch whose first image has index `first` of the run -> (disc, cup), the two stages'
-        uncertainty.ShapeSamples with their logits: validate.predict_pair_samples under the segmenter's offset rule."""
+        uncertainty.ShapeSamples with their logits: validate.predict_pair_samples under the segmenter's offset rule.  With views:
+        validate.predict_pair_views — the V views' deterministic predictions at scale 0, their V K samples otherwise."""
         S = image.shape[2]
+        if self.views is not None:
+            if scale == 0.0:
+                if self._det is not None and self._det[0] is image:
+                    return self._det[1:]
+                return V.predict_pair_views(*self.nets, image, self.views)[2:]
+            per_image = 2 * len(self.views) * self.samples * S * S
+            return V.predict_pair_views(*self.nets, image, self.views, self.samples, self.seed, first * per_image, scale)[2:]
         per_image = 2 * self.samples * S * S                         # an image's share of the noise stream
         return V.predict_pair_samples(*self.nets, image, self.samples, self.seed, first * per_image, scale, want_logits=True)[2:]
 
     def _segmenter(self, B, S):
         if self._seg is None or self._seg.batch_size != B or self._seg.size != S:
-            self._seg = Segmenter(*self.nets, out_dir=self.out_dir, batch_size=B, size=S, samples=self.samples, seed=self.seed)
+            self._seg = Segmenter(*self.nets, out_dir=self.out_dir, batch_size=B, size=S, samples=self.samples, seed=self.seed,
+                                  views=self.views)
         return self._seg
 
     def batch(self, image, label_od, label_oc, first):
@@ -105,7 +131,7 @@ class CalibrationRun:
         extra = (ops.mask_geometry((label != 0).to(torch.uint8).contiguous()), ops.mask_geometry(ops.postprocess_masks(pair, THRESHOLD)))
         out, det = {}, None
         for scale in self.scales:
-            if scale == 0.0:
+            if scale == 0.0 and self.views is None:
                 prob, spread, stats = torch.sigmoid(pair), None, None
             else:
                 disc, cup = self.predict_samples(image, scale, first)
@@ -147,7 +173,7 @@ class CalibrationRun:
                 row = {"scale": scale, "structure": name, "n_scored": int(tail[3]), "n_excluded_neg": int(tail[0]),
                        "n_excluded_pos": int(tail[1]), "n_invalid": int(tail[2]), "error_rate": sp["error_rate"]}
                 row.update({k: sc[k] for k in ("ece", "mce", "brier", "nll", "auroc")})
-                sampled = scale != 0.0
+                sampled = scale != 0.0 or self.views is not None
                 row.update({k: sp[k] if sampled else C.NAN for k in ("spread_wrong_mean", "spread_right_mean", "spread_auroc")})
                 row.update({r + "_coverage": C.NAN for r in C.RATIOS}, vcdr_spearman=C.NAN, n_defined=0)
                 if sampled and name == "cup":
@@ -166,6 +192,8 @@ class CalibrationRun:
                                 for c, v in C.image_risk_coverage([r["vcdr_std"] for r in rows], [r[name + "_dice"] for r in rows]))
         self.table = table
         summary = {"n": len(self.rows) // max(len(self.scales), 1), "scales": list(self.scales), "samples": self.samples, "bins": self.bins}
+        if self.views is not None:
+            summary["views"] = list(self.views)
         summary.update(C.best_scales(table))
         C.write_csv(self.out_dir, "calibration", table)
         C.write_csv(self.out_dir, "reliability", rel)
@@ -193,6 +221,7 @@ class CalibrationRun:
         finally:
             for n, mode in zip(self.nets, modes):
                 n.train(mode)
+        self._det = None
         self.rows = [r for s in self.scales for r in per_scale[s]]
         self.records = {s: np.stack(recs[s]) if recs[s] else np.zeros((0, 2, C.REC), np.uint32) for s in self.scales}
         return self.finish()
@@ -213,11 +242,15 @@ def parse_args(argv=None):
     ap.add_argument("--bins", type=int, default=16, help="reliability bins: a divisor of 1024")
     ap.add_argument("--seed", type=int, default=0, help="the noise stream of the samples")
     ap.add_argument("--batch-size", type=int, default=9)
+    ap.add_argument("--views", default="none", help="test-time views to merge: none, id, hflip, flips, d4 or a comma list of codes 0..7 (0 first)")
     args = ap.parse_args(argv)
     try:
         args.scales, args.bins = C.parse_scales(args.scales), C.check_bins(args.bins)
         if not 1 <= args.samples <= 64:
             raise ValueError("--samples must lie in 1..64 (got %d)" % args.samples)
+        args.views = VW.parse(args.views)
+        if args.views is not None and len(args.views) * args.samples > VW.MAX_MAPS:
+            raise ValueError("--views times --samples must not exceed %d (got %d x %d)" % (VW.MAX_MAPS, len(args.views), args.samples))
     except ValueError as e:
         ap.error(str(e))
     return args
@@ -235,7 +268,7 @@ def main(argv=None):
     tree = FundusTree(args.data_dir, phase="test", splitid=(args.datasetTest,), state="prediction")
     if len(tree) < 1:
         raise SystemExit("no test images under %s" % os.path.join(args.data_dir, "Domain%d" % args.datasetTest, "test"))
-    run = CalibrationRun(*nets, out_dir=args.out, samples=args.samples, scales=args.scales, bins=args.bins, seed=args.seed)
+    run = CalibrationRun(*nets, out_dir=args.out, samples=args.samples, scales=args.scales, bins=args.bins, seed=args.seed, views=args.views)
     summary = run.run(FundusTestBatches(tree, args.batch_size, device))
     torch.cuda.synchronize()
     print(json.dumps(summary, sort_keys=True))

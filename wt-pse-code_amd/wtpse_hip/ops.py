@@ -1190,3 +1190,54 @@ def calibration_hist(prob, spread, label, region=None, threshold=0.75):
     lib().call("wtpse_calibration_hist", ptr(prob), ptr(spread) if spread is not None else 0, ptr(label),
                ptr(region) if region is not None else 0, float(threshold), ptr(rec), B, h, w, stream_ptr())
     return rec
+
+
+# ----------------------------------------------------------------------------------------------- test-time views
+_VIEW_CODES = {}
+
+
+def _view_codes(codes):
+    """The host int array wtpse_dihedral_views / wtpse_views_merge read their codes from, kept per code tuple (a recorded launch
+    plan holds the pointer)."""
+    import ctypes
+    key = tuple(int(c) for c in codes)
+    arr = _VIEW_CODES.get(key)
+    if arr is None:
+        arr = _VIEW_CODES[key] = (ctypes.c_int * max(len(key), 1))(*key)
+    return key, ctypes.addressof(arr)
+
+
+def dihedral_views(x, codes):
+    """x [B,C,S,S] -> [V,B,C,S,S]: plane (b, c) of view v is views.view_host(x[b, c], codes[v]), bit for bit (csrc/views.hip).  The
+    result is freshly allocated on every call: amax_of keeps its table on the tensor object it is given, and a reused buffer
+    would hand the U-Nets the x2h scale of an earlier batch."""
+    _chk(x, "x")
+    if x.dim() != 4 or x.shape[2] != x.shape[3]:
+        raise ValueError("dihedral_views: x must be [B,C,S,S] with square planes (got %s)" % (tuple(x.shape),))
+    B, C, S, _ = x.shape
+    key, cptr = _view_codes(codes)
+    out = torch.empty((len(key), B, C, S, S), dtype=torch.float32, device=x.device)
+    lib().call("wtpse_dihedral_views", ptr(x), ptr(out), cptr, len(key), B * C, S, stream_ptr())
+    return out
+
+
+def views_merge(logits, codes, threshold=0.75, want_logits=True, want_mean_logit=True):
+    """logits [V,B,K,S,S], each view's maps in its own frame -> (mean, std [B,1,S,S] fp32, votes [B,1,S,S] uint8, logits
+    [B,V*K,S,S] un-viewed with sample index v*K + k or None, mean_logit [B,1,S,S] or None): one launch (csrc/views.hip;
+    views.merge_host is its specification).  Every output is freshly allocated."""
+    _chk(logits, "logits")
+    if logits.dim() != 5 or logits.shape[3] != logits.shape[4]:
+        raise ValueError("views_merge: logits must be [V,B,K,S,S] with square planes (got %s)" % (tuple(logits.shape),))
+    V, B, K, S, _ = logits.shape
+    key, cptr = _view_codes(codes)
+    if len(key) != V:
+        raise ValueError("views_merge: %d codes for %d views" % (len(key), V))
+    dev = logits.device
+    mean = torch.empty((B, 1, S, S), dtype=torch.float32, device=dev)
+    std = torch.empty((B, 1, S, S), dtype=torch.float32, device=dev)
+    votes = torch.empty((B, 1, S, S), dtype=torch.uint8, device=dev)
+    out = torch.empty((B, V * K, S, S), dtype=torch.float32, device=dev) if want_logits else None
+    mean_logit = torch.empty((B, 1, S, S), dtype=torch.float32, device=dev) if want_mean_logit else None
+    lib().call("wtpse_views_merge", ptr(logits), cptr, V, B, K, S, float(threshold), ptr(out), ptr(mean), ptr(std), ptr(votes),
+               ptr(mean_logit), stream_ptr())
+    return mean, std, votes, out, mean_logit

@@ -3,7 +3,7 @@ any mix of sizes — through both stages, and per image the segmentation as a la
 cup-to-disc ratios.  The test run (test_run.py) scores a labelled split; this is the path for images that have no label.
 
     python -m wtpse_hip.segment --images DIR --checkpoint C --out O [--batch-size 9] [--no-overlay] [--samples K --seed S --sample-scale X]
-                                [--morphometry [--sectors N] [--eye right|left]]
+                                [--morphometry [--sectors N] [--eye right|left]] [--views none|id|hflip|flips|d4|<codes>]
 
     O/mask/<stem>.png        mode 'L', the image's own size, grey levels 0 (cup) / 128 (disc) / 255 (background): the dataset's
                              label encoding — FundusTree and FundusTestBatches read it as a label
@@ -36,6 +36,13 @@ pair of native-size masks also goes through ops.onh_profile (morphometry.py: ell
 
 measurements.csv and CSV_COLUMNS are the same with and without it.
 
+With --views (Segmenter(views=...); views.parse names the sets; none, the default, changes nothing) every image is predicted under V
+flipped / rotated views of itself and the views' predictions, turned back, are merged (validate.predict_pair_views, ops.views_merge):
+the mask, the overlay and measurements.csv come from the merged logits, and uncertainty/ and uncertainty.csv are written as above —
+over the V views' deterministic predictions with --samples 0, over the V K sampled ones otherwise (n_samples in the table and in
+summary.json is the number of maps merged; sample v K + k is sample k of view v).  summary.json gains views, the code list.  The
+image at folder index i draws from position 2 V K S^2 i of the stream; the cost is V passes of both U-Nets.
+
 Front (`Segmenter.front`): the decoded uint8 images go to the GPU as they are; the LANCZOS resize to 256 x 256 — FundusTree's
 Image.resize((S, S), Image.LANCZOS), bit for bit — is two passes of wtpse_resample_u8 with `resample_table(..., "lanczos")`, batched
 over the images of one size, a pass whose axis already has the target length skipped as Pillow skips it; wtpse_image_finish
@@ -60,6 +67,7 @@ from . import morphometry as M
 from . import ops
 from . import uncertainty as U
 from . import validate as V
+from . import views as VW
 from .input_pipeline import DeviceInputPipeline, _dev_i32, resample_table
 
 EXTENSIONS = (".png", ".jpg", ".jpeg", ".bmp", ".tif", ".tiff")
@@ -205,7 +213,7 @@ class Segmenter:
     previous modes restored.  front / back are the two halves around validate.predict_pair."""
 
     def __init__(self, model, model_shape, model_oc, model_shape_oc, out_dir, batch_size=9, overlay=True, size=256, samples=0, seed=0,
-                 scale=1.0, morphometry=False, sectors=24, eye=None):
+                 scale=1.0, morphometry=False, sectors=24, eye=None, views=None):
         self.morphometry, self.sectors, self.eye = bool(morphometry), M.check_sectors(sectors), M.check_eye(eye)
         self.morph_rows, self.morph_sample_rows = [], []
         if int(batch_size) < 1:
@@ -214,7 +222,16 @@ class Segmenter:
             raise ValueError("samples must lie in 0..64 and scale must not be negative (got %r, %r)" % (samples, scale))
         if 2 * int(batch_size) * int(samples) >= 8192:
             raise ValueError("batch_size * samples must stay below 4096 (one set of post-processing launches per batch)")
+        self.views = VW.parse(views)
+        if self.views is not None:
+            n_views = len(self.views)
+            if n_views * int(samples) > VW.MAX_MAPS:
+                raise ValueError("views * samples must not exceed %d (got %d x %d)" % (VW.MAX_MAPS, n_views, int(samples)))
+            if 2 * int(batch_size) * n_views * max(int(samples), 1) >= 8192:
+                raise ValueError("batch_size * views * max(samples, 1) must stay below 4096 (one set of post-processing launches per batch)")
         self.samples, self.seed, self.scale = int(samples), int(seed), float(scale)
+        # the maps behind uncertainty.csv: the K samples, or with views the V views' predictions (samples = 0) / the V K samples
+        self.n_maps = self.samples if self.views is None else len(self.views) * max(self.samples, 1)
         self.sample_rows, self.sample_offsets = [], []
         self.nets = [model, model_shape, model_oc, model_shape_oc]
         self.out_dir, self.batch_size, self.overlay, self.size = out_dir, int(batch_size), bool(overlay), int(size)
@@ -387,17 +404,19 @@ class Segmenter:
     def finish(self):
         """-> the summary of `self.rows`, written with them (measurements.csv, summary.json)."""
         summary = summarise(self.rows)
-        if self.samples:
+        if self.n_maps:
             vals = [r["vcdr_std"] for r in self.sample_rows if r["vcdr_std"] == r["vcdr_std"]]
-            summary.update(n_samples=self.samples, mean_vcdr_std=float(np.mean(np.array(vals, np.float64))) if vals else None)
+            summary.update(n_samples=self.n_maps, mean_vcdr_std=float(np.mean(np.array(vals, np.float64))) if vals else None)
+        if self.views is not None:
+            summary.update(views=list(self.views))
         if self.morphometry:
             summary.update(M.summarise(self.morph_rows, self.eye), sectors=self.sectors)
         write_measurements(self.out_dir, self.rows, summary)
-        if self.samples:
+        if self.n_maps:
             U.write_csv(self.out_dir, self.sample_rows)
         if self.morphometry:
             M.write_csv(self.out_dir, self.morph_rows)
-            if self.samples:
+            if self.n_maps:
                 M.write_uncertainty_csv(self.out_dir, self.morph_sample_rows)
         return summary
 
@@ -410,20 +429,25 @@ class Segmenter:
             n.eval()
         self.rows, self.sample_rows, self.sample_offsets = [], [], []
         self.morph_rows, self.morph_sample_rows = [], []
-        per_image = 2 * self.samples * self.size * self.size          # an image's share of the noise stream (predict_pair_samples)
+        # an image's share of the noise stream (predict_pair_samples; with views predict_pair_views: V times as much)
+        per_image = 2 * (len(self.views) if self.views is not None else 1) * self.samples * self.size * self.size
         try:
             for first in range(0, len(folder), self.batch_size):
                 idx = range(first, min(first + self.batch_size, len(folder)))
                 images = [folder.load(i) for i in idx]
                 image = self.front(images, device)
                 names, sizes = [folder.names[i] for i in idx], [im.shape[:2] for im in images]
-                if not self.samples:
+                if not self.n_maps:
                     pred, pred_oc = V.predict_pair(*self.nets, image)
                     r = self.back_result(image, pred, pred_oc, sizes)
                     self.write(names, r.labels, r.overlays, r.rows, r.morph)
                     continue
-                pred, pred_oc, disc, cup = V.predict_pair_samples(*self.nets, image, self.samples, self.seed, first * per_image, self.scale,
-                                                                  want_logits=True)
+                if self.views is not None:
+                    pred, pred_oc, disc, cup = V.predict_pair_views(*self.nets, image, self.views, self.samples, self.seed, first * per_image,
+                                                                    self.scale)
+                else:
+                    pred, pred_oc, disc, cup = V.predict_pair_samples(*self.nets, image, self.samples, self.seed, first * per_image,
+                                                                      self.scale, want_logits=True)
                 self.sample_offsets += [i * per_image for i in idx]
                 r = self.back_result(image, pred, pred_oc, sizes, (disc.std, cup.std))
                 self.write(names, r.labels, r.overlays, r.rows, r.morph)
@@ -450,8 +474,14 @@ def main(argv=None):
     ap.add_argument("--morphometry", action="store_true", help="ellipse fits, rim profile and ISNT: morphometry.csv, rim_profile.csv")
     ap.add_argument("--sectors", type=int, default=24, help="angular sectors of the rim profile: a multiple of 8 in 8..360")
     ap.add_argument("--eye", choices=("right", "left"), default=None, help="which eye the crops show: fills nasal / temporal / isnt")
+    ap.add_argument("--views", default="none", help="test-time views to merge: none, id, hflip, flips, d4 or a comma list of codes 0..7 "
+                                                    "(0 first): uncertainty/ and uncertainty.csv over the views")
     args = ap.parse_args(argv)
     M.check_sectors(args.sectors)
+    try:
+        views = VW.parse(args.views)
+    except ValueError as e:
+        ap.error(str(e))
     if not torch.cuda.is_available():
         raise SystemExit("wtpse_hip.segment needs the GPU: the networks have no CPU path")
     folder = ImageFolder(args.images)
@@ -463,7 +493,7 @@ def main(argv=None):
     load_checkpoint(args.checkpoint, *nets)
     summary = Segmenter(*nets, out_dir=args.out, batch_size=args.batch_size, overlay=not args.no_overlay, samples=args.samples,
                         seed=args.seed, scale=args.sample_scale, morphometry=args.morphometry, sectors=args.sectors,
-                        eye=args.eye).run(folder)
+                        eye=args.eye, views=views).run(folder)
     torch.cuda.synchronize()
     print(json.dumps(summary, sort_keys=True))
     return 0

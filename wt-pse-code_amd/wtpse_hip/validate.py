@@ -39,7 +39,8 @@ def predict_pair(model, model_shape, model_oc, model_shape_oc, data, label_size=
     return pred, pred_oc
 
 
-def predict_pair_samples(model, model_shape, model_oc, model_shape_oc, data, n_samples, seed=0, offset=0, scale=1.0, want_logits=False):
+def predict_pair_samples(model, model_shape, model_oc, model_shape_oc, data, n_samples, seed=0, offset=0, scale=1.0, want_logits=False,
+                         image_stride=None):
     """predict_pair at the network size plus n_samples sampled predictions of each stage from the same two U-Net passes
     (WT_PSE.predict_samples).  Stage 1 samples the disc; the ROI is built from the DETERMINISTIC disc logit exactly as predict_pair
     builds it (a cup U-Net pass per sample is not run); stage 2 samples the cup on that ROI, and the cup's samples are multiplied by
@@ -49,15 +50,72 @@ def predict_pair_samples(model, model_shape, model_oc, model_shape_oc, data, n_s
     Stream layout: both stages draw from the ops.randn stream `seed`.  With N = n_samples * H * W, image b of the batch owns the
     2 N elements from offset + 2 N b on: the disc's samples take the first N (sample k at + k H W), the cup's the second N.  An
     image's numbers therefore depend on (seed, offset + 2 N b) alone, not on the batch it is in: a caller that walks a folder
-    passes offset = 2 N * (index of the batch's first image).  offset must be a multiple of 4."""
+    passes offset = 2 N * (index of the batch's first image).  offset must be a multiple of 4.
+    image_stride (elements; None: the 2 N above): image b owns the 2 N elements from offset + image_stride * b on instead — for a
+    caller that interleaves several draws per image in one stream (predict_pair_views)."""
     B, _, H, W = data.shape
     N = int(n_samples) * H * W
+    stride = 2 * N if image_stride is None else int(image_stride)
     with torch.no_grad():
-        disc = model.predict_samples(model_shape, data, n_samples, seed, int(offset), scale, None, want_logits, image_stride=2 * N)
+        disc = model.predict_samples(model_shape, data, n_samples, seed, int(offset), scale, None, want_logits, image_stride=stride)
         pred = disc.logit
         roi, od_pred = ops.roi(data.contiguous(), pred)
         cup = model_oc.predict_samples(model_shape_oc, torch.stack((roi, roi), 0), n_samples, seed, int(offset) + N, scale, None,
-                                       want_logits, image_stride=2 * N)
+                                       want_logits, image_stride=stride)
+        pred_oc = ops.relu_mask(cup.logit, od_pred)
+        ops.shape_samples_mask_(od_pred, cup.mean, cup.std, cup.votes, cup.logits)
+        cup.logit = pred_oc
+    return pred, pred_oc, disc, cup
+
+
+def predict_pair_views(model, model_shape, model_oc, model_shape_oc, data, views, n_samples=0, seed=0, offset=0, scale=1.0):
+    """predict_pair under test-time views (views.py): `views` is what views.parse takes and not None — V codes, 0 first.  The V views
+    of `data` come from one ops.dihedral_views launch (view 0 is `data` itself); each view runs through predict_pair (n_samples = 0)
+    or predict_pair_samples as a call of its own, with its own ROI and its cup masked by its own od_pred — so the identity view is
+    predict_pair bit for bit — and one ops.views_merge per structure turns the maps back and merges them.
+    -> (pred, pred_oc, disc, cup) like predict_pair_samples: pred / pred_oc are the float32 means of the views' un-viewed deterministic
+    logits (views.merge_host's mean_logit); disc / cup are uncertainty.ShapeSamples with their logits [B,n,S,S], n = V maps (the
+    views' deterministic logits; sample v) when n_samples = 0 and n = V K maps (sample v K + k) when n_samples = K > 0; .logit is
+    pred / pred_oc, .pre None.  The merged cup is restricted to the merged disc as predict_pair restricts it: od_pred from the merged
+    disc logit (ops.roi), outside it logit 0, mean 0.5, std 0, no vote.
+
+    Stream layout (n_samples = K > 0): with N = K S S, image b owns the 2 V N elements from offset + 2 V N b on; inside them view v
+    owns the 2 N from + 2 N v on, disc first and cup second as in predict_pair_samples.  A caller that walks a folder passes
+    offset = 2 V N * (index of the batch's first image): an image's draws depend on (seed, its index) alone."""
+    from . import views as VW
+    from .uncertainty import ShapeSamples
+    codes = VW.parse(views)
+    if codes is None:
+        raise ValueError("predict_pair_views needs at least the identity view; without views call predict_pair / predict_pair_samples")
+    V, K = len(codes), int(n_samples)
+    B, _, H, W = data.shape
+    if H != W or K < 0 or V * K > VW.MAX_MAPS:
+        raise ValueError("predict_pair_views: square inputs and views * n_samples <= %d (got %s, %d x %d)" % (VW.MAX_MAPS, tuple(data.shape), V, K))
+    N = K * H * W
+    with torch.no_grad():
+        planes = ops.dihedral_views(data.contiguous(), codes)
+        det, det_oc, smp, smp_oc = [], [], [], []
+        for v in range(V):
+            x = data if v == 0 else planes[v]
+            if K == 0:
+                p, p_oc = predict_pair(model, model_shape, model_oc, model_shape_oc, x)
+            else:
+                p, p_oc, d, c = predict_pair_samples(model, model_shape, model_oc, model_shape_oc, x, K, seed, int(offset) + 2 * N * v, scale,
+                                                     want_logits=True, image_stride=2 * V * N)
+                smp.append(d.logits)
+                smp_oc.append(c.logits)
+            det.append(p)
+            det_oc.append(p_oc)
+        out = []
+        for logits, sampled in ((det, smp), (det_oc, smp_oc)):
+            mean, std, votes, maps, merged = ops.views_merge(torch.stack(logits, 0), codes, 0.75, K == 0, True)
+            if K:
+                mean, std, votes, maps, _ = ops.views_merge(torch.stack(sampled, 0), codes, 0.75, True, False)
+            out.append(ShapeSamples(mean=mean, std=std, votes=votes, logits=maps, logit=merged, pre=None, n_samples=V * max(K, 1),
+                                    seed=int(seed), offset=int(offset), scale=float(scale)))
+        disc, cup = out
+        pred = disc.logit
+        od_pred = ops.roi(data.contiguous(), pred)[1]
         pred_oc = ops.relu_mask(cup.logit, od_pred)
         ops.shape_samples_mask_(od_pred, cup.mean, cup.std, cup.votes, cup.logits)
         cup.logit = pred_oc
