@@ -570,6 +570,24 @@ int wtpse_mask_geometry(const unsigned char* mask, long long* rec, int B, int h,
 int wtpse_onh_profile(const unsigned char* disc, const unsigned char* cup, const long long* geom, const int* table, unsigned* profile,
                       long long* moments, int N, int B, int h, int w, void* stream);
 
+/* ---- whole fundus photographs (csrc/locate.hip; wtpse_hip/locate.py holds the host specifications, bit for bit) -------------------
+ * The one pass over the full-size pictures.  img [N][H][W][3] uint8 (interleaved RGB, any base alignment) -> cells [N][CH][CW][2]
+ * int64, CH = ceil(H / c), CW = ceil(W / c): per c x c cell, over its pixels that lie inside the picture and have max(R, G, B) >= t,
+ *   {n = their count, s = the sum of 77 R + 150 G + 29 B over them}   (locate.cells_host)
+ * (a full 256 x 256 cell of white pixels gives s = 2^32 - 2^24: the sums are 64-bit).  Integer arithmetic only, every cell is written by
+ * exactly one workgroup with a plain store: exact, the same on every run, nothing to zero first, no host synchronisation.  Nothing
+ * outside the 16-byte-aligned hull of img is read.  1 <= N <= 65535, 1 <= H, W <= 65536, 2 <= c <= 256, 0 <= t <= 255; cells 8-byte
+ * aligned. */
+int wtpse_locate_cells(const unsigned char* img, long long* cells, int N, int H, int W, int c, int t, void* stream);
+/* M square boxes of side s out of one picture img [H][W][C] uint8 (C = 1 or 3): out [M][s][s][C], out[m][y][x] = img[top_m + y][left_m + x]
+ * where that lies inside the picture, else 0 (a box may lie partly or wholly outside); boxes [M][2] int32 = (top, left) in DEVICE memory.
+ * A pure copy (locate.crop_host).  1 <= H, W <= 65536, 1 <= M <= 65535, 1 <= s <= 8192; img and out distinct. */
+int wtpse_crop_u8(const unsigned char* img, const int* boxes, unsigned char* out, int H, int W, int C, int M, int s, void* stream);
+/* canvas [H][W][C] uint8 (C = 1 or 3), in place: canvas[top + y][left + x] = patch[y][x] for the pixels of patch [h][w][C] that land
+ * inside the canvas (clipped at all four borders; a patch wholly outside launches nothing).  A pure copy (locate.paste_host).
+ * 1 <= H, W, h, w <= 65536, |top|, |left| <= 2^24; canvas and patch distinct. */
+int wtpse_paste_u8(unsigned char* canvas, const unsigned char* patch, int H, int W, int C, int h, int w, int top, int left, void* stream);
+
 /* ---- calibration against labels (csrc/calibration.hip; calibration.hist_host is the specification, bit for bit) ----------------
  * One pass over a probability map prob, a spread map spread (NULL: every spread is 0) and a label (nonzero = object, as
  * wtpse_seg_metrics takes it; y = 1 for an object pixel, else 0), all [B][h][w] fp32, optionally restricted to the pixels where

@@ -1241,3 +1241,60 @@ def views_merge(logits, codes, threshold=0.75, want_logits=True, want_mean_logit
     lib().call("wtpse_views_merge", ptr(logits), cptr, V, B, K, S, float(threshold), ptr(out), ptr(mean), ptr(std), ptr(votes),
                ptr(mean_logit), stream_ptr())
     return mean, std, votes, out, mean_logit
+
+
+# ----------------------------------------------------------------------------------------------- whole fundus photographs
+def _chk_u8(t, name, dims):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and t.dim() == dims):
+        raise ValueError("%s must be a contiguous %d-d uint8 tensor in device memory (got %s)"
+                         % (name, dims, (tuple(t.shape), t.device, t.dtype, t.is_contiguous()) if isinstance(t, torch.Tensor) else type(t)))
+
+
+def locate_cells(img, c, t):
+    """[N,H,W,3] uint8 on the device -> int64 [N, ceil(H/c), ceil(W/c), 2] = per c x c cell (n, s) over its pixels with
+    max(R,G,B) >= t: their count and the sum of 77 R + 150 G + 29 B (csrc/locate.hip; locate.cells_host bit for bit)."""
+    _chk_u8(img, "img", 4)
+    N, H, W, C = img.shape
+    c, t = int(c), int(t)
+    if C != 3 or not (1 <= N <= 65535 and 1 <= H <= 65536 and 1 <= W <= 65536):
+        raise ValueError("locate_cells: img must be [N,H,W,3] with 1 <= H, W <= 65536 (got %s)" % (tuple(img.shape),))
+    if not 2 <= c <= 256 or not 0 <= t <= 255:
+        raise ValueError("locate_cells: the cell side must lie in 2..256 and the threshold in 0..255 (got %r, %r)" % (c, t))
+    out = torch.empty((N, -(-H // c), -(-W // c), 2), dtype=torch.int64, device=img.device)
+    lib().call("wtpse_locate_cells", ptr(img), ptr(out), N, H, W, c, t, stream_ptr())
+    return out
+
+
+def crop_u8(img, boxes, side):
+    """One [H,W,C] uint8 picture (C = 1 or 3) and boxes [M,2] int32 = (top, left), both on the device -> [M,side,side,C]: the boxes'
+    pixels, 0 beyond the picture's borders (locate.crop_host bit for bit)."""
+    _chk_u8(img, "img", 3)
+    H, W, C = img.shape
+    side = int(side)
+    if not (boxes.is_cuda and boxes.device == img.device and boxes.dtype == torch.int32 and boxes.is_contiguous() and boxes.dim() == 2
+            and boxes.shape[1] == 2 and 1 <= boxes.shape[0] <= 65535):
+        raise ValueError("crop_u8: boxes must be a contiguous [M,2] int32 tensor on img's device (got %s, %s, %s)"
+                         % (tuple(boxes.shape), boxes.device, boxes.dtype))
+    if C not in (1, 3) or not (1 <= H <= 65536 and 1 <= W <= 65536 and 1 <= side <= 8192):
+        raise ValueError("crop_u8: img must be [H,W,1 or 3] with 1 <= H, W <= 65536 and 1 <= side <= 8192 (got %s, %r)" % (tuple(img.shape), side))
+    M = boxes.shape[0]
+    out = torch.empty((M, side, side, C), dtype=torch.uint8, device=img.device)
+    lib().call("wtpse_crop_u8", ptr(img), ptr(boxes), ptr(out), H, W, C, M, side, stream_ptr())
+    return out
+
+
+def paste_u8(canvas, patch, top, left):
+    """canvas [H,W,C] uint8 on the device, IN PLACE: the patch [h,w,C] lands with its corner at (top, left), clipped at the canvas'
+    borders; wholly outside changes nothing (locate.paste_host bit for bit).  -> canvas."""
+    _chk_u8(canvas, "canvas", 3)
+    _chk_u8(patch, "patch", 3)
+    H, W, C = canvas.shape
+    h, w = patch.shape[:2]
+    top, left = int(top), int(left)
+    if C not in (1, 3) or patch.shape[2] != C or patch.device != canvas.device or min(H, W, h, w) < 1 or max(H, W, h, w) > 65536:
+        raise ValueError("paste_u8: canvas %s and patch %s must share C = 1 or 3 and a device, sides in 1..65536"
+                         % (tuple(canvas.shape), tuple(patch.shape)))
+    if max(abs(top), abs(left)) > 1 << 24:
+        raise ValueError("paste_u8: |top|, |left| must not exceed 2^24 (got %r, %r)" % (top, left))
+    lib().call("wtpse_paste_u8", ptr(canvas), ptr(patch), H, W, C, h, w, top, left, stream_ptr())
+    return canvas

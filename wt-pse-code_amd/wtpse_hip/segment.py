@@ -251,20 +251,25 @@ class Segmenter:
 
     def front(self, images, device="cuda"):
         """images: decoded [h,w,3] uint8 arrays of any sizes -> [B,3,S,S] fp32 on the device, in their order: FundusTree's LANCZOS
-        resize, then FundusTestBatches.host_sample's normalisation, bit for bit."""
+        resize, then FundusTestBatches.host_sample's normalisation, bit for bit.  An image may also be a [h,w,3] uint8 tensor that is
+        already on the device (locate.py's crops): it takes the same path without visiting the host."""
         S, dev = self.size, torch.device(device)
         if dev.type != "cuda":
             raise RuntimeError("the segmentation front runs on the GPU only (no CPU fallback)")
         if dev.index is None:
             dev = torch.device("cuda", torch.cuda.current_device())
-        images = [np.ascontiguousarray(im) for im in images]
+        images = [im.contiguous() if isinstance(im, torch.Tensor) else np.ascontiguousarray(im) for im in images]
         for im in images:
-            if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3:
-                raise ValueError("images must be decoded [h,w,3] uint8 arrays (got %s %s)" % (im.shape, im.dtype))
+            on_device = isinstance(im, torch.Tensor)
+            if im.dtype != (torch.uint8 if on_device else np.uint8) or im.ndim != 3 or im.shape[2] != 3 or (on_device and im.device != dev):
+                raise ValueError("images must be decoded [h,w,3] uint8 arrays, or such tensors on %s (got %s %s)" % (dev, tuple(im.shape), im.dtype))
         groups = _groups([im.shape[:2] for im in images])
         small = torch.empty((len(images), S, S, 3), dtype=torch.uint8, device=dev)
         for (H, W), idx in groups.items():
-            t = torch.from_numpy(np.stack([images[i] for i in idx])).to(dev)
+            if any(isinstance(images[i], torch.Tensor) for i in idx):
+                t = torch.stack([images[i] if isinstance(images[i], torch.Tensor) else torch.from_numpy(images[i]).to(dev) for i in idx])
+            else:
+                t = torch.from_numpy(np.stack([images[i] for i in idx])).to(dev)
             if W != S:
                 t = self._lanczos_pass(t, False)
             if H != S:
@@ -459,11 +464,9 @@ class Segmenter:
 
 
 # ---- command line -----------------------------------------------------------------------------------------------------------
-def main(argv=None):
-    import argparse
-    from .test_run import build_networks, load_checkpoint
-    ap = argparse.ArgumentParser(prog="python -m wtpse_hip.segment", description=__doc__.split("\n\n")[0])
-    ap.add_argument("--images", required=True, help="a directory of region-of-interest crops (%s)" % " ".join(EXTENSIONS))
+def add_arguments(ap, images_help=None):
+    """The switches of `python -m wtpse_hip.segment` on an argparse parser (wtpse_hip.locate takes every one of them too)."""
+    ap.add_argument("--images", required=True, help=images_help or "a directory of region-of-interest crops (%s)" % " ".join(EXTENSIONS))
     ap.add_argument("--checkpoint", required=True, help="checkpoint_<epoch>.pth.tar as validate.Validator saves it")
     ap.add_argument("--out", required=True)
     ap.add_argument("--batch-size", type=int, default=9)
@@ -476,12 +479,26 @@ def main(argv=None):
     ap.add_argument("--eye", choices=("right", "left"), default=None, help="which eye the crops show: fills nasal / temporal / isnt")
     ap.add_argument("--views", default="none", help="test-time views to merge: none, id, hflip, flips, d4 or a comma list of codes 0..7 "
                                                     "(0 first): uncertainty/ and uncertainty.csv over the views")
-    args = ap.parse_args(argv)
+
+
+def segmenter_arguments(ap, args):
+    """The parsed switches of `add_arguments` -> Segmenter's keywords (without the networks and out_dir)."""
     M.check_sectors(args.sectors)
     try:
         views = VW.parse(args.views)
     except ValueError as e:
         ap.error(str(e))
+    return dict(batch_size=args.batch_size, overlay=not args.no_overlay, samples=args.samples, seed=args.seed, scale=args.sample_scale,
+                morphometry=args.morphometry, sectors=args.sectors, eye=args.eye, views=views)
+
+
+def main(argv=None):
+    import argparse
+    from .test_run import build_networks, load_checkpoint
+    ap = argparse.ArgumentParser(prog="python -m wtpse_hip.segment", description=__doc__.split("\n\n")[0])
+    add_arguments(ap)
+    args = ap.parse_args(argv)
+    kw = segmenter_arguments(ap, args)
     if not torch.cuda.is_available():
         raise SystemExit("wtpse_hip.segment needs the GPU: the networks have no CPU path")
     folder = ImageFolder(args.images)
@@ -491,9 +508,7 @@ def main(argv=None):
     torch.cuda.set_device(0)
     nets = build_networks(device)
     load_checkpoint(args.checkpoint, *nets)
-    summary = Segmenter(*nets, out_dir=args.out, batch_size=args.batch_size, overlay=not args.no_overlay, samples=args.samples,
-                        seed=args.seed, scale=args.sample_scale, morphometry=args.morphometry, sectors=args.sectors,
-                        eye=args.eye, views=views).run(folder)
+    summary = Segmenter(*nets, out_dir=args.out, **kw).run(folder)
     torch.cuda.synchronize()
     print(json.dumps(summary, sort_keys=True))
     return 0
