@@ -180,8 +180,14 @@ __global__ __launch_bounds__(256) void upsample2x_fwd_k(const float* __restrict_
   const float* src = x + (size_t)bc * H * W;
   float v00 = act_in(src[y0 * W + x0], pro, c, relu), v01 = act_in(src[y0 * W + x1], pro, c, relu);
   float v10 = act_in(src[y1 * W + x0], pro, c, relu), v11 = act_in(src[y1 * W + x1], pro, c, relu);
-  // same association as ATen's upsample_bilinear2d: h0*(w0*a + w1*b) + h1*(w0*c + w1*d)
-  out[i] = (1.f - ly) * ((1.f - lx) * v00 + lx * v01) + ly * ((1.f - lx) * v10 + lx * v11);
+  // same association as ATen's upsample_bilinear2d: h0*(w0*a + w1*b) + h1*(w0*c + w1*d), with every sum of two products spelled
+  // as one rounded product and one fma, here and in the vector kernel below (upsample2x_fwd4_v_k, the kernel the step runs):
+  // horizontally the weights are (1, 0), (0.25, 0.75) or (0.75, 0.25) and the product with the 0.75 is the rounded one, vertically
+  // the second product.  Left to the compiler's contraction the two kernels differed in the last bit: it fused the vector kernel's
+  // sums this way and left this kernel's outer sum unfused (tests/test_dispatch_paths_gpu.py holds the two together).
+  const float h0 = lx < 0.5f ? fmaf(lx, v01, (1.f - lx) * v00) : fmaf(1.f - lx, v00, lx * v01);
+  const float h1 = lx < 0.5f ? fmaf(lx, v11, (1.f - lx) * v10) : fmaf(1.f - lx, v10, lx * v11);
+  out[i] = fmaf(1.f - ly, h0, ly * h1);
 }
 
 __device__ __forceinline__ float up_w(int d, int n, int k) {  // weight of source k in destination d (1-D)
@@ -223,21 +229,23 @@ __global__ __launch_bounds__(256) void upsample2x_fwd4_v_k(const float* __restri
     const float* r1 = x + (size_t)bc * H * W + (size_t)y1 * W;
     float a[4] = {act_in(r0[xm1], pro, c, relu), act_in(r0[m], pro, c, relu), act_in(r0[x1], pro, c, relu), act_in(r0[x2], pro, c, relu)};
     float b[4] = {act_in(r1[xm1], pro, c, relu), act_in(r1[m], pro, c, relu), act_in(r1[x1], pro, c, relu), act_in(r1[x2], pro, c, relu)};
+    // the scalar kernel's arithmetic, spelled out (see there): horizontally the 0.75-weighted product is rounded and the
+    // 0.25-weighted one fused, vertically the second product is rounded
     float ha[4], hb[4];
-    if (m == 0) { ha[0] = 1.f * a[1] + 0.f * a[2]; hb[0] = 1.f * b[1] + 0.f * b[2]; }
-    else        { ha[0] = 0.25f * a[0] + 0.75f * a[1]; hb[0] = 0.25f * b[0] + 0.75f * b[1]; }
-    ha[1] = 0.75f * a[1] + 0.25f * a[2]; hb[1] = 0.75f * b[1] + 0.25f * b[2];
-    ha[2] = 0.25f * a[1] + 0.75f * a[2]; hb[2] = 0.25f * b[1] + 0.75f * b[2];
-    ha[3] = 0.75f * a[2] + 0.25f * a[3]; hb[3] = 0.75f * b[2] + 0.25f * b[3];
+    if (m == 0) { ha[0] = fmaf(0.f, a[2], a[1]); hb[0] = fmaf(0.f, b[2], b[1]); }
+    else        { ha[0] = fmaf(0.25f, a[0], 0.75f * a[1]); hb[0] = fmaf(0.25f, b[0], 0.75f * b[1]); }
+    ha[1] = fmaf(0.25f, a[2], 0.75f * a[1]); hb[1] = fmaf(0.25f, b[2], 0.75f * b[1]);
+    ha[2] = fmaf(0.25f, a[1], 0.75f * a[2]); hb[2] = fmaf(0.25f, b[1], 0.75f * b[2]);
+    ha[3] = fmaf(0.25f, a[3], 0.75f * a[2]); hb[3] = fmaf(0.25f, b[3], 0.75f * b[2]);
     float4 oa, ob;
-    oa.x = (1.f - la) * ha[0] + la * hb[0];
-    oa.y = (1.f - la) * ha[1] + la * hb[1];
-    oa.z = (1.f - la) * ha[2] + la * hb[2];
-    oa.w = (1.f - la) * ha[3] + la * hb[3];
-    ob.x = (1.f - lb) * ha[0] + lb * hb[0];
-    ob.y = (1.f - lb) * ha[1] + lb * hb[1];
-    ob.z = (1.f - lb) * ha[2] + lb * hb[2];
-    ob.w = (1.f - lb) * ha[3] + lb * hb[3];
+    oa.x = fmaf(1.f - la, ha[0], la * hb[0]);
+    oa.y = fmaf(1.f - la, ha[1], la * hb[1]);
+    oa.z = fmaf(1.f - la, ha[2], la * hb[2]);
+    oa.w = fmaf(1.f - la, ha[3], la * hb[3]);
+    ob.x = fmaf(1.f - lb, ha[0], lb * hb[0]);
+    ob.y = fmaf(1.f - lb, ha[1], lb * hb[1]);
+    ob.z = fmaf(1.f - lb, ha[2], lb * hb[2]);
+    ob.w = fmaf(1.f - lb, ha[3], lb * hb[3]);
     float* ob0 = out + (size_t)bc * Ho * Wo + 4 * k;
     if (va) *reinterpret_cast<float4*>(ob0 + (size_t)ya * Wo) = oa;
     if (vb) *reinterpret_cast<float4*>(ob0 + (size_t)yb * Wo) = ob;
