@@ -289,12 +289,12 @@ def test_csv_round_trip_is_bitwise(tmp_path):
 @pytest.mark.parametrize("kw", [{"sectors": 12}, {"sectors": 368}, {"sectors": 0}, {"eye": "both"}, {"eye": "Right"}], ids=str)
 def test_constructors_reject_bad_arguments(kw, tmp_path):
     from wtpse_hip.segment import Segmenter
-    from wtpse_hip.morphometry_run import MorphometryTestRun
+    from wtpse_hip.test_run import TestRun
     for morphometry in (False, True):
         with pytest.raises(ValueError):
             Segmenter(None, None, None, None, out_dir=str(tmp_path / "s"), morphometry=morphometry, **kw)
         with pytest.raises(ValueError):
-            MorphometryTestRun(None, None, None, None, out_dir=str(tmp_path / "t"), morphometry=morphometry, **kw)
+            TestRun(None, None, None, None, out_dir=str(tmp_path / "t"), morphometry=morphometry, **kw)
     assert not os.path.exists(tmp_path / "s") and not os.path.exists(tmp_path / "t")
     ok = Segmenter(None, None, None, None, out_dir=str(tmp_path / "s"), morphometry=True, sectors=64, eye="left")
     assert (ok.morphometry, ok.sectors, ok.eye) == (True, 64, "left")

@@ -1,5 +1,5 @@
 """Optic-disc morphometry on the device (-m gpu): ops.onh_profile against morphometry.profile_host bit for bit, its repeatability and
-argument checks, Segmenter.back / Segmenter.run / MorphometryTestRun.batch with the switch on against the host's finishing of the host's records,
+argument checks, Segmenter.back / Segmenter.run / TestRun.batch with the switch on against the host's finishing of the host's records,
 and the switch-off outputs unchanged beside them."""
 import json
 import os
@@ -212,7 +212,6 @@ def test_segmenter_run_with_morphometry_and_samples(nets, tmp_path):
 
 def test_morphometry_test_run_batch(nets, tmp_path):
     from wtpse_hip import morphometry as M, ops, validate as V
-    from wtpse_hip.morphometry_run import MorphometryTestRun
     from wtpse_hip.test_run import TestRun
     B, h, w = 2, 90, 70
     image = make_inputs(61, B, 64, 64)[0].to(DEV)
@@ -220,17 +219,17 @@ def test_morphometry_test_run_batch(nets, tmp_path):
     loc = np.stack([raster_ellipse(h, w, 47, 33, 14, 10, 0.8), raster_ellipse(h, w, 38, 32, 9, 12, 0.0)])[:, None].astype(np.float32)
     plain = TestRun(*nets, out_dir=str(tmp_path / "plain"))
     m0, orig0, over0 = plain.batch(image, _dev(lod), _dev(loc))
-    run = MorphometryTestRun(*nets, out_dir=str(tmp_path / "morph"), morphometry=True, sectors=24, eye="right")
-    off = MorphometryTestRun(*nets, out_dir=str(tmp_path / "off"))
+    run = TestRun(*nets, out_dir=str(tmp_path / "morph"), morphometry=True, sectors=24, eye="right")
+    off = TestRun(*nets, out_dir=str(tmp_path / "off"))
     m1, orig1, over1 = run.batch(image, _dev(lod), _dev(loc))
     assert np.array_equal(orig0, orig1) and np.array_equal(over0, over1)
     assert all(all(same(a, b) for a, b in zip(m0[k], m1[k])) for k in V.METRIC_KEYS)
     m2 = off.batch(image, _dev(lod), _dev(loc))
     assert np.array_equal(m2[1], orig0) and np.array_equal(m2[2], over0) and off.morph_label == [] and off.morphometry is False
     assert len(run.morph_label) == len(run.morph_pred) == B
-    # the restated batch follows TestRun.batch on the host sides too
+    # the switch leaves the host sides' metrics and pictures as they are too
     mh0 = TestRun(*nets, out_dir=str(tmp_path / "h0"), overlay="host", metrics="host").batch(image, _dev(lod), _dev(loc))
-    mh1 = MorphometryTestRun(*nets, out_dir=str(tmp_path / "h1"), overlay="host", metrics="host", morphometry=True).batch(image, _dev(lod), _dev(loc))
+    mh1 = TestRun(*nets, out_dir=str(tmp_path / "h1"), overlay="host", metrics="host", morphometry=True).batch(image, _dev(lod), _dev(loc))
     assert np.array_equal(mh0[1], mh1[1]) and np.array_equal(mh0[2], mh1[2])
     assert all(all(same(a, b) for a, b in zip(mh0[0][k], mh1[0][k])) for k in V.METRIC_KEYS)
     pred, pred_oc = V.predict_pair(*nets, image, (h, w))
@@ -253,3 +252,28 @@ def test_morphometry_test_run_batch(nets, tmp_path):
     for f in ("per_image.csv", "summary.json"):
         with open(tmp_path / "plain" / f, "rb") as fa, open(tmp_path / "morph" / f, "rb") as fb:
             assert fa.read() == fb.read(), f
+
+
+# ---- the one copy -------------------------------------------------------------------------------------------------------------------
+def test_everything_comes_back_in_one_copy_per_size_group_or_batch(nets, tmp_path, monkeypatch):
+    """Every optional output on: Segmenter.back_result copies once per size group, TestRun.batch once per batch."""
+    from wtpse_hip.test_run import TestRun
+    calls, real = [], torch.Tensor.cpu
+    monkeypatch.setattr(torch.Tensor, "cpu", lambda self, *a, **kw: calls.append(tuple(self.shape)) or real(self, *a, **kw))
+    rng = np.random.default_rng(2)
+    image = _dev(rng.uniform(-1, 1, (3, 3, 256, 256)).astype(np.float32))
+    spread = tuple(_dev(rng.uniform(0, 0.5, (3, 1, 256, 256)).astype(np.float32)) for _ in range(2))
+    lod, loc = (_dev(a) for a in _pseudo_logits(None))
+    seg = _segmenter(str(tmp_path / "seg"), morphometry=True, sectors=24, eye="right")
+    res = seg.back_result(image, lod, loc, BACK_SIZES, spread)
+    assert len(set(BACK_SIZES)) == 2 and len(calls) == 2, calls
+    assert all(x is not None for x in res.overlays + res.spreads + res.morph) and res.spreads[1].shape == (2,) + BACK_SIZES[1]
+    B, h, w = 2, 90, 70
+    small = make_inputs(61, B, 64, 64)[0].to(DEV)
+    lab_od = _dev(np.stack([raster_ellipse(h, w, 44, 36, 30, 26, 0.3), raster_ellipse(h, w, 40, 30, 28, 22, 1.0)])[:, None].astype(np.float32))
+    lab_oc = _dev(np.stack([raster_ellipse(h, w, 47, 33, 14, 10, 0.8), raster_ellipse(h, w, 38, 32, 9, 12, 0.0)])[:, None].astype(np.float32))
+    run = TestRun(*nets, out_dir=str(tmp_path / "run"), overlay="device", metrics="device", morphometry=True)
+    del calls[:]
+    m, original, over = run.batch(small, lab_od, lab_oc)
+    assert len(calls) == 1, calls
+    assert original.shape == over.shape == (B, h, w, 3) and len(m["disc_dice"]) == len(run.morph_pred) == len(run.morph_label) == B

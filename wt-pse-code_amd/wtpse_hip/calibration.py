@@ -15,10 +15,11 @@ of whole q values (bins divides 1024), so only the bin's mean confidence moves, 
 those of the quantised probability, the NLL with p clipped to [2^-11, 1 - 2^-11], half a step from the ends; the AUROCs count two pixels
 that share a q (or a u) as a tie, worth 0.5.
 """
-import json
 import os
 
 import numpy as np
+
+from . import tables as T
 
 BINS = 1024
 REC = 2 * (BINS + 1) * 2 + 4
@@ -242,26 +243,6 @@ def parse_scales(text):
 
 
 # ---- the tables ---------------------------------------------------------------------------------------------------------------------
-def _name(r):
-    name = str(r["name"])
-    return '"' + name.replace('"', '""') + '"' if any(ch in name for ch in ',"\n') else name
-
-
-def _write(path, columns, rows, ints, texts=("name",)):
-    """uncertainty.write_csv's form: floats as repr (they read back to the same float64; nan as "nan")."""
-    with open(path, "w") as f:
-        f.write(",".join(columns) + "\n")
-        for r in rows:
-            f.write(",".join(_name(r) if k == "name" else str(r[k]) if k in texts else str(int(r[k])) if k in ints else repr(float(r[k]))
-                             for k in columns) + "\n")
-
-
-def _read(path, ints, texts=("name",)):
-    import csv
-    with open(path, newline="") as f:
-        return [{k: v if k in texts else int(v) if k in ints else float(v) for k, v in r.items()} for r in csv.DictReader(f)]
-
-
 TABLES = {"calibration": (CALIBRATION_COLUMNS, ("n_scored", "n_excluded_neg", "n_excluded_pos", "n_invalid", "n_defined"), ("structure",)),
           "reliability": (RELIABILITY_COLUMNS, ("bin", "n"), ("structure",)),
           "risk_coverage": (RISK_COLUMNS, (), ("structure", "level")),
@@ -272,18 +253,16 @@ def write_csv(out_dir, table, rows):
     """table: a key of TABLES -> out_dir/<table>.csv with that table's columns."""
     columns, ints, texts = TABLES[table]
     os.makedirs(out_dir, exist_ok=True)
-    _write(os.path.join(out_dir, table + ".csv"), columns, rows, ints, texts)
+    T.write_csv(os.path.join(out_dir, table + ".csv"), columns, rows, ints, texts)
 
 
 def read_csv(out_dir, table):
     _, ints, texts = TABLES[table]
-    return _read(os.path.join(out_dir, table + ".csv"), ints, texts)
+    return T.read_csv(os.path.join(out_dir, table + ".csv"), ints, texts)
 
 
 def write_summary(out_dir, summary):
-    with open(os.path.join(out_dir, "summary.json"), "w") as f:
-        json.dump(summary, f, indent=1, sort_keys=True, allow_nan=False)
-        f.write("\n")
+    T.write_json(os.path.join(out_dir, "summary.json"), summary, allow_nan=False)
 
 
 def best_scales(rows):

@@ -51,7 +51,8 @@ from . import ops
 from . import validate as V
 from . import views as VW
 from .segment import Segmenter, measure
-from .test_run import FundusTestBatches, build_networks, load_checkpoint
+from .packed import fetch
+from .programs import add_split_arguments, open_test_split
 
 THRESHOLD = 0.75                                # the threshold of od_pred, of the post-processing and of the samples' votes
 
@@ -76,14 +77,8 @@ class CalibrationRun:
 
     def _records(self, prob, spread, label, region, extra=()):
         """One launch for both structures, one copy -> (uint32 [2 B, REC], the extra int64 tensors' host copies)."""
-        rec = ops.calibration_hist(prob, spread, label, region, THRESHOLD)
-        host = torch.cat([rec.view(torch.uint8).reshape(-1)] + [t.view(torch.uint8).reshape(-1) for t in extra]).cpu().numpy()      # the one copy
-        n = rec.numel() * 4
-        out, off = [], n
-        for t in extra:
-            out.append(host[off:off + 8 * t.numel()].copy().view(np.int64).reshape(tuple(t.shape)))
-            off += 8 * t.numel()
-        return host[:n].copy().view(np.uint32).reshape(tuple(rec.shape)), out
+        rec, *out = fetch([ops.calibration_hist(prob, spread, label, region, THRESHOLD), *extra])       # the one copy
+        return rec.view(np.uint32), out
 
     def predict_pair(self, image):
         """The deterministic prediction at the network size -> (pred, pred_oc): validate.predict_pair, or with views the merged pair
@@ -104,10 +99,10 @@ class CalibrationRun:
                 if self._det is not None and self._det[0] is image:
                     return self._det[1:]
                 return V.predict_pair_views(*self.nets, image, self.views)[2:]
-            per_image = 2 * len(self.views) * self.samples * S * S
-            return V.predict_pair_views(*self.nets, image, self.views, self.samples, self.seed, first * per_image, scale)[2:]
-        per_image = 2 * self.samples * S * S                         # an image's share of the noise stream
-        return V.predict_pair_samples(*self.nets, image, self.samples, self.seed, first * per_image, scale, want_logits=True)[2:]
+            offset = first * V.noise_share(self.samples, S, len(self.views))
+            return V.predict_pair_views(*self.nets, image, self.views, self.samples, self.seed, offset, scale)[2:]
+        offset = first * V.noise_share(self.samples, S)
+        return V.predict_pair_samples(*self.nets, image, self.samples, self.seed, offset, scale, want_logits=True)[2:]
 
     def _segmenter(self, B, S):
         if self._seg is None or self._seg.batch_size != B or self._seg.size != S:
@@ -203,12 +198,9 @@ class CalibrationRun:
         return summary
 
     def run(self, batches):
-        modes = [n.training for n in self.nets]
-        for n in self.nets:
-            n.eval()
         os.makedirs(self.out_dir, exist_ok=True)
         per_scale, recs, count = {s: [] for s in self.scales}, {s: [] for s in self.scales}, 0
-        try:
+        with V.eval_mode(self.nets):
             for item in batches:
                 image, label_od, label_oc = item[:3]
                 names = item[3] if len(item) > 3 else [""] * image.shape[0]
@@ -218,9 +210,6 @@ class CalibrationRun:
                         recs[s].append(row.pop("rec"))
                         per_scale[s].append(dict(row, scale=s, index=count + i + 1, name=names[i]))
                 count += image.shape[0]
-        finally:
-            for n, mode in zip(self.nets, modes):
-                n.train(mode)
         self._det = None
         self.rows = [r for s in self.scales for r in per_scale[s]]
         self.records = {s: np.stack(recs[s]) if recs[s] else np.zeros((0, 2, C.REC), np.uint32) for s in self.scales}
@@ -233,10 +222,7 @@ def parse_args(argv=None):
     a bad value ends the program before anything runs."""
     import argparse
     ap = argparse.ArgumentParser(prog="python -m wtpse_hip.calibration_run", description=__doc__.split("\n\n")[0])
-    ap.add_argument("--data-dir", required=True)
-    ap.add_argument("--datasetTest", type=int, required=True, help="the target domain: Domain<N>/test is read")
-    ap.add_argument("--checkpoint", required=True, help="checkpoint_<epoch>.pth.tar as validate.Validator saves it")
-    ap.add_argument("--out", required=True)
+    add_split_arguments(ap)
     ap.add_argument("--samples", type=int, default=16, help="K sampled shape latents per image and scale")
     ap.add_argument("--scales", default="0,0.5,1,2", help="the --sample-scale values to score, separated by commas; 0 = the deterministic prediction")
     ap.add_argument("--bins", type=int, default=16, help="reliability bins: a divisor of 1024")
@@ -257,19 +243,10 @@ def parse_args(argv=None):
 
 
 def main(argv=None):
-    from .fundus_data import FundusTree
     args = parse_args(argv)
-    if not torch.cuda.is_available():
-        raise SystemExit("wtpse_hip.calibration_run needs the GPU: the networks have no CPU path")
-    device = "cuda:0"
-    torch.cuda.set_device(0)
-    nets = build_networks(device)
-    load_checkpoint(args.checkpoint, *nets)
-    tree = FundusTree(args.data_dir, phase="test", splitid=(args.datasetTest,), state="prediction")
-    if len(tree) < 1:
-        raise SystemExit("no test images under %s" % os.path.join(args.data_dir, "Domain%d" % args.datasetTest, "test"))
+    nets, batches = open_test_split("calibration_run", args)
     run = CalibrationRun(*nets, out_dir=args.out, samples=args.samples, scales=args.scales, bins=args.bins, seed=args.seed, views=args.views)
-    summary = run.run(FundusTestBatches(tree, args.batch_size, device))
+    summary = run.run(batches)
     torch.cuda.synchronize()
     print(json.dumps(summary, sort_keys=True))
     return 0

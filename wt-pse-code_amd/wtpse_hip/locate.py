@@ -42,6 +42,9 @@ import numpy as np
 import torch
 
 from . import ops
+from . import tables as T
+from . import validate as V
+from .packed import fetch
 from .segment import ImageFolder, Segmenter, _groups
 
 ROI_INT = ("height", "width", "fov_area")
@@ -211,20 +214,11 @@ def plan(cells, c, count=3, disc_scale=0.13, roi_scale=0.4, side=None):
 # ---- roi.csv ----------------------------------------------------------------------------------------------------------------
 def write_roi_csv(out_dir, rows):
     os.makedirs(out_dir, exist_ok=True)
-    with open(os.path.join(out_dir, "roi.csv"), "w") as f:
-        f.write(",".join(ROI_COLUMNS) + "\n")
-        for r in rows:
-            name = str(r["name"])
-            if any(ch in name for ch in ',"\n'):
-                name = '"' + name.replace('"', '""') + '"'
-            f.write(",".join([str(int(r["index"])), name]
-                             + [str(int(r[k])) if k in _INTS else repr(float(r[k])) for k in ROI_COLUMNS[2:]]) + "\n")
+    T.write_csv(os.path.join(out_dir, "roi.csv"), ROI_COLUMNS, rows, ("index",) + _INTS)
 
 
 def read_roi_csv(out_dir):
-    import csv
-    with open(os.path.join(out_dir, "roi.csv"), newline="") as f:
-        return [dict(r, index=int(r["index"]), **{k: int(r[k]) for k in _INTS}, **{k: float(r[k]) for k in _FLOATS}) for r in csv.DictReader(f)]
+    return T.read_csv(os.path.join(out_dir, "roi.csv"), ("index",) + _INTS)
 
 
 def _blank_row(h, w):
@@ -387,16 +381,12 @@ class WholeImageSegmenter:
             for _, pos in _groups([im.shape[:2] for im in images]).items():
                 stack = torch.from_numpy(np.stack([images[p] for p in pos])).to(device)
                 got_rows, got_crops = self.locator.locate(stack)
-                kept = [c for c in got_crops if c is not None]
-                host = torch.cat([c.reshape(-1) for c in kept]).cpu().numpy() if kept else None
-                at = 0
+                host = iter(fetch([c for c in got_crops if c is not None]))         # the one copy
                 for p, row, crop in zip(pos, got_rows, got_crops):
                     i = idx[p]
                     rows[i], crops[i] = dict(row, index=i + 1, name=folder.names[i]), crop
                     if crop is not None:
-                        n = crop.numel()
-                        Image.fromarray(host[at:at + n].reshape(tuple(crop.shape))).save(os.path.join(self.out_dir, "crop", folder.names[i]))
-                        at += n
+                        Image.fromarray(next(host)).save(os.path.join(self.out_dir, "crop", folder.names[i]))
         return rows, crops
 
     def _write_full(self, folder, rows, device):
@@ -418,27 +408,20 @@ class WholeImageSegmenter:
                     ops.paste_u8(masks[j], read("mask", r["name"]).reshape(r["roi_side"], r["roi_side"], 1), r["roi_top"], r["roi_left"])
                     if overlay:
                         ops.paste_u8(photos[j], read("overlay", r["name"]), r["roi_top"], r["roi_left"])
-                host = torch.cat([masks.reshape(-1)] + ([photos.reshape(-1)] if overlay else [])).cpu().numpy()         # the one copy
+                host_masks, *host_photos = fetch([masks.reshape(n, H, W)] + ([photos] if overlay else []))        # the one copy
                 for j, p in enumerate(pos):
                     name = rows[idx[p]]["name"]
-                    Image.fromarray(host[j * H * W:(j + 1) * H * W].reshape(H, W), "L").save(os.path.join(self.out_dir, "full_mask", name))
+                    Image.fromarray(host_masks[j], "L").save(os.path.join(self.out_dir, "full_mask", name))
                     if overlay:
-                        off = n * H * W + j * H * W * 3
-                        Image.fromarray(host[off:off + H * W * 3].reshape(H, W, 3)).save(os.path.join(self.out_dir, "full_overlay", name))
+                        Image.fromarray(host_photos[0][j]).save(os.path.join(self.out_dir, "full_overlay", name))
 
     def run(self, folder):
         if not isinstance(folder, ImageFolder):
             folder = ImageFolder(folder)
         nets = self.segmenter.nets
         device = next(nets[0].parameters()).device
-        modes = [n.training for n in nets]
-        for n in nets:
-            n.eval()
-        try:
+        with V.eval_mode(nets):
             rows, crops = self._locate_all(folder, device)
-        finally:
-            for n, mode in zip(nets, modes):
-                n.train(mode)
         found = [i for i, r in enumerate(rows) if r["located"]]
         summary = self.segmenter.run(CropFolder([folder.paths[i] for i in found], [crops[i] for i in found]))
         for i, m in zip(found, self.segmenter.rows):
@@ -447,9 +430,7 @@ class WholeImageSegmenter:
         self.roi_rows = rows
         write_roi_csv(self.out_dir, rows)
         summary = dict(summary, n_located=len(found), n_verified=sum(1 for r in rows if r["verified"] == 1), n_not_located=len(rows) - len(found))
-        with open(os.path.join(self.out_dir, "summary.json"), "w") as f:
-            json.dump(summary, f, indent=1, sort_keys=True, allow_nan=False)
-            f.write("\n")
+        T.write_json(os.path.join(self.out_dir, "summary.json"), summary, allow_nan=False)
         if self.full and found:
             self._write_full(folder, rows, device)
         return summary
@@ -477,7 +458,7 @@ def parser():
 
 def main(argv=None):
     from . import segment
-    from .test_run import build_networks, load_checkpoint
+    from .programs import load_networks, require_gpu
     ap = parser()
     args = ap.parse_args(argv)
     kw = segment.segmenter_arguments(ap, args)
@@ -486,15 +467,11 @@ def main(argv=None):
             args.cell = int(args.cell)
         except ValueError:
             ap.error("--cell takes auto or an integer in 2..256")
-    if not torch.cuda.is_available():
-        raise SystemExit("wtpse_hip.locate needs the GPU: the networks have no CPU path")
+    require_gpu("locate")
     folder = ImageFolder(args.images)
     if len(folder) < 1:
         raise SystemExit("no image (%s) under %s" % (" ".join(segment.EXTENSIONS), args.images))
-    device = "cuda:0"
-    torch.cuda.set_device(0)
-    nets = build_networks(device)
-    load_checkpoint(args.checkpoint, *nets)
+    nets, _ = load_networks(args.checkpoint)
     try:
         run = WholeImageSegmenter(*nets, out_dir=args.out, full=not args.no_full, candidates=args.candidates, refine=args.refine,
                                   disc_scale=args.disc_scale, roi_scale=args.roi_scale, roi_side=args.roi_side, cell=args.cell,

@@ -21,6 +21,8 @@ import os
 
 import numpy as np
 
+from . import tables as T
+
 MIN_SECTORS, MAX_SECTORS = 8, 360
 EYES = (None, "right", "left")
 SCALE = 1 << 20
@@ -254,25 +256,6 @@ def error_means(rows):
 
 
 # ---- the tables -----------------------------------------------------------------------------------------------------------
-def _name(r):
-    name = str(r["name"])
-    return '"' + name.replace('"', '""') + '"' if any(ch in name for ch in ',"\n') else name
-
-
-def _write(path, columns, rows, ints, texts=("name",)):
-    with open(path, "w") as f:
-        f.write(",".join(columns) + "\n")
-        for r in rows:
-            f.write(",".join(_name(r) if k == "name" else str(r[k]) if k in texts else str(int(r[k])) if k in ints else repr(float(r[k]))
-                             for k in columns) + "\n")
-
-
-def _read(path, ints, texts=("name",)):
-    import csv
-    with open(path, newline="") as f:
-        return [{k: v if k in texts else int(v) if k in ints else float(v) for k, v in r.items()} for r in csv.DictReader(f)]
-
-
 def rim_columns(N):
     return tuple("rim_%03d" % s for s in range(N))
 
@@ -281,16 +264,16 @@ def write_csv(out_dir, rows):
     """rows: [{MORPH_COLUMNS, rim}] -> out_dir/morphometry.csv and out_dir/rim_profile.csv (index, name, rim_000 .. rim_{N-1}, pixels
     at the image's own size).  Floats as repr: they read back to the same float64; nan as "nan"."""
     os.makedirs(out_dir, exist_ok=True)
-    _write(os.path.join(out_dir, "morphometry.csv"), MORPH_COLUMNS, rows, ("index",) + INT_COLUMNS, ("name", "eye"))
+    T.write_csv(os.path.join(out_dir, "morphometry.csv"), MORPH_COLUMNS, rows, ("index",) + INT_COLUMNS, ("name", "eye"))
     cols = rim_columns(rows[0]["sectors"]) if rows else ()
-    _write(os.path.join(out_dir, "rim_profile.csv"), ("index", "name") + cols,
-           [dict(zip(cols, r["rim"]), index=r["index"], name=r["name"]) for r in rows], ("index",))
+    T.write_csv(os.path.join(out_dir, "rim_profile.csv"), ("index", "name") + cols,
+                [dict(zip(cols, r["rim"]), index=r["index"], name=r["name"]) for r in rows], ("index",))
 
 
 def read_csv(out_dir):
     """-> the rows as write_csv wrote them, "rim" (from rim_profile.csv) included."""
-    rows = _read(os.path.join(out_dir, "morphometry.csv"), ("index",) + INT_COLUMNS, ("name", "eye"))
-    rims = _read(os.path.join(out_dir, "rim_profile.csv"), ("index",))
+    rows = T.read_csv(os.path.join(out_dir, "morphometry.csv"), ("index",) + INT_COLUMNS, ("name", "eye"))
+    rims = T.read_csv(os.path.join(out_dir, "rim_profile.csv"), ("index",))
     for r, p in zip(rows, rims):
         assert (r["index"], r["name"]) == (p["index"], p["name"])
         r["rim"] = [p[k] for k in rim_columns(r["sectors"])]
@@ -301,12 +284,12 @@ def write_uncertainty_csv(out_dir, rows):
     """rows: [{index, name, sample_statistics(...)}] -> out_dir/morphometry_uncertainty.csv: STAT_COLUMNS and rim_rel_std_000 ..."""
     os.makedirs(out_dir, exist_ok=True)
     cols = tuple("rim_rel_std_%03d" % s for s in range(len(rows[0]["rim_rel_std"]))) if rows else ()
-    _write(os.path.join(out_dir, "morphometry_uncertainty.csv"), ("index", "name") + STAT_COLUMNS + cols,
-           [dict(r, **dict(zip(cols, r["rim_rel_std"]))) for r in rows], ("index", "n_samples", "n_defined"))
+    T.write_csv(os.path.join(out_dir, "morphometry_uncertainty.csv"), ("index", "name") + STAT_COLUMNS + cols,
+                [dict(r, **dict(zip(cols, r["rim_rel_std"]))) for r in rows], ("index", "n_samples", "n_defined"))
 
 
 def read_uncertainty_csv(out_dir):
-    rows = _read(os.path.join(out_dir, "morphometry_uncertainty.csv"), ("index", "n_samples", "n_defined"))
+    rows = T.read_csv(os.path.join(out_dir, "morphometry_uncertainty.csv"), ("index", "n_samples", "n_defined"))
     return [dict({k: v for k, v in r.items() if not k.startswith("rim_rel_std_")},
                  rim_rel_std=[v for k, v in r.items() if k.startswith("rim_rel_std_")]) for r in rows]
 
@@ -317,11 +300,11 @@ def write_errors_csv(out_dir, rows):
     os.makedirs(out_dir, exist_ok=True)
     means = error_means(rows)
     last = dict({k: NAN if means["mean_" + k] is None else means["mean_" + k] for k in ERROR_COLUMNS}, index=0, name="mean")
-    _write(os.path.join(out_dir, "morphometry_errors.csv"), ("index", "name") + ERROR_COLUMNS, list(rows) + [last], ("index",))
+    T.write_csv(os.path.join(out_dir, "morphometry_errors.csv"), ("index", "name") + ERROR_COLUMNS, list(rows) + [last], ("index",))
     return means
 
 
 def read_errors_csv(out_dir):
     """-> (rows, the closing row of means)."""
-    rows = _read(os.path.join(out_dir, "morphometry_errors.csv"), ("index",))
+    rows = T.read_csv(os.path.join(out_dir, "morphometry_errors.csv"), ("index",))
     return rows[:-1], rows[-1]

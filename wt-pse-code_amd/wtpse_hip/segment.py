@@ -65,10 +65,12 @@ import torch
 
 from . import morphometry as M
 from . import ops
+from . import tables as T
 from . import uncertainty as U
 from . import validate as V
 from . import views as VW
 from .input_pipeline import DeviceInputPipeline, _dev_i32, resample_table
+from .packed import fetch
 
 EXTENSIONS = (".png", ".jpg", ".jpeg", ".bmp", ".tif", ".tiff")
 INT_COLUMNS = ("height", "width", "disc_area", "cup_area", "disc_top", "disc_bottom", "disc_left", "disc_right",
@@ -136,27 +138,13 @@ def write_measurements(out_dir, rows, summary):
     """rows: [{CSV_COLUMNS}] -> out_dir/measurements.csv (floats as repr: they read back to the same float64; nan as "nan") and
     out_dir/summary.json (an undefined mean as null)."""
     os.makedirs(out_dir, exist_ok=True)
-    with open(os.path.join(out_dir, "measurements.csv"), "w") as f:
-        f.write(",".join(CSV_COLUMNS) + "\n")
-        for r in rows:
-            name = str(r["name"])
-            if any(ch in name for ch in ',"\n'):
-                name = '"' + name.replace('"', '""') + '"'
-            f.write(",".join([str(int(r["index"])), name] + [str(int(r[k])) for k in INT_COLUMNS]
-                             + [repr(float(r[k])) for k in FLOAT_COLUMNS]) + "\n")
-    with open(os.path.join(out_dir, "summary.json"), "w") as f:
-        json.dump(summary, f, indent=1, sort_keys=True, allow_nan=False)
-        f.write("\n")
+    T.write_csv(os.path.join(out_dir, "measurements.csv"), CSV_COLUMNS, rows, ("index",) + INT_COLUMNS)
+    T.write_json(os.path.join(out_dir, "summary.json"), summary, allow_nan=False)
 
 
 def read_measurements(out_dir):
     """-> (rows, summary) as write_measurements wrote them."""
-    import csv
-    with open(os.path.join(out_dir, "measurements.csv"), newline="") as f:
-        rows = [dict(r, index=int(r["index"]), **{k: int(r[k]) for k in INT_COLUMNS}, **{k: float(r[k]) for k in FLOAT_COLUMNS})
-                for r in csv.DictReader(f)]
-    with open(os.path.join(out_dir, "summary.json")) as f:
-        return rows, json.load(f)
+    return T.read_csv(os.path.join(out_dir, "measurements.csv"), ("index",) + INT_COLUMNS), T.read_json(os.path.join(out_dir, "summary.json"))
 
 
 # ---- the feed -------------------------------------------------------------------------------------------------------------
@@ -314,29 +302,22 @@ class Segmenter:
             masks = ops.postprocess_masks(torch.cat((lod, loc), 0))
             disc, cup = masks[:n], masks[n:]
             geom = ops.mask_geometry(masks)
-            blob = [geom.view(torch.uint8).reshape(-1), ops.label_map(disc, cup).reshape(-1)]
+            out = [geom, ops.label_map(disc, cup).reshape(n, h, w)]
             if self.overlay:
                 if (h, w) != (S, S):
                     img = ops.resize_bilinear(img, (h, w))              # the test run's picture (test_visulization.py:231-232)
-                blob.append(ops.overlay(img, disc, cup, None, None)[1].reshape(-1))
+                out.append(ops.overlay(img, disc, cup, None, None)[1])
             if spread is not None:
-                blob.append(sp.contiguous().view(torch.uint8).reshape(-1))
+                out.append(sp.reshape(2, n, h, w))
             if self.morphometry:
-                blob.extend(t.view(torch.uint8).reshape(-1) for t in ops.onh_profile(disc, cup, geom[:n], self.sectors))
-            host = torch.cat(blob).cpu().numpy()                       # the one copy
-            rec = host[:2 * n * 64].view(np.int64).reshape(2 * n, 8)
-            off = 2 * n * 64
-            lm = host[off:off + n * h * w].reshape(n, h, w)
-            off += n * h * w
-            ov = host[off:off + n * h * w * 3].reshape(n, h, w, 3) if self.overlay else None
-            off += n * h * w * 3 if self.overlay else 0
-            sm = host[off:off + 8 * n * h * w].copy().view(np.float32).reshape(2, n, h, w) if spread is not None else None
-            off += 8 * n * h * w if spread is not None else 0
+                out.extend(ops.onh_profile(disc, cup, geom[:n], self.sectors))
+            host = iter(fetch(out))                                    # the one copy; taken in the order it was filled
+            rec, lm = next(host), next(host)
+            ov = next(host) if self.overlay else None
+            sm = next(host) if spread is not None else None
             if self.morphometry:
-                N = self.sectors
-                prof = host[off:off + 16 * n * N].copy().view(np.uint32).reshape(n, N, 4)
-                mom = host[off + 16 * n * N:off + 16 * n * N + 64 * n].copy().view(np.int64).reshape(n, 2, 4)
-                mrows = M.finish_batch(rec, mom, prof, h, w, self.eye)
+                prof, mom = next(host), next(host)
+                mrows = M.finish_batch(rec, mom, prof.view(np.uint32), h, w, self.eye)
             for j, i in enumerate(idx):
                 labels[i], rows[i] = lm[j], measure(rec[j], rec[n + j], h, w)
                 overlays[i] = ov[j] if self.overlay else None
@@ -357,27 +338,22 @@ class Segmenter:
         B, K, S = disc.logits.shape[0], disc.logits.shape[1], self.size
         masks = ops.postprocess_masks(torch.cat((disc.logits.reshape(B * K, 1, S, S), cup.logits.reshape(B * K, 1, S, S)), 0))
         geom = ops.mask_geometry(masks)
-        blob = [geom.view(torch.uint8).reshape(-1), disc.votes.reshape(-1), cup.votes.reshape(-1),
-                torch.cat((disc.std, cup.std), 0).view(torch.uint8).reshape(-1)]
+        out = [geom.reshape(2, B, K, 8), disc.votes.reshape(B, S, S), cup.votes.reshape(B, S, S),
+               torch.cat((disc.std, cup.std), 0).reshape(2, B, S, S)]
         if self.morphometry:
-            blob.extend(t.view(torch.uint8).reshape(-1) for t in ops.onh_profile(masks[:B * K], masks[B * K:], geom[:B * K], self.sectors))
-        host = torch.cat(blob).cpu().numpy()
-        n = 2 * B * K * 64
-        rec = host[:n].view(np.int64).reshape(2, B, K, 8)
-        votes = host[n:n + 2 * B * S * S].reshape(2, B, S, S)
-        end = n + 10 * B * S * S
-        std = host[n + 2 * B * S * S:end].copy().view(np.float32).reshape(2, B, S, S)
+            out.extend(ops.onh_profile(masks[:B * K], masks[B * K:], geom[:B * K], self.sectors))
+        rec, votes_disc, votes_cup, std, *morph = fetch(out)           # the one copy
+        votes = (votes_disc, votes_cup)
         rows = []
         for b in range(B):
             row = U.ratio_statistics([measure(rec[0, b, k], rec[1, b, k], S, S) for k in range(K)])
             for c, name in enumerate(("disc", "cup")):
-                row[name + "_disagree_px"], row[name + "_std_mean"] = U.map_statistics(votes[c, b], std[c, b], K)
+                row[name + "_disagree_px"], row[name + "_std_mean"] = U.map_statistics(votes[c][b], std[c, b], K)
             rows.append(row)
         if not self.morphometry:
             return rows, None
         N = self.sectors
-        prof = host[end:end + 16 * B * K * N].copy().view(np.uint32).reshape(B, K, N, 4)
-        mom = host[end + 16 * B * K * N:].copy().view(np.int64).reshape(B, K, 2, 4)
+        prof, mom = morph[0].view(np.uint32).reshape(B, K, N, 4), morph[1].reshape(B, K, 2, 4)
         return rows, [M.sample_statistics([M.finish(rec[0, b, k], rec[1, b, k], mom[b, k], prof[b, k], S, S, self.eye) for k in range(K)])
                       for b in range(B)]
 
@@ -429,14 +405,10 @@ class Segmenter:
         if not isinstance(folder, ImageFolder):
             folder = ImageFolder(folder)
         device = next(self.nets[0].parameters()).device
-        modes = [n.training for n in self.nets]
-        for n in self.nets:
-            n.eval()
         self.rows, self.sample_rows, self.sample_offsets = [], [], []
         self.morph_rows, self.morph_sample_rows = [], []
-        # an image's share of the noise stream (predict_pair_samples; with views predict_pair_views: V times as much)
-        per_image = 2 * (len(self.views) if self.views is not None else 1) * self.samples * self.size * self.size
-        try:
+        per_image = V.noise_share(self.samples, self.size, len(self.views) if self.views is not None else 1)
+        with V.eval_mode(self.nets):
             for first in range(0, len(folder), self.batch_size):
                 idx = range(first, min(first + self.batch_size, len(folder)))
                 images = [folder.load(i) for i in idx]
@@ -457,9 +429,6 @@ class Segmenter:
                 r = self.back_result(image, pred, pred_oc, sizes, (disc.std, cup.std))
                 self.write(names, r.labels, r.overlays, r.rows, r.morph)
                 self.write_samples(names, r.spreads, *self.back_samples_result(disc, cup))
-        finally:
-            for n, mode in zip(self.nets, modes):
-                n.train(mode)
         return self.finish()
 
 
@@ -494,20 +463,16 @@ def segmenter_arguments(ap, args):
 
 def main(argv=None):
     import argparse
-    from .test_run import build_networks, load_checkpoint
+    from .programs import load_networks, require_gpu
     ap = argparse.ArgumentParser(prog="python -m wtpse_hip.segment", description=__doc__.split("\n\n")[0])
     add_arguments(ap)
     args = ap.parse_args(argv)
     kw = segmenter_arguments(ap, args)
-    if not torch.cuda.is_available():
-        raise SystemExit("wtpse_hip.segment needs the GPU: the networks have no CPU path")
+    require_gpu("segment")
     folder = ImageFolder(args.images)
     if len(folder) < 1:
         raise SystemExit("no image (%s) under %s" % (" ".join(EXTENSIONS), args.images))
-    device = "cuda:0"
-    torch.cuda.set_device(0)
-    nets = build_networks(device)
-    load_checkpoint(args.checkpoint, *nets)
+    nets, _ = load_networks(args.checkpoint)
     summary = Segmenter(*nets, out_dir=args.out, **kw).run(folder)
     torch.cuda.synchronize()
     print(json.dumps(summary, sort_keys=True))

@@ -9,6 +9,7 @@ pictures this run writes what the reference never did: a per-image metric table 
     O/overlay/<n>.png             the same with the contours painted
     O/per_image.csv               index, name, disc_dice, cup_dice, disc_hd, disc_asd, cup_hd, cup_asd
     O/summary.json                their means and n — equal to validate.validate_epoch on the same batches
+    O/morphometry_errors.csv      TestRun(morphometry=True) only — the command line of that switch is wtpse_hip.morphometry_run
 
 Pieces: `FundusTestBatches` (the feed: FundusSegmentation(phase='test', state='prediction') under Resize(256) / Normalize_tf /
 ToTensor with the original-size labels, fundus_dataloader.py:100-135), `load_checkpoint` (the filtered load_state_dict sequence,
@@ -39,8 +40,11 @@ import os
 import numpy as np
 import torch
 
+from . import morphometry as M
 from . import ops
+from . import tables as T
 from . import validate as V
+from .packed import fetch
 
 PAINT_OFFSETS = ((0, 0), (1, 0), (1, 1), (0, 1), (-1, 0), (-1, -1), (0, -1))       # utils.py:409-415, in statement order
 GREEN, BLUE, RED = (0, 255, 0), (0, 0, 255), (255, 0, 0)
@@ -180,25 +184,13 @@ def write_table(out_dir, rows, means):
     """rows: [{index, name, <METRIC_KEYS>}] -> out_dir/per_image.csv (floats as repr: they read back to the same float64) and
     out_dir/summary.json (the means and n)."""
     os.makedirs(out_dir, exist_ok=True)
-    with open(os.path.join(out_dir, "per_image.csv"), "w") as f:
-        f.write(",".join(CSV_COLUMNS) + "\n")
-        for r in rows:
-            name = str(r["name"])
-            if any(ch in name for ch in ',"\n'):
-                name = '"' + name.replace('"', '""') + '"'
-            f.write(",".join([str(int(r["index"])), name] + [repr(float(r[k])) for k in V.METRIC_KEYS]) + "\n")
-    with open(os.path.join(out_dir, "summary.json"), "w") as f:
-        json.dump(means, f, indent=1, sort_keys=True)
-        f.write("\n")
+    T.write_csv(os.path.join(out_dir, "per_image.csv"), CSV_COLUMNS, rows, ("index",))
+    T.write_json(os.path.join(out_dir, "summary.json"), means, allow_nan=True)           # (the only summary that may hold NaN)
 
 
 def read_table(out_dir):
     """-> (rows, means) as write_table wrote them."""
-    import csv
-    with open(os.path.join(out_dir, "per_image.csv"), newline="") as f:
-        rows = [dict(r, index=int(r["index"]), **{k: float(r[k]) for k in V.METRIC_KEYS}) for r in csv.DictReader(f)]
-    with open(os.path.join(out_dir, "summary.json")) as f:
-        return rows, json.load(f)
+    return T.read_csv(os.path.join(out_dir, "per_image.csv"), ("index",)), T.read_json(os.path.join(out_dir, "summary.json"))
 
 
 # ---- the driver -----------------------------------------------------------------------------------------------------------
@@ -210,63 +202,75 @@ def _check_side(what, v):
 class TestRun:
     """The loop of test_visulization.py:201-269 plus the metric table.  overlay / metrics pick the side the pictures / the numbers are
     computed on; both sides consume the same device predictions and the same device-resized image, so their pictures, Dice and HD95
-    are identical and ASD agrees within validate.py's 1e-12 relative."""
+    are identical and ASD agrees within validate.py's 1e-12 relative.
+
+    morphometry=True (sectors, eye: morphometry.py) also runs ops.mask_geometry + ops.onh_profile on the prediction's masks and on the
+    label's masks: `batch` appends the batch's `morphometry.finish` rows to `self.morph_pred` / `self.morph_label`, and `run` writes
+    O/morphometry_errors.csv (`self.morph_rows`, `self.morph_means`).  Off, the default, nothing more runs and nothing more is written."""
     __test__ = False                        # (the name starts with "Test": not a pytest class)
 
-    def __init__(self, model, model_shape, model_oc, model_shape_oc, out_dir, overlay="device", metrics="device"):
+    def __init__(self, model, model_shape, model_oc, model_shape_oc, out_dir, overlay="device", metrics="device", morphometry=False,
+                 sectors=24, eye=None):
         _check_side("overlay", overlay)
         _check_side("metrics", metrics)
+        self.morphometry, self.sectors, self.eye = bool(morphometry), M.check_sectors(sectors), M.check_eye(eye)
+        self.morph_pred, self.morph_label, self.morph_rows, self.morph_means = [], [], [], None
         self.nets = [model, model_shape, model_oc, model_shape_oc]
         self.out_dir, self.overlay, self.metrics = out_dir, overlay, metrics
 
     def batch(self, image, label_od, label_oc):
-        """One batch -> (per-image metric lists, original [B,h,w,3] uint8, overlay [B,h,w,3] uint8) on the host.  With both sides on the
-        device everything comes back in ONE device -> host copy."""
+        """One batch -> (per-image metric lists, original [B,h,w,3] uint8, overlay [B,h,w,3] uint8) on the host.  Everything the device
+        sides leave — the metric records, the pictures, with morphometry the two mask sets' geometry, profile and moment records —
+        comes back in ONE device -> host copy."""
         size = tuple(label_od.shape[2:])
         B = image.shape[0]
         pred, pred_oc = V.predict_pair(*self.nets, image, size)
         img = image.contiguous()
         if size != tuple(img.shape[2:]):
             img = ops.resize_bilinear(img, size)                # test_visulization.py:231-232
-        blob, masks = [], None
-        if "device" in (self.overlay, self.metrics):
+        out, masks = [], None
+        if self.morphometry or "device" in (self.overlay, self.metrics):
             masks = ops.postprocess_masks(torch.cat((pred, pred_oc), 0).contiguous())
         if self.metrics == "device":
             labels = torch.cat((label_od, label_oc), 0).to(torch.float32).contiguous()
-            blob.append(ops.seg_metrics(masks, labels).view(torch.uint8).reshape(-1))
+            out.append(ops.seg_metrics(masks, labels))
         if self.overlay == "device":
             gt = [(t == 1).to(torch.uint8).contiguous() for t in (label_od, label_oc)]
-            blob.extend(t.reshape(-1) for t in ops.overlay(img, masks[:B], masks[B:], gt[0], gt[1]))
-        host = (torch.cat(blob) if len(blob) > 1 else blob[0]).cpu().numpy() if blob else None      # the one copy
+            out.extend(ops.overlay(img, masks[:B], masks[B:], gt[0], gt[1]))
+        if self.morphometry:
+            lab = torch.cat([(t == 1).to(torch.uint8) for t in (label_od, label_oc)], 0).contiguous()
+            for mk in (masks, lab):
+                geom = ops.mask_geometry(mk)
+                out.extend((geom,) + tuple(ops.onh_profile(mk[:B], mk[B:], geom[:B], self.sectors)))
+        host = iter(fetch(out))                                 # the one copy; taken below in the order it was filled above
         host_masks = None
         if "host" in (self.overlay, self.metrics):
             host_masks = [(V.postprocess(pred[i])[0], V.postprocess(pred_oc[i])[0]) for i in range(B)]
-        off = 0
         if self.metrics == "device":
-            m = V.finish_records(host[:2 * B * 64].view(np.int64).reshape(2 * B, 8), B)
-            off = 2 * B * 64
+            m = V.finish_records(next(host), B)
         else:
             m = V.host_metrics(pred, pred_oc, label_od, label_oc, masks=host_masks)
         if self.overlay == "device":
-            n = B * size[0] * size[1] * 3
-            original, over = host[off:off + n].reshape(B, size[0], size[1], 3), host[off + n:off + 2 * n].reshape(B, size[0], size[1], 3)
+            original, over = next(host), next(host)
         else:
             lod, loc = label_od.cpu().numpy(), label_oc.cpu().numpy()
             original, over = overlay_host_batch(img.cpu().numpy(), np.stack([a for a, _ in host_masks])[:, None],
                                                 np.stack([b for _, b in host_masks])[:, None], lod, loc)
+        if self.morphometry:
+            for rows in (self.morph_pred, self.morph_label):
+                rec, prof, mom = next(host), next(host), next(host)
+                rows.extend(M.finish_batch(rec, mom, prof.view(np.uint32), size[0], size[1], self.eye))
         return m, original, over
 
     def run(self, batches):
         """batches: iterable of (image, original_od, original_oc[, names]) device tensors (FundusTestBatches) -> the means;
         `self.rows` keeps the per-image table.  Eval mode for the duration, the previous modes restored, as validate_epoch does."""
         from PIL import Image
-        modes = [n.training for n in self.nets]
-        for n in self.nets:
-            n.eval()
         for sub in ("original_image", "overlay"):
             os.makedirs(os.path.join(self.out_dir, sub), exist_ok=True)
         acc, self.rows = V.MetricMeans(), []
-        try:
+        self.morph_pred, self.morph_label, self.morph_rows, self.morph_means = [], [], [], None
+        with V.eval_mode(self.nets):
             for item in batches:
                 image, label_od, label_oc = item[:3]
                 names = item[3] if len(item) > 3 else [""] * image.shape[0]
@@ -277,11 +281,12 @@ class TestRun:
                     Image.fromarray(original[i]).save(os.path.join(self.out_dir, "original_image", "%d.png" % n))
                     Image.fromarray(over[i]).save(os.path.join(self.out_dir, "overlay", "%d.png" % n))
                     self.rows.append(dict({k: m[k][i] for k in V.METRIC_KEYS}, index=n, name=names[i]))
-        finally:
-            for n, mode in zip(self.nets, modes):
-                n.train(mode)
         means = acc.means()
         write_table(self.out_dir, self.rows, means)
+        if self.morphometry:
+            self.morph_rows = [dict(M.error_row(p, l), index=r["index"], name=r["name"])
+                               for r, p, l in zip(self.rows, self.morph_pred, self.morph_label)]
+            self.morph_means = M.write_errors_csv(self.out_dir, self.morph_rows)
         return means
 
 
@@ -299,28 +304,11 @@ def build_networks(device):
 
 
 def main(argv=None):
-    import argparse
-    from .fundus_data import FundusTree
-    ap = argparse.ArgumentParser(prog="python -m wtpse_hip.test_run", description=__doc__.split("\n\n")[0])
-    ap.add_argument("--data-dir", required=True)
-    ap.add_argument("--datasetTest", type=int, required=True, help="the target domain: Domain<N>/test is read")
-    ap.add_argument("--checkpoint", required=True, help="checkpoint_<epoch>.pth.tar as validate.Validator saves it")
-    ap.add_argument("--out", required=True)
-    ap.add_argument("--batch-size", type=int, default=9)
-    ap.add_argument("--overlay", choices=("device", "host"), default="device")
-    ap.add_argument("--metrics", choices=("device", "host"), default="device")
-    args = ap.parse_args(argv)
-    if not torch.cuda.is_available():
-        raise SystemExit("wtpse_hip.test_run needs the GPU: the networks have no CPU path")
-    device = "cuda:0"
-    torch.cuda.set_device(0)
-    nets = build_networks(device)
-    load_checkpoint(args.checkpoint, *nets)
-    tree = FundusTree(args.data_dir, phase="test", splitid=(args.datasetTest,), state="prediction")
-    if len(tree) < 1:
-        raise SystemExit("no test images under %s" % os.path.join(args.data_dir, "Domain%d" % args.datasetTest, "test"))
+    from .programs import open_test_split, test_run_parser
+    args = test_run_parser("test_run", __doc__).parse_args(argv)
+    nets, batches = open_test_split("test_run", args)
     run = TestRun(*nets, out_dir=args.out, overlay=args.overlay, metrics=args.metrics)
-    means = run.run(FundusTestBatches(tree, args.batch_size, device))
+    means = run.run(batches)
     torch.cuda.synchronize()
     print(json.dumps(means, sort_keys=True))
     return 0

@@ -15,10 +15,13 @@ import os
 
 import numpy as np
 
+from . import tables as T
+
 RATIOS = ("vcdr", "hcdr", "acdr")
 STATS = ("mean", "std", "p05", "p95")
 CSV_COLUMNS = ("index", "name", "n_samples", "n_defined") + tuple("%s_%s" % (r, s) for r in RATIOS for s in STATS) + \
     ("disc_disagree_px", "cup_disagree_px", "disc_std_mean", "cup_std_mean")
+INT_COLUMNS = ("index", "n_samples", "n_defined", "disc_disagree_px", "cup_disagree_px")
 
 
 class ShapeSamples:
@@ -110,19 +113,9 @@ def std_picture(std_disc, std_cup):
 
 
 def write_csv(out_dir, rows):
-    """rows: [{CSV_COLUMNS}] -> out_dir/uncertainty.csv, written as segment.write_measurements writes its table (floats as repr)."""
-    ints = ("index", "n_samples", "n_defined", "disc_disagree_px", "cup_disagree_px")
-    with open(os.path.join(out_dir, "uncertainty.csv"), "w") as f:
-        f.write(",".join(CSV_COLUMNS) + "\n")
-        for r in rows:
-            name = str(r["name"])
-            if any(ch in name for ch in ',"\n'):
-                name = '"' + name.replace('"', '""') + '"'
-            f.write(",".join(name if k == "name" else str(int(r[k])) if k in ints else repr(float(r[k])) for k in CSV_COLUMNS) + "\n")
+    """rows: [{CSV_COLUMNS}] -> out_dir/uncertainty.csv (tables.write_csv's form)."""
+    T.write_csv(os.path.join(out_dir, "uncertainty.csv"), CSV_COLUMNS, rows, INT_COLUMNS)
 
 
 def read_csv(out_dir):
-    import csv
-    ints = ("index", "n_samples", "n_defined", "disc_disagree_px", "cup_disagree_px")
-    with open(os.path.join(out_dir, "uncertainty.csv"), newline="") as f:
-        return [{k: v if k == "name" else int(v) if k in ints else float(v) for k, v in r.items()} for r in csv.DictReader(f)]
+    return T.read_csv(os.path.join(out_dir, "uncertainty.csv"), INT_COLUMNS)

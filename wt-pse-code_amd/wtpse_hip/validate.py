@@ -19,10 +19,32 @@ the squared surface distances HD95 interpolates between and the ASD sum, and `de
 `hd95` / `asd` do: Dice and HD95 are bitwise the host path's, ASD agrees within 1e-12 relative (a fixed-order fp64 sum where
 numpy's mean sums pairwise).  One device -> host copy per batch; both classes in one set of launches.  The default stays "host".
 """
+import contextlib
+
 import numpy as np
 import torch
 
 from . import ops
+
+
+@contextlib.contextmanager
+def eval_mode(nets):
+    """The networks in eval mode for the duration of the block, their previous modes restored whatever ends it (Trainer.py:138-141,
+    289-311)."""
+    modes = [n.training for n in nets]
+    for n in nets:
+        n.eval()
+    try:
+        yield
+    finally:
+        for n, mode in zip(nets, modes):
+            n.train(mode)
+
+
+def noise_share(n_samples, size, n_views=1):
+    """An image's share of the noise stream, in elements: 2 V K S^2 — both stages, V views, K samples of S x S normals
+    (predict_pair_samples / predict_pair_views' stream layouts).  The image at index i of a run draws from position i times this."""
+    return 2 * int(n_views) * int(n_samples) * int(size) * int(size)
 
 
 def predict_pair(model, model_shape, model_oc, model_shape_oc, data, label_size=None):
@@ -326,18 +348,11 @@ def validate_epoch(model, model_shape, model_oc, model_shape_oc, batches, metric
     label_od [B,1,h,w], label_oc [B,1,h,w]).  Eval mode for the duration, the previous modes restored (Trainer.py:138-141,289-311).
     metrics="device": post-processing and metrics on the GPU (device_metrics; the labels must be device tensors)."""
     _check_metrics(metrics)
-    nets = [model, model_shape, model_oc, model_shape_oc]
-    modes = [n.training for n in nets]
-    for n in nets:
-        n.eval()
     acc = MetricMeans()
-    try:
+    with eval_mode([model, model_shape, model_oc, model_shape_oc]):
         for image, label_od, label_oc in batches:
             pred, pred_oc = predict_pair(model, model_shape, model_oc, model_shape_oc, image, label_od.shape[2:])
             acc.add(batch_metrics(pred, pred_oc, label_od, label_oc, metrics))
-    finally:
-        for n, m in zip(nets, modes):
-            n.train(m)
     return acc.means()
 
 
@@ -385,12 +400,8 @@ def validate(model, model_shape, model_oc, model_shape_oc, batches, metrics="hos
     Puts the four networks in eval mode for the duration (Trainer.py:138-141) and restores the previous mode.
     metrics="device": post-processing and Dice on the GPU (the labels must be device tensors)."""
     _check_metrics(metrics)
-    nets = [model, model_shape, model_oc, model_shape_oc]
-    modes = [n.training for n in nets]
-    for n in nets:
-        n.eval()
     cup, disc, total = 0.0, 0.0, 0
-    try:
+    with eval_mode([model, model_shape, model_oc, model_shape_oc]):
         for image, label_od, label_oc in batches:
             pred, pred_oc = predict_pair(model, model_shape, model_oc, model_shape_oc, image, label_od.shape[2:])
             if metrics == "device":
@@ -406,7 +417,4 @@ def validate(model, model_shape, model_oc, model_shape_oc, batches, metrics="hos
                 disc += dice(postprocess(pred[i])[0], lod[i, 0])
                 cup += dice(postprocess(pred_oc[i])[0], loc[i, 0])
                 total += 1
-    finally:
-        for n, m in zip(nets, modes):
-            n.train(m)
     return cup / max(total, 1), disc / max(total, 1)
