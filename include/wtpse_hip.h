@@ -422,6 +422,24 @@ int wtpse_adam_dev(float* p, const float* g, float* m, float* v, long long n, co
 int wtpse_loss_log(const float* s0, const float* s1, const float* s2, const float* s3, const float* s4, const float* s5,
                    double* acc, int check_n, int* flag, const int* step_dev, void* stream);
 
+/* ---- weight averaging (csrc/average.hip; specification: wtpse_hip/averaging.py) --------------------------------------
+ * wtpse_avg_step folds one iterate into running means, up to four segments (a_s, p_s, n_s) in ONE launch; a segment with
+ * n_s == 0 is skipped (its pointers may be NULL).  With k = *count + 1, every element of every segment becomes
+ *     a[i] = (k == 1) ? p[i] : a[i] + (p[i] - a[i]) / (float)k
+ * in IEEE fp32: subtraction, (correctly rounded) division and addition each rounded to nearest, in that order, nothing
+ * contracted; then *count = k.  k == 1 copies: a segment is restarted by zeroing the count alone, whatever the buffers hold.
+ * gate (NULL: open) / hold (NULL: never held): one device int each; when *gate == 0 or *hold != 0 neither any a nor the count
+ * changes a bit (hold: the NaN flag of wtpse_loss_log — a poisoned run is never averaged).  The count is bumped behind the
+ * fold (a single-wave launch of its own inside this entry point), so every element of a call sees the same k; nothing that
+ * changes from step to step is passed by value: a recorded call stays valid under replay.  k <= 2^24 is the caller's to keep
+ * ((float)k is exact up to there).  Bases of non-empty segments 16-byte aligned, a_s and p_s distinct; n_s arbitrary. */
+int wtpse_avg_step(float* a0, const float* p0, long long n0, float* a1, const float* p1, long long n1, float* a2, const float* p2,
+                   long long n2, float* a3, const float* p3, long long n3, int* count, const int* gate, const int* hold, void* stream);
+/* Merges the mean `seg` of n_seg iterates into the mean `acc` of n_acc: n_acc == 0 copies; otherwise
+ * w = (float)((double)n_seg / (double)(n_acc + n_seg)), formed on the host, and acc[i] = acc[i] + (seg[i] - acc[i]) * w with the
+ * multiply and the add rounded separately.  n > 0, n_seg >= 1, both bases 16-byte aligned and distinct. */
+int wtpse_avg_merge(float* acc, const float* seg, long long n, long long n_acc, long long n_seg, void* stream);
+
 /* ---- fused 1x1 heads (csrc/head.hip) ------------------------------------------------------------------------------ */
 /* The heads 32 -> 32 (ReLU) -> 8 [-> (ReLU) -> nc] as one kernel per direction: reference algorithms.py:1006-1012
  * (mu_prior / logvar_prior, three layers, nc <= 4) and :1199-1200 (the segmentation net's `mu`, two layers: w3 = b3 = y =

@@ -178,10 +178,13 @@ class HipNet(nn.Module):
     def _finish_init(self):
         # (plain attributes, not registered with nn.Module; the step harness and the data-parallel workers set _dp, _packed_valid,
         # _attach_grads and _defer_allreduce directly)
+        # bn_momentum: the factor of the running statistics' update of every train-mode BatchNorm of this tree (nn.BatchNorm2d's
+        # default).  Passed to the kernels by value: it belongs to a recorded step.  TrainRun.averaged_checkpoint sets it to 1 / k
+        # for its k-th refitting pass (the cumulative mean of torch.optim.swa_utils.update_bn) and puts it back.
         for name, value in dict(_flat=None, _gflat=None, _gwork=None, _packed=None, _x3=None, _xdesc=None, _x16desc=None, _desc=None,
                                 _packed_version=-1, _touched=[], _noise_queue=[], _noise_seed=0x5eed, _noise_ctr=None, _dp=None,
                                 _flag=None, _packed_valid=False, _attach_grads=True, _defer_allreduce=False, _join=[],
-                                _frozen_bias={}, _frozen_pass=False).items():
+                                _frozen_bias={}, _frozen_pass=False, bn_momentum=0.1).items():
             object.__setattr__(self, name, value)
         self._convs = [m for m in self.modules() if isinstance(m, ConvP)]
         for m in self.modules():
@@ -737,7 +740,7 @@ def _bn_coeffs(root, bn, y, stats, training, tab=None, raw_amax=None, want_tape=
     if tab is None:
         tab = ops.fwd_amax_table(y.device)
     return ops.bn_finalize(stats, count, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked,
-                           act_amax=tab) + (tab,)
+                           momentum=root.bn_momentum, act_amax=tab) + (tab,)
 
 
 def convbn_fwd(conv, bn, a0, a1, relu, training, want_tape=True):
@@ -753,7 +756,7 @@ def convbn_fwd(conv, bn, a0, a1, relu, training, want_tape=True):
         t1, pro1 = Act.parts(a1)
         y, ss, mean, invstd = ops.conv_fwd_bnf(a0.t, t1, wptr, layout, conv.bias, conv.cout, conv.k, a0.pro, _relu_bits(a0, a1), pro1,
                                                bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked,
-                                               in_amax0=act_amax(a0) if layout else None,
+                                               momentum=root.bn_momentum, in_amax0=act_amax(a0) if layout else None,
                                                in_amax1=act_amax(a1) if layout == 1 else None, act_amax=tab)
     else:
         y, stats = _conv(conv, a0, a1, False, training, want_amax=not training)

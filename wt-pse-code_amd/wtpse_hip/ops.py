@@ -1002,6 +1002,32 @@ def loss_log(scalars, acc, offset, check_n, flag, step_dev):
     lib().call("wtpse_loss_log", *s, acc.data_ptr() + 8 * int(offset), int(check_n), ptr(flag), ptr(step_dev), stream_ptr())
 
 
+def avg_step(avgs, params, count, gate=None, hold=None):
+    """One iterate into the running means (wtpse_avg_step): up to four (mean, iterate) pairs of flat fp32 tensors in ONE call;
+    count: device int32 (iterates folded so far; bumped behind the fold); gate / hold: optional device int32 — *gate == 0 or
+    *hold != 0 leaves means and count untouched."""
+    if len(avgs) != len(params) or not 1 <= len(avgs) <= 4:
+        raise ValueError("avg_step: one to four (mean, iterate) pairs, got %d / %d" % (len(avgs), len(params)))
+    args = []
+    for a, p in zip(avgs, params):
+        _chk(a, "mean"); _chk(p, "iterate")
+        if a.numel() != p.numel():
+            raise ValueError("avg_step: a mean of %d elements for an iterate of %d" % (a.numel(), p.numel()))
+        args += [ptr(a), ptr(p), a.numel()]
+    args += [0, 0, 0] * (4 - len(avgs))
+    lib().call("wtpse_avg_step", *args, ptr(count), ptr(gate), ptr(hold), stream_ptr())
+
+
+def avg_merge(acc, seg, n_acc, n_seg):
+    """acc (the mean of n_acc iterates) <- the mean of the n_acc + n_seg iterates that acc and seg (the mean of n_seg) cover, in
+    place (wtpse_avg_merge); n_acc == 0 copies.  -> acc."""
+    _chk(acc, "acc"); _chk(seg, "seg")
+    if acc.numel() != seg.numel():
+        raise ValueError("avg_merge: %d elements against %d" % (acc.numel(), seg.numel()))
+    lib().call("wtpse_avg_merge", ptr(acc), ptr(seg), acc.numel(), int(n_acc), int(n_seg), stream_ptr())
+    return acc
+
+
 # ----------------------------------------------------------------------------------------------- validation back half
 def _chk_dev(t, name, dtype):
     if not (t.is_cuda and t.dtype == dtype and t.is_contiguous() and t.dim() == 4 and t.shape[1] == 1):

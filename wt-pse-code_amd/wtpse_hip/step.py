@@ -182,14 +182,21 @@ class TrainStep:
     update() samples as in training either way), every BatchNorm normalises with its running statistics, which are never written,
     and the backward runs the frozen folds (wtpse_hip/nn.py: _bn_bwd): fine-tuning a trained checkpoint on a few images.  The mode
     is part of a recorded step; step() refuses to run when a network's mode is not the one the step was built for.  It is an
-    argument of its own: hparams['freeze_bn'] (which the reference ships and never reads) is NOT looked at."""
+    argument of its own: hparams['freeze_bn'] (which the reference ships and never reads) is NOT looked at.
+    average: optional `averaging.WeightAverage` over the networks this step trains, in NET_KEYS order (two when
+    hparams['whitening'] is false).  The schedule then ends with ONE more call behind the last Adam launch (wtpse_avg_step: every
+    network's new parameters folded into the running means; held by the log's flag like Adam), which lands in the last recorded
+    stretch.  Averaging observes and never perturbs: parameters, moments and buffers are those of a step without it.  Without one
+    (the default) nothing is issued."""
 
     def __init__(self, model_od, shape_od, model_oc, shape_oc, hparams, lr=5e-4, betas=(0.9, 0.99), dp=None, graph=False, log=None,
-                 freeze_bn=False):
+                 freeze_bn=False, average=None):
         self.hp = hparams
         self.freeze_bn = bool(freeze_bn)
         if self.freeze_bn and dp is not None:
             raise ValueError("freeze_bn=True is not supported together with data-parallel training (dp=)")
+        if average is not None and dp is not None:
+            raise ValueError("average= is not supported together with data-parallel training (dp=)")
         self.full = bool(hparams['whitening'])
         self.nets = [model_od, model_oc] + ([shape_od, shape_oc] if self.full else [])
         self.model_od, self.shape_od, self.model_oc, self.shape_oc = model_od, shape_od, model_oc, shape_oc
@@ -209,6 +216,12 @@ class TrainStep:
         self.by_key = {k: n for k, n in zip(NET_KEYS, (model_od, shape_od, model_oc, shape_oc)) if any(n is x for x in self.nets)}
         # (keyed by network, looked up by id() everywhere: its order — NET_KEYS', not self.nets' — carries no meaning)
         self.opt = {id(self.by_key[k]): FlatAdam(self.by_key[k], r, betas) for k, r in zip(NET_KEYS, lrs) if k in self.by_key}
+        self.average = average
+        if average is not None:
+            trained = [self.by_key[k] for k in NET_KEYS if k in self.by_key]
+            if len(average.nets) != len(trained) or any(a is not b for a, b in zip(average.nets, trained)):
+                raise ValueError("average= must be a WeightAverage over the %d networks this step trains, in the order %s"
+                                 % (len(trained), [k for k in NET_KEYS if k in self.by_key]))
         self.log = log
         if log is not None:
             want = self.log_names(hparams)
@@ -287,6 +300,8 @@ class TrainStep:
             res.update(ins_oc=rc["ins"], dom_oc=rc["dom"])
             rd = yield from self._shape_call(self.shape_oc, self.model_oc, roi, target_oc)
             res.update(kd_oc=rd["kd"], ins_shape_oc=rd["ins_total"], dom_shape_oc=rd["dom"])
+        if self.average is not None:     # behind the last Adam launch: the iterate this step has produced, all networks in one call
+            self.average.update(hold=self.log.flag if self.log is not None else None)
         return res
 
     @staticmethod
@@ -444,6 +459,8 @@ class TrainStep:
             for dst, src in zip(self._static, (image, target_od, target_oc)):
                 if dst.data_ptr() != src.data_ptr():
                     dst.copy_(src)
+            if self.average is not None:
+                self.average.tick()         # the recorded update() executes once per replay
             self._replay()
             return self._result
         gen = self._schedule(image, target_od, target_oc, noise or {})

@@ -11,6 +11,11 @@ What differs from the reference loop, and why it cannot change a result:
     holds every later Adam launch (wtpse_adam_dev's `hold`): from the failing iteration on no parameter and no Adam moment
     changes, and `train_epoch()` raises the reference's ValueError, naming the iteration, when it reads the log.  The flag is read
     before every validation and before every file this module writes: nothing is ever written from a poisoned run.
+  * averaged weights (SWAD; `TrainRun(swad=...)`, off by default).  The one exception to "no host synchronisation inside an epoch":
+    every `swad_every`-th iteration the run stops at ONE point to evaluate — it reads the NaN flag, the loss of the current weights and
+    the count of the segment it takes (three small copies at the same point; the first one drains the stream) — and goes on.  Between
+    evaluations the running means are kept by one more launch per step (wtpse_avg_step, part of the recorded step), with no host
+    contact.  Once the loss valley is closed no further evaluation runs.
   * no tensorboard scalars, image grids, `code/` snapshot or yaml dump.
 
 Data-parallel runs are not covered here (`TrainStep`'s own `dp` path is).
@@ -24,8 +29,10 @@ from bisect import bisect_right
 import numpy as np
 import torch
 
+from . import ops
+from .averaging import LossValley, WeightAverage
 from .step import NET_KEYS, TrainStep
-from .validate import best_checkpoint
+from .validate import best_checkpoint, eval_mode, predict_pair
 
 CKPT_KEYS = ("model", "model_shape", "model_oc", "model_oc_shape")     # Trainer.py:282-288, in the order (od, od_shape, oc, oc_shape)
 
@@ -167,11 +174,32 @@ class TrainRun:
     checkpoint_every: write out_dir/run_checkpoint.pth.tar after every that many epochs (0: never).
     freeze_bn: train on frozen BatchNorm statistics (TrainStep(freeze_bn=True)): train_epoch() keeps the networks in eval mode, the
     running statistics never change.  Part of config(), so load() restores it; a checkpoint from before the flag loads as False.
+    swad: an `averaging.LossValley` switches dense weight averaging on (None, the default: off — not one launch, allocation or host
+    read is added).  The step then keeps the running mean of every iterate since the last evaluation on the device
+    (`averaging.WeightAverage`), and after every `swad_every`-th iteration of the run (> 0) train_epoch() evaluates: check() for the NaN
+    flag, the loss of the CURRENT weights in eval mode, `average.take()`, `swad.observe(...)`, `close_gate()` once the valley is
+    closed (no evaluation runs after that), and the networks go back to their training mode.
+    swad_loss(run) -> float: the loss of an evaluation.  Default: over `swad_batches` — a sequence, or a callable returning an iterable,
+    of (image, target_od, target_oc) in the training format at the network's size — the mean of bce_sigmoid_fwd(disc logits,
+    target_od) + bce_sigmoid_fwd(cup logits, target_oc) on `validate.predict_pair`'s logits (the cup's behind the ROI mask), summed
+    on the device and read once.  One of the two must be given.
+    train() ends by writing out_dir/swad_checkpoint.pth.tar (`averaged_checkpoint()`) and out_dir/swad.csv; config() carries the
+    valley's parameters and swad_every, state() / restore() the WeightAverage's and the LossValley's state: a resumed run writes the
+    same swad_checkpoint bit for bit.  A checkpoint from before the field loads with swad off; one that carries swad state is refused
+    by a run without swad.
     """
+
+    swad, swad_every, average = None, 0, None        # averaging is off unless the constructor switches it on
 
     def __init__(self, model_od, shape_od, model_oc, shape_oc, hparams, next_batch, iter_per_epoch, max_epoch, lr=(1e-3, 1e-3, 1e-3, 1e-3),
                  stop_epoch=-1, val_batches=None, validator=None, interval_validate=10, lr_schedule=None, out_dir=None, graph="plan",
-                 seed=0, checkpoint_every=0, betas=(0.9, 0.99), freeze_bn=False):
+                 seed=0, checkpoint_every=0, betas=(0.9, 0.99), freeze_bn=False, swad=None, swad_every=0, swad_batches=None, swad_loss=None):
+        if isinstance(swad, dict):                  # a saved config()'s form of the valley's parameters ({}: off)
+            swad = LossValley(**swad) if swad else None
+        if swad is not None and int(swad_every) <= 0:
+            raise ValueError("swad needs swad_every > 0 (iterations between two evaluations), got %r" % (swad_every,))
+        if swad is not None and swad_batches is None and swad_loss is None:
+            raise ValueError("swad needs a swad_batches feed (or a swad_loss of its own) to evaluate the current weights on")
         if lr_schedule not in (None, "reference"):
             raise ValueError("lr_schedule must be None or 'reference', got %r" % (lr_schedule,))
         if (val_batches is None) != (validator is None):
@@ -189,8 +217,13 @@ class TrainRun:
             next_batch.set_seed(self.seed)
         device = next(model_od.parameters()).device
         self.log = LossLog(device, TrainStep.log_names(hparams))
+        self.swad, self.swad_every, self.swad_batches, self.swad_loss = swad, int(swad_every) if swad is not None else 0, swad_batches, swad_loss
+        self.average = None
+        if swad is not None:
+            full = bool(hparams['whitening'])
+            self.average = WeightAverage([n for k, n in zip(NET_KEYS, self.nets) if full or k in ("od", "oc")])
         self.train_step = TrainStep(model_od, shape_od, model_oc, shape_oc, hparams, lr=self.base_lr, betas=betas, graph=graph, log=self.log,
-                                    freeze_bn=self.freeze_bn)
+                                    freeze_bn=self.freeze_bn, average=self.average)
         self.epoch = 0                 # epochs completed = index of the epoch train_epoch() runs next
         self.iteration = 0             # iterations completed
         self.last = None               # what the last train_epoch() returned
@@ -218,9 +251,11 @@ class TrainRun:
                 n.train(not self.freeze_bn)
         start = time.perf_counter()
         self.log.reset()
-        for _ in range(self.iter_per_epoch):
+        for i in range(self.iter_per_epoch):
             image, target_od, target_oc = self.next_batch(self.py_rng, self.np_rng)
             self.train_step.step(image, target_od, target_oc)
+            if self.swad is not None and not self.swad.closed and (self.iteration + i + 1) % self.swad_every == 0:
+                self._swad_evaluate(self.iteration + i + 1)
         sums, flag = self.log.read()
         self._raise_if_nan(flag)
         self.iteration += self.iter_per_epoch
@@ -239,12 +274,140 @@ class TrainRun:
         self.epoch += 1
         return self.last
 
+    # ------------------------------------------------------------------------------------------------ averaged weights
+    def _swad_default_loss(self):
+        if any(n is None for n in self.nets):
+            raise ValueError("the default swad loss predicts with all four networks: pass swad_loss= for a run without shape networks")
+        batches = self.swad_batches() if callable(self.swad_batches) else self.swad_batches
+        total = torch.zeros((), dtype=torch.float64, device=self.log.acc.device)
+        n = 0
+        for image, target_od, target_oc in batches:
+            pred, pred_oc = predict_pair(*self.nets, image)
+            total += ops.bce_sigmoid_fwd(pred, target_od.contiguous()).double()
+            total += ops.bce_sigmoid_fwd(pred_oc, target_oc.contiguous()).double()
+            n += 1
+        if n == 0:
+            raise ValueError("swad_batches is empty")
+        return float(total.item()) / n
+
+    def _swad_evaluate(self, iteration):
+        """One evaluation, `iteration` iterations into the run (the one point inside an epoch at which the host waits for the device)."""
+        self.check()
+        with eval_mode([n for n in self.nets if n is not None]):
+            loss = float(self.swad_loss(self)) if self.swad_loss is not None else self._swad_default_loss()
+        segment, count = self.average.take()
+        self.swad.observe(segment, count, loss, iteration)
+        if self.swad.closed:
+            self.average.close_gate()
+
+    def _forward_only(self, image, target_od, target_oc):
+        """The forward halves of calls A-D as TrainStep._schedule issues them, on the networks as they stand, tapes dropped: what a
+        train-mode pass does to the BatchNorm running statistics and nothing else.  The teacher pass inside calls B and D runs with
+        its segmentation network in eval mode, so every BatchNorm sees the batch exactly once."""
+        model_od, shape_od, model_oc, shape_oc = self.nets
+        image = image.contiguous()
+        res, tape = model_od._forward_update(image, target_od, image, want_tape=True)
+        del tape
+        out = res[0]
+        if shape_od is not None and self.train_step.full:
+            with eval_mode([model_od]):
+                _, tape = shape_od._forward_update(model_od, image, target_od, want_tape=True)
+            del tape
+        roi, _ = ops.roi(image, out)
+        res, tape = model_oc._forward_update(roi, target_oc, roi, want_tape=True)
+        del tape, res
+        if shape_oc is not None and self.train_step.full:
+            with eval_mode([model_oc]):
+                _, tape = shape_oc._forward_update(model_oc, roi, target_oc, want_tape=True)
+            del tape
+
+    def averaged_checkpoint(self, bn_batches=None):
+        """-> the four-key dict of `best_checkpoint` for the AVERAGED weights plus "swad": {converged, start, end, iterates, threshold,
+        losses, iterations, evaluations} (`LossValley.result()`'s info).
+
+        The averaged flats are copied into the live flat buffers in place (a recorded step stays valid) and the packed weights are
+        refreshed; every BatchNorm's running statistics are reset and refitted over `bn_batches` (default: iter_per_epoch) train-mode,
+        forward-only passes of calls A-D (`_forward_only`), batch k with the factor 1 / k — the cumulative mean over the batches, which
+        is torch.optim.swa_utils.update_bn, the pass SWAD runs on its averaged model.  The batches come from `next_batch` with fresh
+        generators seeded seed + 1.  A freeze_bn run trains on statistics it never writes: it keeps them (no refit).
+        Afterwards everything the run owns is put back bit for bit: parameters, buffers, packed weights, Philox positions, the feed's
+        state(); Adam's state and the run's two host generators are not touched at all.  Synchronises."""
+        if self.swad is None:
+            raise ValueError("this run does not average (TrainRun(swad=...))")
+        self.check()
+        tensors, info = self.swad.result()
+        nets = self.average.nets
+        bn_batches = self.iter_per_epoch if bn_batches is None else int(bn_batches)
+        feed_state = self.next_batch.state() if hasattr(self.next_batch, "state") else None
+        saved = []
+        for n in nets:
+            saved.append(dict(flat=n.flat_params().clone(), packed=n._packed.clone(), x3=n._x3.clone(), version=n._packed_version,
+                              bufs=[b.clone() for b in n.buffers()], ctr=n._noise_ctr.clone(), momentum=n.bn_momentum,
+                              modes=[(m, m.training) for m in n.modules()]))
+        try:
+            for n, avg in zip(nets, tensors):
+                n.flat_params().copy_(avg)
+                n.invalidate_packed()
+                n.ensure_ready(repack=True)
+            if not self.freeze_bn and bn_batches > 0:
+                for n in nets:
+                    n.train(True)
+                    for m in n.modules():
+                        if isinstance(getattr(m, "running_mean", None), torch.Tensor) and hasattr(m, "num_batches_tracked"):
+                            m.running_mean.zero_()
+                            m.running_var.fill_(1.0)
+                            m.num_batches_tracked.zero_()
+                py_rng, np_rng = random.Random(self.seed + 1), np.random.RandomState(self.seed + 1)
+                for k in range(1, bn_batches + 1):
+                    for n in nets:
+                        object.__setattr__(n, "bn_momentum", 1.0 / k)
+                    self._forward_only(*self.next_batch(py_rng, np_rng))
+            d = {key: {name: v.detach().clone() for name, v in n.state_dict().items()}
+                 for key, n in zip(CKPT_KEYS, self.nets) if n is not None}
+            d["swad"] = info
+        finally:
+            for n, sv in zip(nets, saved):
+                object.__setattr__(n, "bn_momentum", sv["momentum"])
+                for m, mode in sv["modes"]:
+                    m.training = mode
+                n.flat_params().copy_(sv["flat"])
+                n._packed.copy_(sv["packed"])
+                n._x3.copy_(sv["x3"])
+                object.__setattr__(n, "_packed_version", sv["version"])
+                for b, old in zip(n.buffers(), sv["bufs"]):
+                    b.copy_(old)
+                n._noise_ctr.copy_(sv["ctr"])
+            if feed_state is not None:
+                self.next_batch.load_state(feed_state)
+            torch.cuda.synchronize()
+        return d
+
+    def write_swad(self):
+        """out_dir/swad_checkpoint.pth.tar (averaged_checkpoint(): loads wherever a best-Dice checkpoint does) and out_dir/swad.csv
+        (one line per evaluation: evaluation, iteration, loss, held / merged / outside).  Nothing is written from a poisoned run (the
+        reference's ValueError) or before the first evaluation."""
+        if self.swad is None or self.out_dir is None or not self.swad.losses:
+            return
+        d = self.averaged_checkpoint()
+        path = os.path.join(self.out_dir, "swad_checkpoint.pth.tar")
+        tmp = "%s.tmp%d" % (path, os.getpid())
+        torch.save(d, tmp)
+        os.replace(tmp, path)
+        path = os.path.join(self.out_dir, "swad.csv")
+        tmp = "%s.tmp%d" % (path, os.getpid())
+        with open(tmp, "w", newline="") as f:
+            w = csv.writer(f)
+            w.writerow(["evaluation", "iteration", "loss", "status"])
+            w.writerows([[e, it, repr(loss), status] for e, it, loss, status in self.swad.table()])
+        os.replace(tmp, path)
+
     # ------------------------------------------------------------------------------------------------ the run
     def train(self):
         """Trainer.py:1025-1056 in its order: train the epoch; stop when `stop_epoch == epoch` (before its validation); the
         schedule; validate when (epoch + 1) % interval_validate == 0 and epoch > 2.  -> the six best values in the reference's
         order [cup_dice, cup_hd, cup_asd, disc_dice, disc_hd, disc_asd] (zeros while no validation has improved;
-        they travel with a checkpoint, so a resumed run that finds no new best returns the earlier one)."""
+        they travel with a checkpoint, so a resumed run that finds no new best returns the earlier one).  With swad, the run ends
+        (also at stop_epoch) by writing the averaged checkpoint and its table (`write_swad`)."""
         for epoch in range(self.epoch, self.max_epoch):
             self.train_epoch()
             if self.stop_epoch == epoch:
@@ -262,13 +425,15 @@ class TrainRun:
                     self.best = [float(v) for v in r[1:]]
             if self.checkpoint_every > 0 and self.out_dir is not None and (epoch + 1) % self.checkpoint_every == 0:
                 self.save(os.path.join(self.out_dir, "run_checkpoint.pth.tar"))
+        self.write_swad()
         return list(self.best)
 
     # ------------------------------------------------------------------------------------------------ checkpoints
     def config(self):
         return {"lr": list(self.base_lr), "iter_per_epoch": self.iter_per_epoch, "max_epoch": self.max_epoch, "stop_epoch": self.stop_epoch,
                 "interval_validate": self.interval_validate, "lr_schedule": self.lr_schedule or "", "seed": self.seed,
-                "checkpoint_every": self.checkpoint_every, "graph": self.graph, "betas": list(self.betas), "freeze_bn": self.freeze_bn}
+                "checkpoint_every": self.checkpoint_every, "graph": self.graph, "betas": list(self.betas), "freeze_bn": self.freeze_bn,
+                "swad": self.swad.config() if self.swad is not None else {}, "swad_every": self.swad_every}
 
     @staticmethod
     def config_kwargs(config):
@@ -278,6 +443,8 @@ class TrainRun:
         cfg["lr_schedule"] = cfg["lr_schedule"] or None
         cfg["lr"], cfg["betas"] = tuple(cfg["lr"]), tuple(cfg["betas"])
         cfg["freeze_bn"] = bool(cfg.get("freeze_bn", False))
+        cfg["swad"] = LossValley(**cfg["swad"]) if cfg.get("swad") else None      # (a checkpoint from before the field: off)
+        cfg["swad_every"] = int(cfg.get("swad_every", 0))
         return cfg
 
     def state(self):
@@ -295,6 +462,8 @@ class TrainRun:
                  loss_sums=dict(self.last["sums"]) if self.last is not None else {},
                  loss_names=list(self.log.names), best=list(self.best),
                  feed=self.next_batch.state() if hasattr(self.next_batch, "state") else {})
+        if self.swad is not None:
+            d["swad_state"] = {"average": self.average.state(), "valley": self.swad.state()}
         return d
 
     def save(self, path):
@@ -335,6 +504,12 @@ class TrainRun:
                 raise ValueError("the checkpoint carries the state of its batch feed (%s) and this run's next_batch cannot take it"
                                  % sorted(d["feed"]))
             self.next_batch.load_state(d["feed"])
+        if d.get("swad_state"):
+            if self.swad is None:
+                raise ValueError("the checkpoint carries the state of its weight averaging (swad) and this run does not average: "
+                                 "construct it with swad=")
+            self.average.load_state(d["swad_state"]["average"])
+            self.swad.load_state(d["swad_state"]["valley"], device=self.log.acc.device)
         path = os.path.join(self.out_dir, "train_log.csv") if self.out_dir is not None else None
         if path is not None and os.path.isfile(path):
             with open(path, newline="") as f:
