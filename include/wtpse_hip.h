@@ -524,6 +524,22 @@ int wtpse_aug_warp(const unsigned char* img, const unsigned char* mask, const do
 int wtpse_aug_photometric(unsigned char* img, const unsigned char* lut, const int* rect, const int* pts, const int* pt_off,
                           const int* pt_val, int max_pts, int N, int S, void* stream);
 
+/* ---- amplitude mixing between source domains (csrc/spectrum.hip) ---------------------------------------------------------
+ * The optional stage between the augmentations (or the crop) and wtpse_input_finish; input_pipeline.amplitude_mix_host is its
+ * float64 specification.  img [N][S][S][3] uint8; a row n with 0 <= partner[n] < N keeps the phase of its 2-D spectrum F per
+ * channel and moves its amplitude towards that of row partner[n] (spectrum G, always of the INPUT) inside the window |k_y| <= b,
+ * |k_x| <= b of signed frequencies in [-S/2, S/2 - 1]:  D = lam[n] (|G| - |F|) F / |F| there (F / |F| = 1 where |F| = 0), 0
+ * outside;  y = x + real(ifft2(D));  out_u8 = rint(clip(y, 0, 255)), half to even; out_f32 (may be NULL) = y.  Any other
+ * partner[n] (-1) copies the row.  fp32 arithmetic; lam = 0 and partner[n] = n return the input bit for bit; no atomics: the same
+ * result on every run.  S: a power of two from 32 to 512; 0 <= b <= S/2 (b = S/2: the whole spectrum); N <= 65535.
+ * twiddle [S][2] = (cos, -sin)(2 pi t / S), computed in double precision and rounded once.  work: 16-byte aligned,
+ * wtpse_amix_workspace(N, S, b) floats.  img != out_u8.  Three launches: row transforms (two real rows per complex transform,
+ * columns u <= b kept), column transforms + D + inverse column transforms, inverse row transforms + store. */
+/* floats of workspace a call needs: 4 * N * 3 * (b + 1) * S; -1 for a shape wtpse_amplitude_mix refuses.  Host only. */
+int wtpse_amix_workspace(int N, int S, int b);
+int wtpse_amplitude_mix(const unsigned char* img, const int* partner, const float* lam, const float* twiddle,
+                        unsigned char* out_u8, float* out_f32, float* work, int N, int S, int b, void* stream);
+
 /* ---- validation back half (csrc/postprocess.hip) --------------------------------------------------- */
 /* utils.postprocessing (utils.py:267-329) bit for bit: logit [B][h][w] fp32 -> out [B][h][w] uint8 = the largest 8-connected
  * component of sigmoid(logit) > threshold (ties: the first in raster order), holes (background not 4-connected to the border)

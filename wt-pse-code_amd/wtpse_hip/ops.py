@@ -1324,3 +1324,40 @@ def paste_u8(canvas, patch, top, left):
         raise ValueError("paste_u8: |top|, |left| must not exceed 2^24 (got %r, %r)" % (top, left))
     lib().call("wtpse_paste_u8", ptr(canvas), ptr(patch), H, W, C, h, w, top, left, stream_ptr())
     return canvas
+
+
+# ----------------------------------------------------------------------------------------------- amplitude mixing
+_TWIDDLES = {}
+
+
+def amplitude_mix(img, partner, lam, b, want_float=False):
+    """[N,S,S,3] uint8 on the device, partner [N] int (-1: leave the row alone) and lam [N] float on the host, b = half width of the
+    frequency window -> the batch with the amplitude of every row that has a partner moved towards its partner's (csrc/spectrum.hip;
+    input_pipeline.amplitude_mix_host is the specification); with want_float also the unrounded fp32 values [N,S,S,3]."""
+    from .input_pipeline import _check_mix_size, twiddle_table
+    import numpy as np
+    _chk_u8(img, "img", 4)
+    N, S = int(img.shape[0]), int(img.shape[1])
+    if img.shape[2] != S or img.shape[3] != 3 or not 1 <= N <= 65535:
+        raise ValueError("amplitude_mix: img must be [N,S,S,3] with 1 <= N <= 65535 (got %s)" % (tuple(img.shape),))
+    _check_mix_size(S)
+    b = int(b)
+    partner, lam = np.asarray(partner), np.asarray(lam, np.float64)
+    if partner.shape != (N,) or lam.shape != (N,) or partner.dtype.kind not in "iu" or not np.all(np.isfinite(lam)):
+        raise ValueError("amplitude_mix: partner must be [%d] integers and lam [%d] finite floats" % (N, N))
+    if partner.min() < -1 or partner.max() >= N or not 0 <= b <= S // 2:
+        raise ValueError("amplitude_mix: partner indices must lie in -1 .. %d and b in 0 .. %d (got b = %r)" % (N - 1, S // 2, b))
+    nfloats = lib().query("wtpse_amix_workspace", N, S, b)
+    if nfloats < 0:
+        raise ValueError("amplitude_mix: a [%d,%d,%d,3] batch with b = %d needs more workspace than one call can take" % (N, S, S, b))
+    dev = img.device
+    tw = _TWIDDLES.get((str(dev), S))
+    if tw is None:
+        tw = _TWIDDLES[(str(dev), S)] = torch.from_numpy(twiddle_table(S)).to(dev)
+    work = workspace("amix", nfloats, dev)
+    dpartner = torch.from_numpy(partner.astype(np.int32)).to(dev, non_blocking=True)
+    dlam = torch.from_numpy(lam.astype(np.float32)).to(dev, non_blocking=True)
+    out = torch.empty_like(img)
+    outf = torch.empty(img.shape, dtype=torch.float32, device=dev) if want_float else None
+    lib().call("wtpse_amplitude_mix", ptr(img), ptr(dpartner), ptr(dlam), ptr(tw), ptr(out), ptr(outf), ptr(work), N, S, b, stream_ptr())
+    return (out, outf) if want_float else out

@@ -86,12 +86,23 @@ class FundusBatches:
     and eraser draw from the numpy generator too — the draws interleave per sample: index, crop, augmentations.  The elastic
     transform's uniform fields come from the device Philox stream `noise_seed` (TrainRun sets it to the run seed: `set_seed`) at a
     running position, which is feed state as well: `state()` carries it as "noise_pos", and a state saved before the field existed
-    loads with position 0."""
+    loads with position 0.
 
-    def __init__(self, datasets, batch_size, device, size=256, augment=None, pipe=None):
-        from .input_pipeline import DeviceInputPipeline
+    style: an `input_pipeline.AmplitudeMix` switches the amplitude-mixing stage on (None: off — not one launch, allocation or draw
+    is added).  A batch is assembled domain-major, so every sample has partners from the other domains next to it; the stage's
+    draws (`draw_mix`) come from the numpy generator AFTER all of the batch's other draws: every stream is what it is without the
+    stage up to that point.  The stage keeps no state of its own — the generator, which TrainRun's checkpoints carry, is all of it.
+    It needs at least two source domains and a side that is a power of two from 32 to 512 (ValueError here)."""
+
+    def __init__(self, datasets, batch_size, device, size=256, augment=None, pipe=None, style=None):
+        from .input_pipeline import DeviceInputPipeline, _check_mix_size
         self.augment = augment
+        self.style = style
         self.datasets = list(datasets)
+        if style is not None:
+            if len(self.datasets) < 2:
+                raise ValueError("amplitude mixing needs at least two source domains, got %d" % len(self.datasets))
+            _check_mix_size(int(size))
         self.order = list(range(len(self.datasets)))
         # Trainer.py:1011: per_domain_batch = batch_size // source_domain_num — a batch holds domains * per_domain samples
         # (30 for the reference's batch_size 32 over three source domains)
@@ -112,7 +123,10 @@ class FundusBatches:
         py_rng.shuffle(self.order)
         if self.augment is None:
             images, masks = multi_batch([self.datasets[i] for i in self.order], self.per_domain, np_rng)
-            return self.pipe(images, masks, [draw(py_rng, self.size) for _ in images])
+            draws = [draw(py_rng, self.size) for _ in images]
+            if self.style is None:
+                return self.pipe(images, masks, draws)
+            return self.pipe(images, masks, draws, mix_draws=self._mix_draws(np_rng))
         images, masks, draws, aug_draws = [], [], [], []
         for i in self.order:
             for _ in range(self.per_domain):
@@ -121,7 +135,14 @@ class FundusBatches:
                 masks += mask
                 draws.append(draw(py_rng, self.size))
                 aug_draws.append(draw_augment(py_rng, np_rng, self.size, self.augment))
-        return self.pipe(images, masks, draws, aug_draws)
+        if self.style is None:
+            return self.pipe(images, masks, draws, aug_draws)
+        return self.pipe(images, masks, draws, aug_draws, mix_draws=self._mix_draws(np_rng))
+
+    def _mix_draws(self, np_rng):
+        from .input_pipeline import draw_mix
+        partner, lam = draw_mix(np_rng, len(self.datasets), self.per_domain, self.style)
+        return partner, lam, self.style.band(self.size)
 
     def set_seed(self, seed):
         """The seed of the elastic transform's noise stream (TrainRun calls this with the run seed)."""
