@@ -238,6 +238,14 @@ int wtpse_conv_wgrad_r_bn(const float* g, const float* bn_y, const float* bn_coe
 int wtpse_bn_finalize(const float* stats_partial, int nblk, int C, long long count, const float* gamma, const float* beta,
                       float* running_mean, float* running_var, long long* num_batches, float momentum, float eps,
                       float* scale_shift, float* save_mean, float* save_invstd, unsigned* act_amax, void* stream);
+/* eval mode on TARGET statistics (wtpse_hip/adapt.py holds the float64 specification): fold the partials of this call (count values
+ * per channel), pool them with acc [C][2] = (sum, sum^2) over the acc_count values of earlier calls (NULL / 0: no history; with acc,
+ * the pooled sums are left there), blend mean and biased variance with the running ones at weight w in [0, 1] (w = 1: the target's
+ * alone) -> scale_shift [C][2].  Optional: moments [C][4] = (mean_t, var_t, mean_b, var_b), div [C] = KL(N_t || N_s), act_amax (ZERO on
+ * entry) = twice the Samuelson bound of |scale y + shift| over this call.  The running buffers are read, never written. */
+int wtpse_bn_finalize_blend(const float* stats_partial, int nblk, int C, long long count, const float* gamma, const float* beta,
+                            const float* running_mean, const float* running_var, double w, float eps, double* acc, double acc_count,
+                            float* scale_shift, double* moments, double* div, unsigned* act_amax, void* stream);
 /* act_amax (the WHOLE table is written: it need not be zero) = bound of |scale_shift[c][0] * y + scale_shift[c][1]| over a tensor y whose
  * amax table is raw_amax: max_c |scale| * amax + |shift| — the x2h input bound of an activation behind an eval-mode BatchNorm. */
 int wtpse_act_bound(const float* scale_shift, int C, const unsigned* raw_amax, unsigned* act_amax, void* stream);

@@ -12,16 +12,14 @@
 // partial rows (the 8192-tile convolutions, the upsampling kernels) — every row is then read in ONE round of eight loads per thread:
 // the launch sits between two convolutions of a dependency chain (54 + 40 times per step with its backward twin) and its 9 us were
 // four rounds of strided loads that miss this XCD's L2 (the partials were written by workgroups all over the chip)
+//
+// bn_fold_partials: the fold itself, shared by bn_finalize_k and bn_finalize_blend_k (one text: the two cannot drift apart) — every
+// thread of the workgroup calls; lane-strided loads, butterfly within the wave, the waves in order; thread 0 returns with the sums
 template <int NT>
-__global__ __launch_bounds__(NT) void bn_finalize_k(const float* __restrict__ part, int nblk, int C, double count,
-                                                    const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                    float* __restrict__ rmean, float* __restrict__ rvar,
-                                                    long long* __restrict__ nbt, float momentum, float eps,
-                                                    float* __restrict__ scale_shift, float* __restrict__ save_mean,
-                                                    float* __restrict__ save_invstd, unsigned* __restrict__ act_amax) {
+__device__ __forceinline__ void bn_fold_partials(const float* __restrict__ part, int nblk, int C, int c, int t, double& s1, double& s2) {
   __shared__ double shs[2][NT / 64];
-  const int c = blockIdx.x, t = threadIdx.x;
-  double s1 = 0.0, s2 = 0.0;
+  s1 = 0.0;
+  s2 = 0.0;
   for (int k0 = t; k0 < nblk; k0 += NT * 8) {
     float2 p2[8];
 #pragma unroll
@@ -51,6 +49,20 @@ __global__ __launch_bounds__(NT) void bn_finalize_k(const float* __restrict__ pa
       s1 += shs[0][w];
       s2 += shs[1][w];
     }
+  }
+}
+
+template <int NT>
+__global__ __launch_bounds__(NT) void bn_finalize_k(const float* __restrict__ part, int nblk, int C, double count,
+                                                    const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                    float* __restrict__ rmean, float* __restrict__ rvar,
+                                                    long long* __restrict__ nbt, float momentum, float eps,
+                                                    float* __restrict__ scale_shift, float* __restrict__ save_mean,
+                                                    float* __restrict__ save_invstd, unsigned* __restrict__ act_amax) {
+  const int c = blockIdx.x, t = threadIdx.x;
+  double s1, s2;
+  bn_fold_partials<NT>(part, nblk, C, c, t, s1, s2);
+  if (t == 0) {
     double mean = s1 / count;
     double var = s2 / count - mean * mean;
     if (var < 0.0) var = 0.0;
@@ -67,6 +79,66 @@ __global__ __launch_bounds__(NT) void bn_finalize_k(const float* __restrict__ pa
       rvar[c] = (float)((1.0 - momentum) * rvar[c] + momentum * unbiased);
     }
     if (nbt && c == 0) *nbt += 1;
+  }
+}
+
+// Eval-mode BatchNorm on TARGET statistics (wtpse_hip/adapt.py is the float64 specification): this call's partials, pooled with the
+// sums of earlier calls (acc [C][2], acc_count pixels; null / 0: no history), blended with the running ("source") statistics at weight
+// w — mean_b = (1 - w) mean_s + w mean_t, likewise the variances — and turned into (scale, shift).  The running buffers are only read.
+// moments [C][4] = (mean_t, var_t, mean_b, var_b); div [C] = KL(N_t || N_s); both optional.  With acc, thread 0 of the channel leaves
+// the pooled sums there after reading them (plain stores: the launches of one stream serialise).
+// act_amax: |scale y + shift| <= |gamma| invstd (sqrt(var_call (M - 1)) + |mean_call - mean_b|) + |beta| over THIS call's M values
+// (Samuelson's inequality about the call's own mean), times 2: E[x^2] - mean^2 can undershoot the call's variance.
+template <int NT>
+__global__ __launch_bounds__(NT) void bn_finalize_blend_k(const float* __restrict__ part, int nblk, int C, double count,
+                                                          const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                          const float* __restrict__ rmean, const float* __restrict__ rvar,
+                                                          double w, float eps, double* __restrict__ acc, double acc_count,
+                                                          float* __restrict__ scale_shift, double* __restrict__ moments,
+                                                          double* __restrict__ div, unsigned* __restrict__ act_amax) {
+  const int c = blockIdx.x, t = threadIdx.x;
+  double s1, s2;
+  bn_fold_partials<NT>(part, nblk, C, c, t, s1, s2);
+  if (t == 0) {
+    double p1 = s1, p2 = s2;
+    if (acc) {
+      p1 += acc[2 * c];
+      p2 += acc[2 * c + 1];
+      acc[2 * c] = p1;
+      acc[2 * c + 1] = p2;
+    }
+    const double n = acc_count + count;
+    double mean = p1 / n;
+    double var = p2 / n - mean * mean;
+    if (var < 0.0) var = 0.0;
+    const double mean_s = rmean[c], var_s = rvar[c];
+    const double mean_b = (1.0 - w) * mean_s + w * mean;
+    const double var_b = (1.0 - w) * var_s + w * var;
+    double invstd = 1.0 / sqrt(var_b + (double)eps);
+    float sc = (float)(gamma[c] * invstd);
+    scale_shift[2 * c] = sc;
+    scale_shift[2 * c + 1] = (float)(beta[c] - mean_b * gamma[c] * invstd);
+    if (moments) {
+      moments[4 * c] = mean;
+      moments[4 * c + 1] = var;
+      moments[4 * c + 2] = mean_b;
+      moments[4 * c + 3] = var_b;
+    }
+    if (div) {
+      const double vs = var_s + (double)eps, vt = var + (double)eps, dm = mean - mean_s;
+      div[c] = 0.5 * (log(vs / vt) + (vt + dm * dm) / vs - 1.0);
+    }
+    if (act_amax) {
+      const double mean_c = s1 / count;
+      double var_c = s2 / count - mean_c * mean_c;
+      if (var_c < 0.0) var_c = 0.0;
+      const double dev = sqrt(var_c * (count > 1.0 ? count - 1.0 : 1.0)) + fabs(mean_c - mean_b);
+      // (clamped to the largest float: a bound beyond it would enter the table as inf, which the consumers' x3_scale_from_amax reads
+      // as "no scale" (1) like any unknown amax — the finite maximum gives them the smallest scale instead; an activation of that size
+      // overflows the fp16 split either way and fails loudly there)
+      const double bound = 2.0 * (fabs((double)gamma[c]) * invstd * dev + fabs((double)beta[c]));
+      amax_put(act_amax, (float)fmin(bound, 3.4028234663852886e38), (unsigned)c);
+    }
   }
 }
 
@@ -450,6 +522,21 @@ extern "C" int wtpse_bn_finalize(const float* stats_partial, int nblk, int C, lo
     hipLaunchKernelGGL(bn_finalize_k<256>, dim3(C), dim3(256), 0, (hipStream_t)stream, stats_partial, nblk, C, (double)count,
                        gamma, beta, running_mean, running_var, num_batches, momentum, eps, scale_shift, save_mean,
                        save_invstd, act_amax);
+  return wtpse_status();
+}
+
+extern "C" int wtpse_bn_finalize_blend(const float* stats_partial, int nblk, int C, long long count, const float* gamma,
+                                       const float* beta, const float* running_mean, const float* running_var, double w, float eps,
+                                       double* acc, double acc_count, float* scale_shift, double* moments, double* div,
+                                       unsigned* act_amax, void* stream) {
+  WTPSE_REQUIRE(stats_partial && gamma && beta && running_mean && running_var && scale_shift && nblk > 0 && C > 0 && count > 0);
+  WTPSE_REQUIRE(w >= 0.0 && w <= 1.0 && acc_count >= 0.0 && (acc != nullptr || acc_count == 0.0));
+  if (nblk >= 2048)
+    hipLaunchKernelGGL(bn_finalize_blend_k<1024>, dim3(C), dim3(1024), 0, (hipStream_t)stream, stats_partial, nblk, C, (double)count,
+                       gamma, beta, running_mean, running_var, w, eps, acc, acc_count, scale_shift, moments, div, act_amax);
+  else
+    hipLaunchKernelGGL(bn_finalize_blend_k<256>, dim3(C), dim3(256), 0, (hipStream_t)stream, stats_partial, nblk, C, (double)count,
+                       gamma, beta, running_mean, running_var, w, eps, acc, acc_count, scale_shift, moments, div, act_amax);
   return wtpse_status();
 }
 

@@ -181,10 +181,12 @@ class HipNet(nn.Module):
         # bn_momentum: the factor of the running statistics' update of every train-mode BatchNorm of this tree (nn.BatchNorm2d's
         # default).  Passed to the kernels by value: it belongs to a recorded step.  TrainRun.averaged_checkpoint sets it to 1 / k
         # for its k-th refitting pass (the cumulative mean of torch.optim.swa_utils.update_bn) and puts it back.
+        # bn_blend: None, or an adapt.BlendState — every EVAL-mode BatchNorm of this tree then runs on this call's statistics, pooled
+        # and blended with the running ones (adapt.py; _blend_state below).  Eager only; train mode ignores it.
         for name, value in dict(_flat=None, _gflat=None, _gwork=None, _packed=None, _x3=None, _xdesc=None, _x16desc=None, _desc=None,
                                 _packed_version=-1, _touched=[], _noise_queue=[], _noise_seed=0x5eed, _noise_ctr=None, _dp=None,
                                 _flag=None, _packed_valid=False, _attach_grads=True, _defer_allreduce=False, _join=[],
-                                _frozen_bias={}, _frozen_pass=False, bn_momentum=0.1).items():
+                                _frozen_bias={}, _frozen_pass=False, bn_momentum=0.1, bn_blend=None).items():
             object.__setattr__(self, name, value)
         self._convs = [m for m in self.modules() if isinstance(m, ConvP)]
         for m in self.modules():
@@ -721,12 +723,32 @@ def _wgrad(layer, dy, a0, a1=None, with_bias=True):
 
 
 # ---- conv + BatchNorm (+ReLU): the result stays virtual (raw conv output + per-channel scale/shift) --------------
-def _bn_coeffs(root, bn, y, stats, training, tab=None, raw_amax=None, want_tape=False):
+def _blend_state(root, training, want_tape):
+    """The adapt.BlendState an eval-mode conv + BatchNorm layer of `root` runs under, or None (no switch, or train mode: the batch's
+    own statistics rule there).  What the blended path does not do raises here, before anything is launched."""
+    blend = root.bn_blend
+    if blend is None or training:
+        return None
+    if want_tape:
+        raise RuntimeError("bn_blend: no backward through blended BatchNorm statistics (call update() outside adapt.blended)")
+    if root.bn_synced:
+        raise RuntimeError("bn_blend is not supported together with synchronised BatchNorm")
+    if ops.lib()._rec is not None:
+        raise RuntimeError("bn_blend is eager only: it cannot be recorded into a launch plan")
+    return blend
+
+
+def _bn_coeffs(root, bn, y, stats, training, tab=None, raw_amax=None, want_tape=False, blend=None):
     """-> (ss, mean, invstd, tab): scale / shift of the BatchNorm over y and the amax table of its output (x2h).  Train mode: from
     the (sum, sum^2) partials `stats`, exchanged first where BatchNorm is synchronised; tab: the zeroed table to fill (None: one is
     taken here).  Eval mode: from the running statistics; the bound follows from raw_amax, the amax table of the data, if known.
     With a tape, mean / invstd are then the running mean and 1 / sqrt(running_var + eps): what the frozen folds of the backward take
-    in place of the batch statistics (the same launch emits them)."""
+    in place of the batch statistics (the same launch emits them).
+    Eval mode under `blend` (_blend_state): from the partials `stats` again, pooled and blended with the running statistics by
+    wtpse_bn_finalize_blend; the bound comes out of that launch (no look at the data), the running buffers are not written."""
+    if blend is not None:
+        tab = ops.fwd_amax_table(y.device)
+        return blend.finalize(bn, y, stats, tab), None, None, tab
     if not training:
         if want_tape:
             ss, mean, invstd = ops.bn_eval_coeffs_stats(bn.weight, bn.bias, bn.running_mean, bn.running_var)
@@ -750,6 +772,7 @@ def convbn_fwd(conv, bn, a0, a1, relu, training, want_tape=True):
     # (x2h) the bound of the activated output travels with it to its consumers: from the statistics' fold in train mode
     # (|gamma| sqrt(N - 1) + |beta|: common.h, bn_act_bound), from the stored data's amax behind an eval-mode BatchNorm
     tab = ops.fwd_amax_table(a0.t.device) if training else None
+    blend = _blend_state(root, training, want_tape)
     if training and BN_TAIL and not root.bn_synced:
         # the convolution finishes its own statistics (csrc/common.h: bnf_tail): no finalize launch
         layout, wptr = _weights(conv, wide=a1 is not None)
@@ -759,8 +782,9 @@ def convbn_fwd(conv, bn, a0, a1, relu, training, want_tape=True):
                                                momentum=root.bn_momentum, in_amax0=act_amax(a0) if layout else None,
                                                in_amax1=act_amax(a1) if layout == 1 else None, act_amax=tab)
     else:
-        y, stats = _conv(conv, a0, a1, False, training, want_amax=not training)
-        ss, mean, invstd, tab = _bn_coeffs(root, bn, y, stats, training, tab, getattr(y, "wt_amax", None), want_tape)
+        stats_wanted = training or blend is not None        # (under blend the conv leaves its partials as in train mode, and no amax)
+        y, stats = _conv(conv, a0, a1, False, stats_wanted, want_amax=not stats_wanted)
+        ss, mean, invstd, tab = _bn_coeffs(root, bn, y, stats, training, tab, getattr(y, "wt_amax", None), want_tape, blend)
     z = Act(y, ss, relu, tab)
     if not want_tape:
         return z, None
@@ -859,10 +883,12 @@ CONVU_CONV_FIRST = os.environ.get("WTPSE_CONVU_REFERENCE_ORDER", "0") != "1"    
 
 def upbn_fwd(conv, bn, a0, training, want_tape=True):
     root = conv._root
-    z, _ = _conv(conv, a0, None, False, False, want_amax=not training)      # low resolution, pre-BatchNorm
+    blend = _blend_state(root, training, want_tape)
+    stats_wanted = training or blend is not None
+    z, _ = _conv(conv, a0, None, False, False, want_amax=not stats_wanted)      # low resolution, pre-BatchNorm
     # (bilinear interpolation is a convex combination: the upsampled map is bounded by the amax of the low-resolution one)
-    y, stats = ops.upsample2x_fwd_stats(z) if training else (ops.upsample2x_fwd(z), None)
-    ss, mean, invstd, tab = _bn_coeffs(root, bn, y, stats, training, None, getattr(z, "wt_amax", None), want_tape)
+    y, stats = ops.upsample2x_fwd_stats(z) if stats_wanted else (ops.upsample2x_fwd(z), None)
+    ss, mean, invstd, tab = _bn_coeffs(root, bn, y, stats, training, None, getattr(z, "wt_amax", None), want_tape, blend)
     out = Act(y, ss, True, tab)
     if not want_tape:
         return out, None

@@ -472,6 +472,21 @@ def bn_finalize(stats, count, gamma, beta, rmean, rvar, nbt, momentum=0.1, eps=1
     return ss, mean, invstd
 
 
+def bn_finalize_blend(stats, count, gamma, beta, rmean, rvar, w, eps=1e-5, acc=None, acc_count=0, moments=None, div=None, act_amax=None):
+    """Eval-mode scale / shift on target statistics (include/wtpse_hip.h, wtpse_bn_finalize_blend; adapt.py is the specification): the
+    partials `stats` of this call's `count` values per channel, pooled with acc (float64 [C,2], updated in place; acc_count values seen
+    before) and blended with the running statistics at weight w.  rmean / rvar are read only.  moments (float64 [C,4]), div (float64
+    [C]) and act_amax (a zeroed amax table) are filled when given.  -> ss [C,2]."""
+    nblk, C, _ = stats.shape
+    for t, shape in ((acc, (C, 2)), (moments, (C, 4)), (div, (C,))):
+        if t is not None and not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == shape):
+            raise ValueError("bn_finalize_blend: acc / moments / div must be contiguous float64 device tensors [C,2] / [C,4] / [C]")
+    ss = torch.empty((C, 2), dtype=torch.float32, device=stats.device)
+    lib().call("wtpse_bn_finalize_blend", ptr(stats), nblk, C, int(count), ptr(gamma), ptr(beta), ptr(rmean), ptr(rvar), float(w),
+               float(eps), ptr(acc), float(acc_count), ptr(ss), ptr(moments), ptr(div), ptr(act_amax), stream_ptr())
+    return ss
+
+
 def bn_eval_coeffs(gamma, beta, rmean, rvar, eps=1e-5):
     C = gamma.numel()
     ss = torch.empty((C, 2), dtype=torch.float32, device=gamma.device)

@@ -4,6 +4,7 @@ cup-to-disc ratios.  The test run (test_run.py) scores a labelled split; this is
 
     python -m wtpse_hip.segment --images DIR --checkpoint C --out O [--batch-size 9] [--no-overlay] [--samples K --seed S --sample-scale X]
                                 [--morphometry [--sectors N] [--eye right|left]] [--views none|id|hflip|flips|d4|<codes>]
+                                [--adapt none|batch|stream [--prior 16]]
 
     O/mask/<stem>.png        mode 'L', the image's own size, grey levels 0 (cup) / 128 (disc) / 255 (background): the dataset's
                              label encoding — FundusTree and FundusTestBatches read it as a label
@@ -43,6 +44,11 @@ over the V views' deterministic predictions with --samples 0, over the V K sampl
 summary.json is the number of maps merged; sample v K + k is sample k of view v).  summary.json gains views, the code list.  The
 image at folder index i draws from position 2 V K S^2 i of the stream; the cost is V passes of both U-Nets.
 
+With --adapt batch|stream (Segmenter(adapt=..., prior=N0); none, the default, changes nothing) the eval-mode BatchNorm layers run on the
+images' own statistics blended with the checkpoint's (adapt.py): per network batch, or pooled over the run in folder order.  The
+predictions then depend on the images that share the batch (and, for stream, on those before it); --adapt stream refuses --views,
+whose every view would be pooled as one more image.  summary.json gains adapt and prior.  A checkpoint from wtpse_hip.adapt needs no switch.
+
 Front (`Segmenter.front`): the decoded uint8 images go to the GPU as they are; the LANCZOS resize to 256 x 256 — FundusTree's
 Image.resize((S, S), Image.LANCZOS), bit for bit — is two passes of wtpse_resample_u8 with `resample_table(..., "lanczos")`, batched
 over the images of one size, a pass whose axis already has the target length skipped as Pillow skips it; wtpse_image_finish
@@ -63,6 +69,7 @@ import os
 import numpy as np
 import torch
 
+from . import adapt as A
 from . import morphometry as M
 from . import ops
 from . import tables as T
@@ -201,7 +208,7 @@ class Segmenter:
     previous modes restored.  front / back are the two halves around validate.predict_pair."""
 
     def __init__(self, model, model_shape, model_oc, model_shape_oc, out_dir, batch_size=9, overlay=True, size=256, samples=0, seed=0,
-                 scale=1.0, morphometry=False, sectors=24, eye=None, views=None):
+                 scale=1.0, morphometry=False, sectors=24, eye=None, views=None, adapt=None, prior=A.DEFAULT_PRIOR):
         self.morphometry, self.sectors, self.eye = bool(morphometry), M.check_sectors(sectors), M.check_eye(eye)
         self.morph_rows, self.morph_sample_rows = [], []
         if int(batch_size) < 1:
@@ -211,6 +218,9 @@ class Segmenter:
         if 2 * int(batch_size) * int(samples) >= 8192:
             raise ValueError("batch_size * samples must stay below 4096 (one set of post-processing launches per batch)")
         self.views = VW.parse(views)
+        self.adapt, self.prior = A.check_adapt(adapt, self.views), float(prior)
+        if self.adapt is not None and not self.prior >= 0.0:
+            raise ValueError("prior must not be negative (got %r)" % (prior,))
         if self.views is not None:
             n_views = len(self.views)
             if n_views * int(samples) > VW.MAX_MAPS:
@@ -390,6 +400,8 @@ class Segmenter:
             summary.update(n_samples=self.n_maps, mean_vcdr_std=float(np.mean(np.array(vals, np.float64))) if vals else None)
         if self.views is not None:
             summary.update(views=list(self.views))
+        if self.adapt is not None:
+            summary.update(adapt=self.adapt, prior=self.prior)
         if self.morphometry:
             summary.update(M.summarise(self.morph_rows, self.eye), sectors=self.sectors)
         write_measurements(self.out_dir, self.rows, summary)
@@ -408,7 +420,7 @@ class Segmenter:
         self.rows, self.sample_rows, self.sample_offsets = [], [], []
         self.morph_rows, self.morph_sample_rows = [], []
         per_image = V.noise_share(self.samples, self.size, len(self.views) if self.views is not None else 1)
-        with V.eval_mode(self.nets):
+        with V.eval_mode(self.nets), A.blended(self.nets, A.make_state(self.adapt, self.prior)):
             for first in range(0, len(folder), self.batch_size):
                 idx = range(first, min(first + self.batch_size, len(folder)))
                 images = [folder.load(i) for i in idx]
@@ -448,6 +460,7 @@ def add_arguments(ap, images_help=None):
     ap.add_argument("--eye", choices=("right", "left"), default=None, help="which eye the crops show: fills nasal / temporal / isnt")
     ap.add_argument("--views", default="none", help="test-time views to merge: none, id, hflip, flips, d4 or a comma list of codes 0..7 "
                                                     "(0 first): uncertainty/ and uncertainty.csv over the views")
+    A.add_adapt_arguments(ap)
 
 
 def segmenter_arguments(ap, args):
@@ -455,10 +468,16 @@ def segmenter_arguments(ap, args):
     M.check_sectors(args.sectors)
     try:
         views = VW.parse(args.views)
+        adapt = A.check_adapt(args.adapt, views)
+        if args.prior < 0:
+            raise ValueError("--prior must not be negative")
     except ValueError as e:
         ap.error(str(e))
-    return dict(batch_size=args.batch_size, overlay=not args.no_overlay, samples=args.samples, seed=args.seed, scale=args.sample_scale,
-                morphometry=args.morphometry, sectors=args.sectors, eye=args.eye, views=views)
+    kw = dict(batch_size=args.batch_size, overlay=not args.no_overlay, samples=args.samples, seed=args.seed, scale=args.sample_scale,
+              morphometry=args.morphometry, sectors=args.sectors, eye=args.eye, views=views)
+    if adapt is not None:                   # (off: the keywords are what they were)
+        kw.update(adapt=adapt, prior=args.prior)
+    return kw
 
 
 def main(argv=None):
