@@ -425,10 +425,28 @@ int wtpse_adam_dev(float* p, const float* g, float* m, float* v, long long n, co
  * s0..s5: device fp32 scalars (trailing ones may be NULL); for every non-NULL sj: acc[j] += (double)*sj — the reference's
  * `running += loss.item()`, so a double accumulator fed in iteration order holds its running sums bit for bit.
  * NaN test on the first check_n scalars, in fp32 and in the reference's order: check_n = 3: isnan((s0 + s1) + s2) (inf + -inf
- * counts), 1: isnan(s0), 0: none.  flag: two device ints, sticky (never cleared here): when the test holds and flag[0] == 0,
+ * counts), 1: isnan(s0), 0: none.  check_n | 16 (17, 19): the scalar behind those, s1 or s3, is added last and tested with them (the
+ * boundary term of TrainStep(boundary=): isnan(s0 + s1), isnan(((s0 + s1) + s2) + s3)).  flag: two device ints, sticky (never cleared here): when the test holds and flag[0] == 0,
  * flag[0] = 1 and flag[1] = *step_dev (the calling network's count of completed steps = the failing iteration; NULL: 0). */
 int wtpse_loss_log(const float* s0, const float* s1, const float* s2, const float* s3, const float* s4, const float* s5,
                    double* acc, int check_n, int* flag, const int* step_dev, void* stream);
+
+/* ---- boundary loss (csrc/boundary.hip; specification: wtpse_hip/boundary.py) ---------------------------------------------
+ * wtpse_signed_distance: the signed distance map of B label planes t [B][h][w] fp32 (nonzero = object, as wtpse_seg_metrics takes
+ * a label).  Per plane, with pos = {t != 0}: d2_out[p] = min over q in pos of |p - q|^2 and d2_in[p] = min over q outside pos,
+ * exact integers (-1 where the set is empty); phi[p] = sqrt(d2_out[p]) outside, 1 - sqrt(d2_in[p]) inside (Kervadec's
+ * one_hot2dist: edt(neg) neg - (edt(pos) - 1) pos), and phi = 0 on a plane without a contour (pos empty or everything; recognised
+ * on the device).  phi is float32 of the float64 expression, bit for bit.  d2_out / d2_in: int32 [B][h][w] or NULL (not wanted).
+ * ws: wtpse_signed_distance_ws(B, h, w) 4-byte words (<= 0: unsupported size; 1 <= h, w <= 4096).  Two launches, no atomics,
+ * nothing read by the host: results do not depend on scheduling.
+ * wtpse_boundary_loss: *loss = (1/n) sum_i sigmoid(x_i m_i) phi_i (mask NULL: m = 1), block partials (wtpse_reduce_blocks(n)
+ * floats) folded in a fixed order; the weight is NOT applied to it.  With dx != NULL the same pass adds the gradient of
+ * (*alpha_dev) * loss into dx in place: dx_i += (*alpha_dev) / n * phi_i * s_i (1 - s_i) * m_i.  alpha_dev: one device float (a
+ * schedule changes the weight of a recorded call between replays); may be NULL when dx is. */
+int wtpse_signed_distance_ws(int B, int h, int w);
+int wtpse_signed_distance(const float* t, float* phi, int* d2_out, int* d2_in, void* ws, int B, int h, int w, void* stream);
+int wtpse_boundary_loss(const float* x, const float* mask, const float* phi, const float* alpha_dev, long long n, float* partial,
+                        float* loss, float* dx, void* stream);
 
 /* ---- weight averaging (csrc/average.hip; specification: wtpse_hip/averaging.py) --------------------------------------
  * wtpse_avg_step folds one iterate into running means, up to four segments (a_s, p_s, n_s) in ONE launch; a segment with

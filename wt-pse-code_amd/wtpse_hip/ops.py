@@ -987,6 +987,45 @@ def mse_bwd(a, b, g=None, w=1.0):
     return da
 
 
+def signed_distance(t, want_d2=False):
+    """The signed distance map of every label plane of `t` (device fp32, [..., h, w], nonzero = object): phi of the same shape —
+    boundary.signed_distance_host per plane, bit for bit float32 of it (wtpse_signed_distance).  want_d2: -> (phi, d2_out, d2_in)
+    with the two exact squared-distance maps (int32, -1 where the set is empty)."""
+    _chk(t, "t")
+    if t.dim() < 2:
+        raise ValueError("signed_distance: label planes [..., h, w], got shape %s" % (tuple(t.shape),))
+    h, w = int(t.shape[-2]), int(t.shape[-1])
+    B = t.numel() // max(h * w, 1)
+    L = lib()
+    words = L.query("wtpse_signed_distance_ws", B, h, w)
+    if words <= 0:
+        raise ValueError("signed_distance: unsupported size %s (1 <= h, w <= 4096)" % (tuple(t.shape),))
+    phi = torch.empty_like(t)
+    d2_out = torch.empty(t.shape, dtype=torch.int32, device=t.device) if want_d2 else None
+    d2_in = torch.empty(t.shape, dtype=torch.int32, device=t.device) if want_d2 else None
+    ws = workspace("signed_distance", words, t.device)
+    L.call("wtpse_signed_distance", ptr(t), ptr(phi), ptr(d2_out), ptr(d2_in), ptr(ws), B, h, w, stream_ptr())
+    return (phi, d2_out, d2_in) if want_d2 else phi
+
+
+def boundary_loss(x, phi, alpha_dev, mask=None, dx=None):
+    """-> the unweighted boundary loss mean(sigmoid(x * mask) * phi) (0-dim device fp32; mask None: the disc form).  With dx the same
+    launch adds (*alpha_dev) / n * phi * s (1 - s) [* mask] into dx IN PLACE (alpha_dev: device fp32 scalar, read by the kernel)."""
+    _chk(x, "x"); _chk(phi, "phi"); _chk(mask, "mask"); _chk(dx, "dx"); _chk(alpha_dev, "alpha_dev")
+    n = x.numel()
+    for name, v in (("phi", phi), ("mask", mask), ("dx", dx)):
+        if v is not None and v.numel() != n:
+            raise ValueError("boundary_loss: %s has %d elements, x has %d" % (name, v.numel(), n))
+    if dx is not None and alpha_dev is None:
+        raise ValueError("boundary_loss: dx needs the device weight alpha_dev")
+    # phi reaches several hundred: an amax table that describes the region loss's gradient alone no longer bounds dx
+    _amax_stale(dx)
+    loss = torch.empty((), dtype=torch.float32, device=x.device)
+    lib().call("wtpse_boundary_loss", ptr(x), ptr(mask), ptr(phi), ptr(alpha_dev), n, ptr(_red_ws(n, x.device)), ptr(loss), ptr(dx),
+               stream_ptr())
+    return loss
+
+
 def roi(image, logit):
     B, C, H, W = image.shape
     out = torch.empty_like(image)

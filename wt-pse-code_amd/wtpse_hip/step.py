@@ -187,16 +187,26 @@ class TrainStep:
     hparams['whitening'] is false).  The schedule then ends with ONE more call behind the last Adam launch (wtpse_avg_step: every
     network's new parameters folded into the running means; held by the log's flag like Adam), which lands in the last recorded
     stretch.  Averaging observes and never perturbs: parameters, moments and buffers are those of a step without it.  Without one
-    (the default) nothing is issued."""
+    (the default) nothing is issued.
+    boundary: optional `boundary.BoundaryLoss`: the objective of calls A and C becomes L_seg + alpha * L_B, L_B = mean(sigmoid(logit) *
+    phi) with phi the signed distance map of the call's target (the cup call on the ROI-masked logits, as its region loss).  Each of
+    the two calls then computes phi of its target (wtpse_signed_distance) and, behind the region loss's gradient, issues ONE
+    wtpse_boundary_loss that yields the unweighted L_B (`bd_od` / `bd_oc` of the result and of the log) and adds alpha's share into
+    that gradient — all in the call's own chain, so it is part of a recorded step.  alpha is a device float
+    (`set_boundary_weight`: a stream-ordered write that the next replay picks up, like the learning rates); it starts at
+    boundary.weight_at(0).  Without one (the default) not one launch or buffer is added and the names are unchanged."""
 
     def __init__(self, model_od, shape_od, model_oc, shape_oc, hparams, lr=5e-4, betas=(0.9, 0.99), dp=None, graph=False, log=None,
-                 freeze_bn=False, average=None):
+                 freeze_bn=False, average=None, boundary=None):
         self.hp = hparams
         self.freeze_bn = bool(freeze_bn)
         if self.freeze_bn and dp is not None:
             raise ValueError("freeze_bn=True is not supported together with data-parallel training (dp=)")
         if average is not None and dp is not None:
             raise ValueError("average= is not supported together with data-parallel training (dp=)")
+        if boundary is not None and dp is not None:
+            raise ValueError("boundary= is not supported together with data-parallel training (dp=)")
+        self.boundary = boundary
         self.full = bool(hparams['whitening'])
         self.nets = [model_od, model_oc] + ([shape_od, shape_oc] if self.full else [])
         self.model_od, self.shape_od, self.model_oc, self.shape_oc = model_od, shape_od, model_oc, shape_oc
@@ -224,13 +234,18 @@ class TrainStep:
                                  % (len(trained), [k for k in NET_KEYS if k in self.by_key]))
         self.log = log
         if log is not None:
-            want = self.log_names(hparams)
+            want = self.log_names(hparams, boundary=boundary is not None)
             if list(log.names) != want:
-                raise ValueError("the loss log's names must be TrainStep.log_names(hparams) = %s, got %s" % (want, list(log.names)))
+                raise ValueError("the loss log's names must be TrainStep.log_names(hparams%s) = %s, got %s"
+                                 % (", boundary=True" if boundary is not None else "", want, list(log.names)))
         for o in self.opt.values():
             o.ready()
             o.hold = None if log is None else log.flag
         self.last_od_pred = None
+        self._bd_weight, self.bd_alpha = None, None
+        if boundary is not None:
+            self._bd_weight = float(boundary.weight_at(0))
+            self.bd_alpha = torch.full((1,), self._bd_weight, dtype=torch.float32, device=next(model_od.parameters()).device)
         # exact data-parallel mode runs ~100 small collectives inside every forward: it stays eager
         self.graph = bool(graph) and not (dp is not None and dp.exact)
         self.plan = self.graph and graph == "plan"
@@ -258,8 +273,12 @@ class TrainStep:
         r = {"seg": loss}
         if self.full:
             r["ins"], r["dom"] = res[2][0], res[2][3]
+        check_n = len(r)
+        if self.boundary is not None:       # alpha * L_B on top: its gradient joins the region loss's, its value the call's NaN test
+            r["bd"] = ops.boundary_loss(out, ops.signed_distance(target.contiguous()), self.bd_alpha, mask=od_pred, dx=d_out)
+            check_n |= 16
         # the reference's running sums and NaN test of this call (Trainer.py:788-800 / 874-885), in front of backward and Adam
-        self._log("seg_od" if od_pred is None else "seg_oc", list(r.values()), len(r), model)
+        self._log("seg_od" if od_pred is None else "seg_oc", list(r.values()), check_n, model)
         model._backward_update(tape, d_out, None, None, w_ins=gi, w_dom=gd)
         del tape
         yield model
@@ -289,6 +308,9 @@ class TrainStep:
         res = {"seg_od": ra["seg"]}
         if self.full:
             res.update(ins_od=ra["ins"], dom_od=ra["dom"])
+        if self.boundary is not None:
+            res["bd_od"] = ra["bd"]
+        if self.full:
             rb = yield from self._shape_call(self.shape_od, self.model_od, image, target_od)
             res.update(kd_od=rb["kd"], ins_shape_od=rb["ins_total"], ins_ij_od=rb["ins_off"], ins_ii_od=rb["ins_diag"],
                        dom_shape_od=rb["dom"])
@@ -298,6 +320,9 @@ class TrainStep:
         res["seg_oc"] = rc["seg"]
         if self.full:
             res.update(ins_oc=rc["ins"], dom_oc=rc["dom"])
+        if self.boundary is not None:
+            res["bd_oc"] = rc["bd"]
+        if self.full:
             rd = yield from self._shape_call(self.shape_oc, self.model_oc, roi, target_oc)
             res.update(kd_oc=rd["kd"], ins_shape_oc=rd["ins_total"], dom_shape_oc=rd["dom"])
         if self.average is not None:     # behind the last Adam launch: the iterate this step has produced, all networks in one call
@@ -305,12 +330,19 @@ class TrainStep:
         return res
 
     @staticmethod
-    def log_names(hparams):
-        """The loss names in the order a LossLog for this step holds them: the keys of step()'s result, call by call (A-D)."""
+    def log_names(hparams, boundary=False):
+        """The loss names in the order a LossLog for this step holds them: the keys of step()'s result, call by call (A-D).
+        boundary: with the boundary term's `bd_od` / `bd_oc`, each directly behind the last name of its call (A / C), so that the
+        call's one wtpse_loss_log launch covers it."""
         if not bool(hparams['whitening']):
-            return ["seg_od", "seg_oc"]
-        return ["seg_od", "ins_od", "dom_od", "kd_od", "ins_shape_od", "ins_ij_od", "ins_ii_od", "dom_shape_od",
-                "seg_oc", "ins_oc", "dom_oc", "kd_oc", "ins_shape_oc", "dom_shape_oc"]
+            names = ["seg_od", "seg_oc"]
+        else:
+            names = ["seg_od", "ins_od", "dom_od", "kd_od", "ins_shape_od", "ins_ij_od", "ins_ii_od", "dom_shape_od",
+                     "seg_oc", "ins_oc", "dom_oc", "kd_oc", "ins_shape_oc", "dom_shape_oc"]
+        if boundary:
+            for last, new in (("dom_od", "bd_od"), ("dom_oc", "bd_oc")) if bool(hparams['whitening']) else (("seg_od", "bd_od"), ("seg_oc", "bd_oc")):
+                names.insert(names.index(last) + 1, new)
+        return names
 
     def _log(self, first, scalars, check_n, net):
         """One wtpse_loss_log launch: `scalars` into the log's slots that start at name `first`."""
@@ -398,11 +430,30 @@ class TrainStep:
         """{network key: rate} as last set (host values)."""
         return {k: self.opt[id(n)].lr for k, n in self.by_key.items()}
 
+    def set_boundary_weight(self, a):
+        """The boundary term's weight alpha from the next step on, recorded or not: a stream-ordered write of the device float the
+        kernel reads (rounded to fp32), no host sync."""
+        if self.boundary is None:
+            raise ValueError("this TrainStep has no boundary term (TrainStep(boundary=...))")
+        a = float(a)
+        if not (a >= 0.0 and a != float("inf")):
+            raise ValueError("the boundary weight must be a finite number >= 0, got %r" % (a,))
+        self._bd_weight = a
+        self.bd_alpha.fill_(a)
+
+    def get_boundary_weight(self):
+        """The weight as last set (the host value; None without a boundary term)."""
+        return self._bd_weight
+
     def state_dict(self):
         """What a run needs beside the networks' own state_dict()s to continue where it stopped: per network the optimiser state
-        (torch.optim.Adam's layout, FlatAdam.state_dict) and the Philox seed and position of its sampling noise.  Synchronises."""
-        return {"optim": {k: self.opt[id(n)].state_dict() for k, n in self.by_key.items()},
-                "noise": {k: {"seed": int(n._noise_seed), "ctr": int(n._noise_ctr.item())} for k, n in self.by_key.items()}}
+        (torch.optim.Adam's layout, FlatAdam.state_dict) and the Philox seed and position of its sampling noise; with a boundary term
+        its current weight.  Synchronises."""
+        sd = {"optim": {k: self.opt[id(n)].state_dict() for k, n in self.by_key.items()},
+              "noise": {k: {"seed": int(n._noise_seed), "ctr": int(n._noise_ctr.item())} for k, n in self.by_key.items()}}
+        if self.boundary is not None:
+            sd["boundary_weight"] = float(self._bd_weight)
+        return sd
 
     def load_state_dict(self, sd):
         """Restores everything in place (moments, step counts, learning rates, Philox positions), so a step that has already been
@@ -422,6 +473,8 @@ class TrainStep:
             n.ensure_ready()
             object.__setattr__(n, "_noise_seed", int(sd["noise"][k]["seed"]))
             n._noise_ctr.fill_(int(sd["noise"][k]["ctr"]))
+        if self.boundary is not None and "boundary_weight" in sd:
+            self.set_boundary_weight(sd["boundary_weight"])
 
     def close(self):
         """Release the native launch plans (and their hipEvents) of a recorded step."""

@@ -208,13 +208,23 @@ class TrainRun:
     valley's parameters and swad_every, state() / restore() the WeightAverage's and the LossValley's state: a resumed run writes the
     same swad_checkpoint bit for bit.  A checkpoint from before the field loads with swad off; one that carries swad state is refused
     by a run without swad.
+    boundary: a `boundary.BoundaryLoss` (or a saved config()'s dict form of one) adds the boundary term to calls A and C
+    (TrainStep(boundary=)); None, the default: off, nothing is added.  The device weight is set to boundary.weight_at(epoch) at the
+    start of every epoch and again by restore(), so a resumed run continues the schedule bit for bit; the loss table gets the
+    columns bd_od / bd_oc through the log's names and every epoch's result carries "boundary_weight".
     """
 
     swad, swad_every, average = None, 0, None        # averaging is off unless the constructor switches it on
+    boundary = None                                  # so is the boundary term
 
     def __init__(self, model_od, shape_od, model_oc, shape_oc, hparams, next_batch, iter_per_epoch, max_epoch, lr=(1e-3, 1e-3, 1e-3, 1e-3),
                  stop_epoch=-1, val_batches=None, validator=None, interval_validate=10, lr_schedule=None, out_dir=None, graph="plan",
-                 seed=0, checkpoint_every=0, betas=(0.9, 0.99), freeze_bn=False, swad=None, swad_every=0, swad_batches=None, swad_loss=None):
+                 seed=0, checkpoint_every=0, betas=(0.9, 0.99), freeze_bn=False, swad=None, swad_every=0, swad_batches=None, swad_loss=None,
+                 boundary=None):
+        if isinstance(boundary, dict):              # a saved config()'s form ({}: off)
+            from .boundary import BoundaryLoss
+            boundary = BoundaryLoss(**boundary) if boundary else None
+        self.boundary = boundary
         if isinstance(swad, dict):                  # a saved config()'s form of the valley's parameters ({}: off)
             swad = LossValley(**swad) if swad else None
         if swad is not None and int(swad_every) <= 0:
@@ -237,14 +247,14 @@ class TrainRun:
         if hasattr(next_batch, "set_seed"):            # a feed with a device noise stream of its own (FundusBatches with augment=)
             next_batch.set_seed(self.seed)
         device = next(model_od.parameters()).device
-        self.log = LossLog(device, TrainStep.log_names(hparams))
+        self.log = LossLog(device, TrainStep.log_names(hparams, boundary=boundary is not None))
         self.swad, self.swad_every, self.swad_batches, self.swad_loss = swad, int(swad_every) if swad is not None else 0, swad_batches, swad_loss
         self.average = None
         if swad is not None:
             full = bool(hparams['whitening'])
             self.average = WeightAverage([n for k, n in zip(NET_KEYS, self.nets) if full or k in ("od", "oc")])
         self.train_step = TrainStep(model_od, shape_od, model_oc, shape_oc, hparams, lr=self.base_lr, betas=betas, graph=graph, log=self.log,
-                                    freeze_bn=self.freeze_bn, average=self.average)
+                                    freeze_bn=self.freeze_bn, average=self.average, boundary=boundary)
         self.epoch = 0                 # epochs completed = index of the epoch train_epoch() runs next
         self.iteration = 0             # iterations completed
         self.last = None               # what the last train_epoch() returned
@@ -272,6 +282,8 @@ class TrainRun:
                 n.train(not self.freeze_bn)
         start = time.perf_counter()
         self.log.reset()
+        if self.boundary is not None:
+            self.train_step.set_boundary_weight(self.boundary.weight_at(self.epoch))
         for i in range(self.iter_per_epoch):
             image, target_od, target_oc = self.next_batch(self.py_rng, self.np_rng)
             self.train_step.step(image, target_od, target_oc)
@@ -283,6 +295,8 @@ class TrainRun:
         seconds = time.perf_counter() - start
         self.last = {"epoch": self.epoch, "sums": sums, "means": {k: v / self.iter_per_epoch for k, v in sums.items()},
                      "lr": self.train_step.get_lr(), "seconds": seconds}
+        if self.boundary is not None:
+            self.last["boundary_weight"] = self.train_step.get_boundary_weight()
         if self.out_dir is not None:
             path = os.path.join(self.out_dir, "train_log.csv")
             new = not os.path.isfile(path)
@@ -454,7 +468,8 @@ class TrainRun:
         return {"lr": list(self.base_lr), "iter_per_epoch": self.iter_per_epoch, "max_epoch": self.max_epoch, "stop_epoch": self.stop_epoch,
                 "interval_validate": self.interval_validate, "lr_schedule": self.lr_schedule or "", "seed": self.seed,
                 "checkpoint_every": self.checkpoint_every, "graph": self.graph, "betas": list(self.betas), "freeze_bn": self.freeze_bn,
-                "swad": self.swad.config() if self.swad is not None else {}, "swad_every": self.swad_every}
+                "swad": self.swad.config() if self.swad is not None else {}, "swad_every": self.swad_every,
+                "boundary": self.boundary.config() if self.boundary is not None else {}}
 
     @staticmethod
     def config_kwargs(config):
@@ -466,6 +481,7 @@ class TrainRun:
         cfg["freeze_bn"] = bool(cfg.get("freeze_bn", False))
         cfg["swad"] = LossValley(**cfg["swad"]) if cfg.get("swad") else None      # (a checkpoint from before the field: off)
         cfg["swad_every"] = int(cfg.get("swad_every", 0))
+        cfg["boundary"] = dict(cfg.get("boundary") or {})       # (a checkpoint from before the field: off)
         return cfg
 
     def state(self):
@@ -515,6 +531,8 @@ class TrainRun:
         are dropped: the resumed run writes them again."""
         self.train_step.load_state_dict(d["train_step"])
         self.epoch, self.iteration = int(d["epoch"]), int(d["iteration"])
+        if self.boundary is not None:       # the schedule's value for the epoch that runs next (train_epoch() sets it again)
+            self.train_step.set_boundary_weight(self.boundary.weight_at(self.epoch))
         if self.validator is not None:
             self.validator.best_mean_dice, self.validator.best_epoch = float(d["best_mean_dice"]), int(d["best_epoch"])
         self.py_rng.setstate(_py_state_from_lists(d["py_rng"]))
