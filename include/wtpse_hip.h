@@ -426,7 +426,10 @@ int wtpse_adam_dev(float* p, const float* g, float* m, float* v, long long n, co
  * `running += loss.item()`, so a double accumulator fed in iteration order holds its running sums bit for bit.
  * NaN test on the first check_n scalars, in fp32 and in the reference's order: check_n = 3: isnan((s0 + s1) + s2) (inf + -inf
  * counts), 1: isnan(s0), 0: none.  check_n | 16 (17, 19): the scalar behind those, s1 or s3, is added last and tested with them (the
- * boundary term of TrainStep(boundary=): isnan(s0 + s1), isnan(((s0 + s1) + s2) + s3)).  flag: two device ints, sticky (never cleared here): when the test holds and flag[0] == 0,
+ * boundary term of TrainStep(boundary=): isnan(s0 + s1), isnan(((s0 + s1) + s2) + s3)).  check_n | 32: ONE MORE scalar, the one behind
+ * the tested ones and behind the bit-16 scalar if that bit is set, is added last and tested too (the overlap term of
+ * TrainStep(overlap=)): 35: isnan(((s0 + s1) + s2) + s3), 49: isnan((s0 + s1) + s2), 51: isnan((((s0 + s1) + s2) + s3) + s4).  33 is
+ * refused as it has always been; it would be the test 17 already is, isnan(s0 + s1), and callers write 17.  flag: two device ints, sticky (never cleared here): when the test holds and flag[0] == 0,
  * flag[0] = 1 and flag[1] = *step_dev (the calling network's count of completed steps = the failing iteration; NULL: 0). */
 int wtpse_loss_log(const float* s0, const float* s1, const float* s2, const float* s3, const float* s4, const float* s5,
                    double* acc, int check_n, int* flag, const int* step_dev, void* stream);
@@ -447,6 +450,23 @@ int wtpse_signed_distance_ws(int B, int h, int w);
 int wtpse_signed_distance(const float* t, float* phi, int* d2_out, int* d2_in, void* ws, int B, int h, int w, void* stream);
 int wtpse_boundary_loss(const float* x, const float* mask, const float* phi, const float* alpha_dev, long long n, float* partial,
                         float* loss, float* dx, void* stream);
+
+/* ---- overlap loss: soft Dice / Tversky / focal Tversky per image (csrc/overlap.hip; specification: wtpse_hip/overlap.py) ----
+ * x, t, mask (NULL: m = 1), dx: [B][hw] fp32, one plane per image.  Per plane, with z = x m and s = sigmoid(z) (fp64):
+ *     TP = sum m s t,  FP = sum m s - TP,  FN = sum m t - TP,  TI = (TP + smooth) / (TP + fp FP + fn FN + smooth),
+ *     L_b = (1 - TI)^focal, and L_b = 0 with a zero gradient where 1 - TI <= 0 (decided before any power is taken);
+ * plane_loss[b] = L_b (fp32 [B], or NULL: not wanted), *loss = mean over b of L_b; the weight is NOT applied to either.
+ * With dx != NULL the gradient of (*w_dev) * loss is added into dx in place, in fp64 and rounded once on the add:
+ *     dx_i += (*w_dev / B) (-focal (1 - TI)^(focal - 1)) m_i [t_i D - N (t_i + fp (1 - t_i) - fn t_i)] / D^2 s_i (1 - s_i) m_i
+ * (N, D: numerator and denominator of TI); an increment of exactly 0 leaves the element's bits alone.  w_dev: one device float
+ * (a schedule changes the weight of a recorded call between replays); may be NULL when dx is.  fp, fn >= 0 with fp + fn > 0,
+ * focal > 0, smooth > 0 go by value: constants of a run.  ws: wtpse_overlap_loss_ws(B, hw) BYTES, 8-byte aligned (-1: refused
+ * shape; 1 <= B < 65536, 1 <= hw <= 2^30, B hw < 2^31).  Three launches: fp64 partial sums per workgroup (the number of
+ * workgroups per plane depends on hw alone), the per-plane fold + increment, wtpse_reduce_rows with scale 1 / B.  Fixed order of
+ * additions, no atomics: results do not depend on scheduling, nor on a plane's place in the batch or its alignment. */
+int wtpse_overlap_loss_ws(int B, int hw);
+int wtpse_overlap_loss(const float* x, const float* mask, const float* t, const float* w_dev, int B, int hw, float fp, float fn,
+                       float focal, float smooth, void* ws, float* plane_loss, float* loss, float* dx, void* stream);
 
 /* ---- weight averaging (csrc/average.hip; specification: wtpse_hip/averaging.py) --------------------------------------
  * wtpse_avg_step folds one iterate into running means, up to four segments (a_s, p_s, n_s) in ONE launch; a segment with

@@ -710,7 +710,9 @@ __global__ __launch_bounds__(64) void loss_log_k(const float* s0, const float* s
   if (j == 0 && check_n > 0) {
     float t = *s0;
     if ((check_n & 15) == 3) t = (t + *s1) + *s2;
-    if (check_n & 16) t = t + ((check_n & 15) == 3 ? *s3 : *s1);        // the scalar behind the tested ones as well
+    int k = check_n & 15;
+    if (check_n & 16) t = t + *(k == 3 ? s3 : s1), ++k;                 // the scalar behind the tested ones as well
+    if (check_n & 32) t = t + *(k == 4 ? s4 : k == 3 ? s3 : s2);        // and one more behind that
     if (isnan(t) && flag[0] == 0) {
       flag[0] = 1;
       flag[1] = step_dev ? *step_dev : 0;
@@ -1032,10 +1034,14 @@ extern "C" int wtpse_adam_dev(float* p, const float* g, float* m, float* v, long
 }
 extern "C" int wtpse_loss_log(const float* s0, const float* s1, const float* s2, const float* s3, const float* s4, const float* s5,
                               double* acc, int check_n, int* flag, const int* step_dev, void* stream) {
-  WTPSE_REQUIRE(s0 && acc && flag && (check_n == 0 || check_n == 1 || check_n == 3 || check_n == 17 || check_n == 19));
+  WTPSE_REQUIRE(s0 && acc && flag && (check_n == 0 || check_n == 1 || check_n == 3 || check_n == 17 || check_n == 19 ||
+                                      check_n == 35 || check_n == 49 || check_n == 51));
   WTPSE_REQUIRE((check_n & 15) != 3 || (s1 && s2));
   WTPSE_REQUIRE(check_n != 17 || s1);
   WTPSE_REQUIRE(check_n != 19 || s3);
+  WTPSE_REQUIRE(check_n != 35 || s3);
+  WTPSE_REQUIRE(check_n != 49 || (s1 && s2));
+  WTPSE_REQUIRE(check_n != 51 || (s3 && s4));
   WTPSE_REQUIRE((((uintptr_t)acc) & 7) == 0);
   hipLaunchKernelGGL(loss_log_k, dim3(1), dim3(64), 0, ST, s0, s1, s2, s3, s4, s5, acc, check_n, flag, step_dev);
   return wtpse_status();

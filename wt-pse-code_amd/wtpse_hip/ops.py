@@ -1026,6 +1026,34 @@ def boundary_loss(x, phi, alpha_dev, mask=None, dx=None):
     return loss
 
 
+def overlap_loss(x, t, w_dev, cfg, mask=None, dx=None, want_planes=False):
+    """-> the unweighted overlap loss of x [B, ...] against t, one plane per image: overlap.overlap_loss_host with cfg's fp / fn /
+    focal / smooth (an `overlap.OverlapLoss`; the kernel takes them as fp32) on x * mask (mask None: the disc form) — 0-dim device
+    fp32; want_planes: -> (loss, per-plane losses [B]).  With dx the call adds the gradient of (*w_dev) * loss into dx IN PLACE
+    (w_dev: device fp32 scalar, read by the kernel)."""
+    _chk(x, "x"); _chk(t, "t"); _chk(mask, "mask"); _chk(dx, "dx"); _chk(w_dev, "w_dev")
+    if x.dim() < 2 or x.numel() == 0:
+        raise ValueError("overlap_loss: logits [B, ..., H, W], got shape %s" % (tuple(x.shape),))
+    n, B = x.numel(), int(x.shape[0])
+    for name, v in (("t", t), ("mask", mask), ("dx", dx)):
+        if v is not None and v.numel() != n:
+            raise ValueError("overlap_loss: %s has %d elements, x has %d" % (name, v.numel(), n))
+    if dx is not None and w_dev is None:
+        raise ValueError("overlap_loss: dx needs the device weight w_dev")
+    L = lib()
+    nbytes = L.query("wtpse_overlap_loss_ws", B, n // B)
+    if nbytes <= 0:
+        raise ValueError("overlap_loss: unsupported size %s" % (tuple(x.shape),))
+    # an amax table that describes the region loss's gradient alone no longer bounds dx
+    _amax_stale(dx)
+    loss = torch.empty((), dtype=torch.float32, device=x.device)
+    planes = torch.empty((B,), dtype=torch.float32, device=x.device) if want_planes else None
+    ws = workspace("overlap_loss", (nbytes + 3) // 4, x.device)
+    L.call("wtpse_overlap_loss", ptr(x), ptr(mask), ptr(t), ptr(w_dev), B, n // B, float(cfg.fp), float(cfg.fn), float(cfg.focal),
+           float(cfg.smooth), ptr(ws), ptr(planes), ptr(loss), ptr(dx), stream_ptr())
+    return (loss, planes) if want_planes else loss
+
+
 def roi(image, logit):
     B, C, H, W = image.shape
     out = torch.empty_like(image)

@@ -194,10 +194,15 @@ class TrainStep:
     wtpse_boundary_loss that yields the unweighted L_B (`bd_od` / `bd_oc` of the result and of the log) and adds alpha's share into
     that gradient — all in the call's own chain, so it is part of a recorded step.  alpha is a device float
     (`set_boundary_weight`: a stream-ordered write that the next replay picks up, like the learning rates); it starts at
-    boundary.weight_at(0).  Without one (the default) not one launch or buffer is added and the names are unchanged."""
+    boundary.weight_at(0).  Without one (the default) not one launch or buffer is added and the names are unchanged.
+    overlap: optional `overlap.OverlapLoss`: calls A and C add w * L_ov, the soft Dice / Tversky / focal Tversky loss per image of the
+    call's logits against its target (the cup call inside the ROI mask; wtpse_hip/overlap.py).  ONE wtpse_overlap_loss per call, behind
+    the boundary term when both are on and behind the region loss's gradient otherwise, yields the unweighted L_ov (`ov_od` / `ov_oc`,
+    directly behind `bd_*` or in its place, part of the call's NaN test) and adds w's share into the gradient of the logits.  w is a
+    device float (`set_overlap_weight`), starting at overlap.weight_at(0).  Without one (the default) nothing is added."""
 
     def __init__(self, model_od, shape_od, model_oc, shape_oc, hparams, lr=5e-4, betas=(0.9, 0.99), dp=None, graph=False, log=None,
-                 freeze_bn=False, average=None, boundary=None):
+                 freeze_bn=False, average=None, boundary=None, overlap=None):
         self.hp = hparams
         self.freeze_bn = bool(freeze_bn)
         if self.freeze_bn and dp is not None:
@@ -206,7 +211,9 @@ class TrainStep:
             raise ValueError("average= is not supported together with data-parallel training (dp=)")
         if boundary is not None and dp is not None:
             raise ValueError("boundary= is not supported together with data-parallel training (dp=)")
-        self.boundary = boundary
+        if overlap is not None and dp is not None:
+            raise ValueError("overlap= is not supported together with data-parallel training (dp=)")
+        self.boundary, self.overlap = boundary, overlap
         self.full = bool(hparams['whitening'])
         self.nets = [model_od, model_oc] + ([shape_od, shape_oc] if self.full else [])
         self.model_od, self.shape_od, self.model_oc, self.shape_oc = model_od, shape_od, model_oc, shape_oc
@@ -234,10 +241,11 @@ class TrainStep:
                                  % (len(trained), [k for k in NET_KEYS if k in self.by_key]))
         self.log = log
         if log is not None:
-            want = self.log_names(hparams, boundary=boundary is not None)
+            want = self.log_names(hparams, boundary=boundary is not None, overlap=overlap is not None)
             if list(log.names) != want:
-                raise ValueError("the loss log's names must be TrainStep.log_names(hparams%s) = %s, got %s"
-                                 % (", boundary=True" if boundary is not None else "", want, list(log.names)))
+                raise ValueError("the loss log's names must be TrainStep.log_names(hparams%s%s) = %s, got %s"
+                                 % (", boundary=True" if boundary is not None else "", ", overlap=True" if overlap is not None else "",
+                                    want, list(log.names)))
         for o in self.opt.values():
             o.ready()
             o.hold = None if log is None else log.flag
@@ -246,6 +254,10 @@ class TrainStep:
         if boundary is not None:
             self._bd_weight = float(boundary.weight_at(0))
             self.bd_alpha = torch.full((1,), self._bd_weight, dtype=torch.float32, device=next(model_od.parameters()).device)
+        self._ov_weight, self.ov_w = None, None
+        if overlap is not None:
+            self._ov_weight = float(overlap.weight_at(0))
+            self.ov_w = torch.full((1,), self._ov_weight, dtype=torch.float32, device=next(model_od.parameters()).device)
         # exact data-parallel mode runs ~100 small collectives inside every forward: it stays eager
         self.graph = bool(graph) and not (dp is not None and dp.exact)
         self.plan = self.graph and graph == "plan"
@@ -277,6 +289,10 @@ class TrainStep:
         if self.boundary is not None:       # alpha * L_B on top: its gradient joins the region loss's, its value the call's NaN test
             r["bd"] = ops.boundary_loss(out, ops.signed_distance(target.contiguous()), self.bd_alpha, mask=od_pred, dx=d_out)
             check_n |= 16
+        if self.overlap is not None:        # w * L_ov on top, in the same way; one more scalar behind the tested ones
+            r["ov"] = ops.overlap_loss(out, target.contiguous(), self.ov_w, self.overlap, mask=od_pred, dx=d_out)
+            # (1 | 32 is no check_n of wtpse_loss_log: "s0 and the scalar behind it" is written 17)
+            check_n = 17 if check_n == 1 else check_n | 32
         # the reference's running sums and NaN test of this call (Trainer.py:788-800 / 874-885), in front of backward and Adam
         self._log("seg_od" if od_pred is None else "seg_oc", list(r.values()), check_n, model)
         model._backward_update(tape, d_out, None, None, w_ins=gi, w_dom=gd)
@@ -310,6 +326,8 @@ class TrainStep:
             res.update(ins_od=ra["ins"], dom_od=ra["dom"])
         if self.boundary is not None:
             res["bd_od"] = ra["bd"]
+        if self.overlap is not None:
+            res["ov_od"] = ra["ov"]
         if self.full:
             rb = yield from self._shape_call(self.shape_od, self.model_od, image, target_od)
             res.update(kd_od=rb["kd"], ins_shape_od=rb["ins_total"], ins_ij_od=rb["ins_off"], ins_ii_od=rb["ins_diag"],
@@ -322,6 +340,8 @@ class TrainStep:
             res.update(ins_oc=rc["ins"], dom_oc=rc["dom"])
         if self.boundary is not None:
             res["bd_oc"] = rc["bd"]
+        if self.overlap is not None:
+            res["ov_oc"] = rc["ov"]
         if self.full:
             rd = yield from self._shape_call(self.shape_oc, self.model_oc, roi, target_oc)
             res.update(kd_oc=rd["kd"], ins_shape_oc=rd["ins_total"], dom_shape_oc=rd["dom"])
@@ -330,10 +350,11 @@ class TrainStep:
         return res
 
     @staticmethod
-    def log_names(hparams, boundary=False):
+    def log_names(hparams, boundary=False, overlap=False):
         """The loss names in the order a LossLog for this step holds them: the keys of step()'s result, call by call (A-D).
         boundary: with the boundary term's `bd_od` / `bd_oc`, each directly behind the last name of its call (A / C), so that the
-        call's one wtpse_loss_log launch covers it."""
+        call's one wtpse_loss_log launch covers it.  overlap: with the overlap term's `ov_od` / `ov_oc`, directly behind `bd_*` when
+        present, else where `bd_*` would go."""
         if not bool(hparams['whitening']):
             names = ["seg_od", "seg_oc"]
         else:
@@ -342,6 +363,10 @@ class TrainStep:
         if boundary:
             for last, new in (("dom_od", "bd_od"), ("dom_oc", "bd_oc")) if bool(hparams['whitening']) else (("seg_od", "bd_od"), ("seg_oc", "bd_oc")):
                 names.insert(names.index(last) + 1, new)
+        if overlap:
+            for call in ("od", "oc"):
+                last = "bd_" + call if boundary else ("dom_" if bool(hparams['whitening']) else "seg_") + call
+                names.insert(names.index(last) + 1, "ov_" + call)
         return names
 
     def _log(self, first, scalars, check_n, net):
@@ -445,14 +470,31 @@ class TrainStep:
         """The weight as last set (the host value; None without a boundary term)."""
         return self._bd_weight
 
+    def set_overlap_weight(self, w):
+        """The overlap term's weight from the next step on, recorded or not: a stream-ordered write of the device float the kernel
+        reads (rounded to fp32), no host sync."""
+        if self.overlap is None:
+            raise ValueError("this TrainStep has no overlap term (TrainStep(overlap=...))")
+        w = float(w)
+        if not (w >= 0.0 and w != float("inf")):
+            raise ValueError("the overlap weight must be a finite number >= 0, got %r" % (w,))
+        self._ov_weight = w
+        self.ov_w.fill_(w)
+
+    def get_overlap_weight(self):
+        """The weight as last set (the host value; None without an overlap term)."""
+        return self._ov_weight
+
     def state_dict(self):
         """What a run needs beside the networks' own state_dict()s to continue where it stopped: per network the optimiser state
-        (torch.optim.Adam's layout, FlatAdam.state_dict) and the Philox seed and position of its sampling noise; with a boundary term
-        its current weight.  Synchronises."""
+        (torch.optim.Adam's layout, FlatAdam.state_dict) and the Philox seed and position of its sampling noise; with a boundary /
+        an overlap term its current weight.  Synchronises."""
         sd = {"optim": {k: self.opt[id(n)].state_dict() for k, n in self.by_key.items()},
               "noise": {k: {"seed": int(n._noise_seed), "ctr": int(n._noise_ctr.item())} for k, n in self.by_key.items()}}
         if self.boundary is not None:
             sd["boundary_weight"] = float(self._bd_weight)
+        if self.overlap is not None:
+            sd["overlap_weight"] = float(self._ov_weight)
         return sd
 
     def load_state_dict(self, sd):
@@ -475,6 +517,8 @@ class TrainStep:
             n._noise_ctr.fill_(int(sd["noise"][k]["ctr"]))
         if self.boundary is not None and "boundary_weight" in sd:
             self.set_boundary_weight(sd["boundary_weight"])
+        if self.overlap is not None and "overlap_weight" in sd:
+            self.set_overlap_weight(sd["overlap_weight"])
 
     def close(self):
         """Release the native launch plans (and their hipEvents) of a recorded step."""

@@ -212,15 +212,23 @@ class TrainRun:
     (TrainStep(boundary=)); None, the default: off, nothing is added.  The device weight is set to boundary.weight_at(epoch) at the
     start of every epoch and again by restore(), so a resumed run continues the schedule bit for bit; the loss table gets the
     columns bd_od / bd_oc through the log's names and every epoch's result carries "boundary_weight".
+    overlap: an `overlap.OverlapLoss` (or a saved config()'s dict form of one) adds the soft Dice / Tversky term to calls A and C
+    (TrainStep(overlap=)) in the same way: None, the default, is off; the weight follows overlap.weight_at(epoch) and restore(); the
+    loss table gets ov_od / ov_oc, every epoch's result "overlap_weight".
     """
 
     swad, swad_every, average = None, 0, None        # averaging is off unless the constructor switches it on
     boundary = None                                  # so is the boundary term
+    overlap = None                                   # and the overlap term
 
     def __init__(self, model_od, shape_od, model_oc, shape_oc, hparams, next_batch, iter_per_epoch, max_epoch, lr=(1e-3, 1e-3, 1e-3, 1e-3),
                  stop_epoch=-1, val_batches=None, validator=None, interval_validate=10, lr_schedule=None, out_dir=None, graph="plan",
                  seed=0, checkpoint_every=0, betas=(0.9, 0.99), freeze_bn=False, swad=None, swad_every=0, swad_batches=None, swad_loss=None,
-                 boundary=None):
+                 boundary=None, overlap=None):
+        if isinstance(overlap, dict):               # a saved config()'s form ({}: off)
+            from .overlap import OverlapLoss
+            overlap = OverlapLoss(**overlap) if overlap else None
+        self.overlap = overlap
         if isinstance(boundary, dict):              # a saved config()'s form ({}: off)
             from .boundary import BoundaryLoss
             boundary = BoundaryLoss(**boundary) if boundary else None
@@ -247,14 +255,14 @@ class TrainRun:
         if hasattr(next_batch, "set_seed"):            # a feed with a device noise stream of its own (FundusBatches with augment=)
             next_batch.set_seed(self.seed)
         device = next(model_od.parameters()).device
-        self.log = LossLog(device, TrainStep.log_names(hparams, boundary=boundary is not None))
+        self.log = LossLog(device, TrainStep.log_names(hparams, boundary=boundary is not None, overlap=overlap is not None))
         self.swad, self.swad_every, self.swad_batches, self.swad_loss = swad, int(swad_every) if swad is not None else 0, swad_batches, swad_loss
         self.average = None
         if swad is not None:
             full = bool(hparams['whitening'])
             self.average = WeightAverage([n for k, n in zip(NET_KEYS, self.nets) if full or k in ("od", "oc")])
         self.train_step = TrainStep(model_od, shape_od, model_oc, shape_oc, hparams, lr=self.base_lr, betas=betas, graph=graph, log=self.log,
-                                    freeze_bn=self.freeze_bn, average=self.average, boundary=boundary)
+                                    freeze_bn=self.freeze_bn, average=self.average, boundary=boundary, overlap=overlap)
         self.epoch = 0                 # epochs completed = index of the epoch train_epoch() runs next
         self.iteration = 0             # iterations completed
         self.last = None               # what the last train_epoch() returned
@@ -284,6 +292,8 @@ class TrainRun:
         self.log.reset()
         if self.boundary is not None:
             self.train_step.set_boundary_weight(self.boundary.weight_at(self.epoch))
+        if self.overlap is not None:
+            self.train_step.set_overlap_weight(self.overlap.weight_at(self.epoch))
         for i in range(self.iter_per_epoch):
             image, target_od, target_oc = self.next_batch(self.py_rng, self.np_rng)
             self.train_step.step(image, target_od, target_oc)
@@ -297,6 +307,8 @@ class TrainRun:
                      "lr": self.train_step.get_lr(), "seconds": seconds}
         if self.boundary is not None:
             self.last["boundary_weight"] = self.train_step.get_boundary_weight()
+        if self.overlap is not None:
+            self.last["overlap_weight"] = self.train_step.get_overlap_weight()
         if self.out_dir is not None:
             path = os.path.join(self.out_dir, "train_log.csv")
             new = not os.path.isfile(path)
@@ -469,7 +481,8 @@ class TrainRun:
                 "interval_validate": self.interval_validate, "lr_schedule": self.lr_schedule or "", "seed": self.seed,
                 "checkpoint_every": self.checkpoint_every, "graph": self.graph, "betas": list(self.betas), "freeze_bn": self.freeze_bn,
                 "swad": self.swad.config() if self.swad is not None else {}, "swad_every": self.swad_every,
-                "boundary": self.boundary.config() if self.boundary is not None else {}}
+                "boundary": self.boundary.config() if self.boundary is not None else {},
+                "overlap": self.overlap.config() if self.overlap is not None else {}}
 
     @staticmethod
     def config_kwargs(config):
@@ -482,6 +495,7 @@ class TrainRun:
         cfg["swad"] = LossValley(**cfg["swad"]) if cfg.get("swad") else None      # (a checkpoint from before the field: off)
         cfg["swad_every"] = int(cfg.get("swad_every", 0))
         cfg["boundary"] = dict(cfg.get("boundary") or {})       # (a checkpoint from before the field: off)
+        cfg["overlap"] = dict(cfg.get("overlap") or {})         # (likewise)
         return cfg
 
     def state(self):
@@ -533,6 +547,8 @@ class TrainRun:
         self.epoch, self.iteration = int(d["epoch"]), int(d["iteration"])
         if self.boundary is not None:       # the schedule's value for the epoch that runs next (train_epoch() sets it again)
             self.train_step.set_boundary_weight(self.boundary.weight_at(self.epoch))
+        if self.overlap is not None:
+            self.train_step.set_overlap_weight(self.overlap.weight_at(self.epoch))
         if self.validator is not None:
             self.validator.best_mean_dice, self.validator.best_epoch = float(d["best_mean_dice"]), int(d["best_epoch"])
         self.py_rng.setstate(_py_state_from_lists(d["py_rng"]))
