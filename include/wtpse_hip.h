@@ -424,12 +424,17 @@ int wtpse_adam_dev(float* p, const float* g, float* m, float* v, long long n, co
 /* Device-side loss log (Trainer.py:788-800, 828-832, 874-885, 917-919): one single-wave launch per update() call of a step.
  * s0..s5: device fp32 scalars (trailing ones may be NULL); for every non-NULL sj: acc[j] += (double)*sj — the reference's
  * `running += loss.item()`, so a double accumulator fed in iteration order holds its running sums bit for bit.
- * NaN test on the first check_n scalars, in fp32 and in the reference's order: check_n = 3: isnan((s0 + s1) + s2) (inf + -inf
- * counts), 1: isnan(s0), 0: none.  check_n | 16 (17, 19): the scalar behind those, s1 or s3, is added last and tested with them (the
- * boundary term of TrainStep(boundary=): isnan(s0 + s1), isnan(((s0 + s1) + s2) + s3)).  check_n | 32: ONE MORE scalar, the one behind
- * the tested ones and behind the bit-16 scalar if that bit is set, is added last and tested too (the overlap term of
- * TrainStep(overlap=)): 35: isnan(((s0 + s1) + s2) + s3), 49: isnan((s0 + s1) + s2), 51: isnan((((s0 + s1) + s2) + s3) + s4).  33 is
- * refused as it has always been; it would be the test 17 already is, isnan(s0 + s1), and callers write 17.  flag: two device ints, sticky (never cleared here): when the test holds and flag[0] == 0,
+ * NaN test: the first k scalars (s0 always, and all k non-NULL) are added left to right in fp32, the reference's order, and the sum is
+ * tested (inf + -inf counts):
+ *     check_n   k   sum tested
+ *     0         0   none
+ *     1         1   s0
+ *     17        2   s0 + s1
+ *     3, 49     3   (s0 + s1) + s2
+ *     19, 35    4   ((s0 + s1) + s2) + s3
+ *     51        5   (((s0 + s1) + s2) + s3) + s4
+ * The codes are historical names for the count k: both names of k = 3 and of k = 4 are accepted, every other value is refused.
+ * flag: two device ints, sticky (never cleared here): when the test holds and flag[0] == 0,
  * flag[0] = 1 and flag[1] = *step_dev (the calling network's count of completed steps = the failing iteration; NULL: 0). */
 int wtpse_loss_log(const float* s0, const float* s1, const float* s2, const float* s3, const float* s4, const float* s5,
                    double* acc, int check_n, int* flag, const int* step_dev, void* stream);

@@ -152,6 +152,45 @@ def test_loss_log_argument_checks():
     assert ad(p, g, m, v, 8, lr, 0.9, 0.99, 1e-8, 0, None, None, None) == -1         # step < 1
 
 
+LOSS_LOG_COUNTS = {0: 0, 1: 1, 17: 2, 3: 3, 49: 3, 19: 4, 35: 4, 51: 5}      # check_n -> tested scalars (include/wtpse_hip.h)
+
+
+def test_loss_log_codes_are_counts():
+    """wtpse_loss_log's check_n is a historical name for a count k: for every accepted code each of s0 .. s(k-1) is required, every
+    other integer from -1 to 64 is refused with all six scalars given, and ops names the code of every count.  As above: real memory
+    behind every non-null pointer, status -1 expected, nothing launched."""
+    import ctypes
+    from wtpse_hip import build, ops
+    from wtpse_hip.lib import LIB_PATH
+    build.build()
+    gpu = torch.cuda.is_available()
+    if gpu:
+        torch.cuda.init()
+    dll = ctypes.CDLL(LIB_PATH)
+    keep = []
+
+    def mem(n, dtype):
+        t = torch.zeros(n, dtype=dtype, device="cuda" if gpu else "cpu")
+        keep.append(t)
+        return t.data_ptr()
+
+    fn = dll.wtpse_loss_log
+    fn.argtypes = [ctypes.c_void_p] * 7 + [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    fn.restype = ctypes.c_int
+    s = [mem(1, torch.float32) for _ in range(6)]
+    acc, flag, t = mem(6, torch.float64), mem(2, torch.int32), mem(1, torch.int32)
+    for code, k in LOSS_LOG_COUNTS.items():
+        for j in range(k):
+            args = list(s)
+            args[j] = None
+            assert fn(*args, acc, code, flag, t, None) == -1, (code, j)
+    for code in range(-1, 65):
+        if code not in LOSS_LOG_COUNTS:
+            assert fn(*s, acc, code, flag, t, None) == -1, code
+    assert tuple(ops.loss_log_code(k) for k in range(6)) == (0, 1, 17, 3, 19, 51)
+    assert [LOSS_LOG_COUNTS[ops.loss_log_code(k)] for k in range(6)] == list(range(6))
+
+
 def test_run_state_round_trips_weights_only():
     """A saved-state dict as TrainRun.state() builds it — tensors, numbers, strings, lists, dicts — through torch.save and
     torch.load(weights_only=True), the two host generators included: they continue their streams where they were."""

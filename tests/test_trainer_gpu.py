@@ -130,6 +130,37 @@ def test_loss_log_kernel():
     assert flag.tolist() == [1, 3]
 
 
+def test_loss_log_codes_are_counts():
+    """Every accepted check_n NaN-tests the fp32 sum of the first k scalars and nothing else (the table of include/wtpse_hip.h), with
+    six scalars given: a NaN in slot j raises the flag exactly when j < k; +inf in slot 0 with -inf in slot k - 1 raises (k >= 2),
+    with the -inf in slot k it does not (1 <= k <= 5; k = 0 has no such pair, and its six NaN cases show that no slot is tested);
+    the sums take all six values in every case; the two names of k = 3 and of k = 4 give the same flag and sums."""
+    from wtpse_hip import ops
+    dev = torch.device("cuda:0")
+    nan, inf = float("nan"), float("inf")
+    step = torch.full((1,), 7, dtype=torch.int32, device=dev)
+    got = {}
+    for code, k in {0: 0, 1: 1, 17: 2, 3: 3, 49: 3, 19: 4, 35: 4, 51: 5}.items():
+        cases = [({j: nan}, j < k) for j in range(6)]
+        if k >= 2:
+            cases.append(({0: inf, k - 1: -inf}, True))
+        if k >= 1:
+            cases.append(({0: inf, k: -inf}, False))
+        for put, raised in cases:
+            vals = [put.get(j, float(j + 1)) for j in range(6)]
+            s = torch.tensor(vals, dtype=torch.float32, device=dev)
+            acc = torch.zeros(6, dtype=torch.float64, device=dev)
+            flag = torch.zeros(2, dtype=torch.int32, device=dev)
+            ops.loss_log([s[j] for j in range(6)], acc, 0, code, flag, step)
+            print("check_n %d (k = %d), %s: flag %s" % (code, k, vals, flag.tolist()))
+            assert flag.tolist() == ([1, 7] if raised else [0, 0]), (code, vals)
+            assert all((a != a) if (b != b) else a == b for a, b in zip(acc.tolist(), vals)), (code, vals, acc.tolist())
+            got[code, repr(vals)] =(flag.tolist(), [repr(a) for a in acc.tolist()])
+    for a, b in ((3, 49), (19, 35)):
+        mine = {case: r for (code, case), r in got.items() if code == a}
+        assert mine and mine == {case: r for (code, case), r in got.items() if code == b}, (a, b)
+
+
 # ------------------------------------------------------------------------------------------- 2. schedule under replay
 def _scheduled_run(graph, change=True):
     from wtpse_hip.step import TrainStep

@@ -19,6 +19,8 @@ import math
 
 import numpy as np
 
+from .terms import WeightSchedule
+
 
 def _plane(t):
     t = np.asarray(t)
@@ -118,18 +120,13 @@ def boundary_grad_host(x, phi, alpha, mask=None):
     return float(alpha) / x.size * phi * (e / (1.0 + e) ** 2) * m
 
 
-class BoundaryLoss:
+class BoundaryLoss(WeightSchedule):
     """The boundary term of a run and its weight schedule: alpha = weight_at(epoch) = min(cap, weight + ramp * epoch) — Kervadec's
     "increase" strategy (start small, add a constant per epoch), capped.  `TrainStep(boundary=)` / `TrainRun(boundary=)` take one."""
 
     def __init__(self, weight=0.01, ramp=0.01, cap=1.0):
-        for name, v in (("weight", weight), ("ramp", ramp), ("cap", cap)):
-            if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v < 0:
-                raise ValueError("BoundaryLoss: %s must be a finite number >= 0, got %r" % (name, v))
+        self._nonneg(weight=weight, ramp=ramp, cap=cap)
         self.weight, self.ramp, self.cap = float(weight), float(ramp), float(cap)
-
-    def weight_at(self, epoch):
-        return min(self.cap, self.weight + self.ramp * int(epoch))
 
     def config(self):
         return {"weight": self.weight, "ramp": self.ramp, "cap": self.cap}

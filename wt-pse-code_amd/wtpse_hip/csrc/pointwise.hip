@@ -698,21 +698,22 @@ __global__ __launch_bounds__(256) void adam_k(float* __restrict__ p, const float
 
 // ------------------------------------------------------------------------------------------------ loss log (Trainer.py:788-800, 874-885)
 // One wave: lane j < 6 folds scalar j into its running sum (the reference's `running_x += loss.item()`: an fp32 value widened to
-// double, added to a double); lane 0 evaluates the reference's NaN test in fp32, in its order, and raises the sticky flag.
+// double, added to a double); lane 0 evaluates the reference's NaN test on the first k scalars (0..5), summed left to right in
+// fp32, and raises the sticky flag.
 __global__ __launch_bounds__(64) void loss_log_k(const float* s0, const float* s1, const float* s2, const float* s3, const float* s4,
-                                                 const float* s5, double* __restrict__ acc, int check_n, int* __restrict__ flag,
+                                                 const float* s5, double* __restrict__ acc, int k, int* __restrict__ flag,
                                                  const int* __restrict__ step_dev) {
   const int j = threadIdx.x;
   if (j < 6) {
     const float* s = j == 0 ? s0 : j == 1 ? s1 : j == 2 ? s2 : j == 3 ? s3 : j == 4 ? s4 : s5;
     if (s) acc[j] += (double)*s;
   }
-  if (j == 0 && check_n > 0) {
+  if (j == 0 && k > 0) {
     float t = *s0;
-    if ((check_n & 15) == 3) t = (t + *s1) + *s2;
-    int k = check_n & 15;
-    if (check_n & 16) t = t + *(k == 3 ? s3 : s1), ++k;                 // the scalar behind the tested ones as well
-    if (check_n & 32) t = t + *(k == 4 ? s4 : k == 3 ? s3 : s2);        // and one more behind that
+    if (k > 1) t = t + *s1;
+    if (k > 2) t = t + *s2;
+    if (k > 3) t = t + *s3;
+    if (k > 4) t = t + *s4;
     if (isnan(t) && flag[0] == 0) {
       flag[0] = 1;
       flag[1] = step_dev ? *step_dev : 0;
@@ -1034,16 +1035,16 @@ extern "C" int wtpse_adam_dev(float* p, const float* g, float* m, float* v, long
 }
 extern "C" int wtpse_loss_log(const float* s0, const float* s1, const float* s2, const float* s3, const float* s4, const float* s5,
                               double* acc, int check_n, int* flag, const int* step_dev, void* stream) {
-  WTPSE_REQUIRE(s0 && acc && flag && (check_n == 0 || check_n == 1 || check_n == 3 || check_n == 17 || check_n == 19 ||
-                                      check_n == 35 || check_n == 49 || check_n == 51));
-  WTPSE_REQUIRE((check_n & 15) != 3 || (s1 && s2));
-  WTPSE_REQUIRE(check_n != 17 || s1);
-  WTPSE_REQUIRE(check_n != 19 || s3);
-  WTPSE_REQUIRE(check_n != 35 || s3);
-  WTPSE_REQUIRE(check_n != 49 || (s1 && s2));
-  WTPSE_REQUIRE(check_n != 51 || (s3 && s4));
+  // check_n -> the number of tested scalars (the table of include/wtpse_hip.h); every other value is refused
+  static const int codes[][2] = {{0, 0}, {1, 1}, {17, 2}, {3, 3}, {49, 3}, {19, 4}, {35, 4}, {51, 5}};
+  int k = -1;
+  for (const auto& c : codes)
+    if (c[0] == check_n) k = c[1];
+  const float* const s[5] = {s0, s1, s2, s3, s4};
+  WTPSE_REQUIRE(s0 && acc && flag && k >= 0);
+  for (int j = 1; j < k; ++j) WTPSE_REQUIRE(s[j]);
   WTPSE_REQUIRE((((uintptr_t)acc) & 7) == 0);
-  hipLaunchKernelGGL(loss_log_k, dim3(1), dim3(64), 0, ST, s0, s1, s2, s3, s4, s5, acc, check_n, flag, step_dev);
+  hipLaunchKernelGGL(loss_log_k, dim3(1), dim3(64), 0, ST, s0, s1, s2, s3, s4, s5, acc, k, flag, step_dev);
   return wtpse_status();
 }
 extern "C" int wtpse_randn(float* out, long long n, unsigned long long seed, unsigned long long offset,

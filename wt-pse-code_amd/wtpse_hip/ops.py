@@ -1075,9 +1075,17 @@ def adam_step_dev(p, g, m, v, lr_dev, beta1, beta2, eps, step, step_dev=None, ho
                int(step), ptr(step_dev), ptr(hold), stream_ptr())
 
 
+def loss_log_code(k):
+    """wtpse_loss_log's check_n for "NaN-test the first k scalars" (the table of include/wtpse_hip.h)."""
+    if not 0 <= k <= 5:
+        raise ValueError("loss_log: the NaN test covers the first 0 to 5 scalars of a call, got %d" % k)
+    return (0, 1, 17, 3, 19, 51)[k]
+
+
 def loss_log(scalars, acc, offset, check_n, flag, step_dev):
     """acc[offset + j] += scalars[j] (up to six 0-dim fp32 device tensors; acc: device float64) and the reference's NaN test on the
-    first check_n of them into flag (device int32 [2]); see wtpse_loss_log in include/wtpse_hip.h."""
+    first scalars into flag (device int32 [2]): check_n is the code of their count, `loss_log_code(k)`; see wtpse_loss_log in
+    include/wtpse_hip.h."""
     if not 1 <= len(scalars) <= 6 or offset + len(scalars) > acc.numel():
         raise ValueError("loss_log: %d scalars at offset %d of an accumulator of %d" % (len(scalars), offset, acc.numel()))
     s = [ptr(t) for t in scalars] + [0] * (6 - len(scalars))

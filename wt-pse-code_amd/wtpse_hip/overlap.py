@@ -29,6 +29,7 @@ import math
 import numpy as np
 
 from .boundary import _sigmoid
+from .terms import WeightSchedule
 
 
 def _params(fp, fn, focal, smooth):
@@ -103,17 +104,13 @@ def overlap_grad_host(x, t, weight, mask=None, fp=0.5, fn=0.5, focal=1.0, smooth
     return out.reshape(shape)
 
 
-class OverlapLoss:
+class OverlapLoss(WeightSchedule):
     """The overlap term of a run and its weight schedule: w = weight_at(epoch) = min(cap, weight + ramp * epoch) (cap None: no cap).
     fp / fn weigh false positives / false negatives (0.5, 0.5: soft Dice), focal is the exponent of 1 - TI, smooth the eps of the
     index.  `TrainStep(overlap=)` / `TrainRun(overlap=)` take one."""
 
     def __init__(self, weight=1.0, fp=0.5, fn=0.5, focal=1.0, smooth=1.0, ramp=0.0, cap=None):
-        vals = (("weight", weight), ("fp", fp), ("fn", fn), ("focal", focal), ("smooth", smooth), ("ramp", ramp)) \
-            + ((("cap", cap),) if cap is not None else ())
-        for name, v in vals:
-            if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v < 0:
-                raise ValueError("OverlapLoss: %s must be a finite number >= 0, got %r" % (name, v))
+        self._nonneg(weight=weight, fp=fp, fn=fn, focal=focal, smooth=smooth, ramp=ramp, **({} if cap is None else {"cap": cap}))
         if fp + fn <= 0:
             raise ValueError("OverlapLoss: fp + fn must be > 0, got fp=%r, fn=%r" % (fp, fn))
         for name, v in (("focal", focal), ("smooth", smooth)):
@@ -121,10 +118,6 @@ class OverlapLoss:
                 raise ValueError("OverlapLoss: %s must be > 0, got %r" % (name, v))
         self.weight, self.fp, self.fn, self.focal, self.smooth = float(weight), float(fp), float(fn), float(focal), float(smooth)
         self.ramp, self.cap = float(ramp), None if cap is None else float(cap)
-
-    def weight_at(self, epoch):
-        w = self.weight + self.ramp * int(epoch)
-        return w if self.cap is None else min(self.cap, w)
 
     def config(self):
         return {"weight": self.weight, "fp": self.fp, "fn": self.fn, "focal": self.focal, "smooth": self.smooth, "ramp": self.ramp,

@@ -33,9 +33,26 @@ recording reads (`load_state_dict`); betas, eps and the Philox seeds are passed 
 import torch
 
 from . import ops
+from .boundary import BoundaryLoss
+from .overlap import OverlapLoss
+from .terms import LossTerm
 
 
 NET_KEYS = ("od", "od_shape", "oc", "oc_shape")      # the four networks in the order of train.py:120-138 (lr, lr_shape, lr_oc, lr_oc_shape)
+
+
+def _issue_boundary(term, out, target, mask, dx):
+    return ops.boundary_loss(out, ops.signed_distance(target.contiguous()), term.dev, mask=mask, dx=dx)
+
+
+def _issue_overlap(term, out, target, mask, dx):
+    return ops.overlap_loss(out, target.contiguous(), term.dev, term.schedule, mask=mask, dx=dx)
+
+
+# The extra terms of calls A and C, in the order they are issued and named: (constructor keyword = stem of the state key, log tag,
+# schedule class, issue function (LossTerm.issue)).  TrainStep and TrainRun take everything about a term from here.
+TERMS = (("boundary", "bd", BoundaryLoss, _issue_boundary),
+         ("overlap", "ov", OverlapLoss, _issue_overlap))
 
 
 def adam_state_to_torch(m, v, t, shapes, lr, betas, eps):
@@ -188,18 +205,16 @@ class TrainStep:
     network's new parameters folded into the running means; held by the log's flag like Adam), which lands in the last recorded
     stretch.  Averaging observes and never perturbs: parameters, moments and buffers are those of a step without it.  Without one
     (the default) nothing is issued.
-    boundary: optional `boundary.BoundaryLoss`: the objective of calls A and C becomes L_seg + alpha * L_B, L_B = mean(sigmoid(logit) *
-    phi) with phi the signed distance map of the call's target (the cup call on the ROI-masked logits, as its region loss).  Each of
-    the two calls then computes phi of its target (wtpse_signed_distance) and, behind the region loss's gradient, issues ONE
-    wtpse_boundary_loss that yields the unweighted L_B (`bd_od` / `bd_oc` of the result and of the log) and adds alpha's share into
-    that gradient — all in the call's own chain, so it is part of a recorded step.  alpha is a device float
-    (`set_boundary_weight`: a stream-ordered write that the next replay picks up, like the learning rates); it starts at
-    boundary.weight_at(0).  Without one (the default) not one launch or buffer is added and the names are unchanged.
-    overlap: optional `overlap.OverlapLoss`: calls A and C add w * L_ov, the soft Dice / Tversky / focal Tversky loss per image of the
-    call's logits against its target (the cup call inside the ROI mask; wtpse_hip/overlap.py).  ONE wtpse_overlap_loss per call, behind
-    the boundary term when both are on and behind the region loss's gradient otherwise, yields the unweighted L_ov (`ov_od` / `ov_oc`,
-    directly behind `bd_*` or in its place, part of the call's NaN test) and adds w's share into the gradient of the logits.  w is a
-    device float (`set_overlap_weight`), starting at overlap.weight_at(0).  Without one (the default) nothing is added."""
+    Extra terms of calls A and C (the table TERMS; each off by default, and then not one launch, buffer or name is added): a term that
+    is on makes the objective of the two calls L_seg + w * L_term.  Each call issues its terms in the table's order behind the region
+    loss's gradient, in the call's own chain, so they are part of a recorded step: a term yields its unweighted value (`<tag>_od` /
+    `<tag>_oc` of the result and of the log, behind the call's other scalars and part of its NaN test) and adds w's share into the
+    gradient of the logits.  w is a device float (`set_<term>_weight`: a stream-ordered write that the next replay picks up, like the
+    learning rates) that starts at the schedule's weight_at(0); state_dict() carries it as `<term>_weight`.
+    boundary: a `boundary.BoundaryLoss`, tag `bd`: L_B = mean(sigmoid(logit) * phi) with phi the signed distance map of the call's
+    target (wtpse_signed_distance, then ONE wtpse_boundary_loss; the cup call on the ROI-masked logits, as its region loss).
+    overlap: an `overlap.OverlapLoss`, tag `ov`: the soft Dice / Tversky / focal Tversky loss per image of the call's logits against its
+    target (ONE wtpse_overlap_loss; the cup call inside the ROI mask; wtpse_hip/overlap.py)."""
 
     def __init__(self, model_od, shape_od, model_oc, shape_oc, hparams, lr=5e-4, betas=(0.9, 0.99), dp=None, graph=False, log=None,
                  freeze_bn=False, average=None, boundary=None, overlap=None):
@@ -209,11 +224,13 @@ class TrainStep:
             raise ValueError("freeze_bn=True is not supported together with data-parallel training (dp=)")
         if average is not None and dp is not None:
             raise ValueError("average= is not supported together with data-parallel training (dp=)")
-        if boundary is not None and dp is not None:
-            raise ValueError("boundary= is not supported together with data-parallel training (dp=)")
-        if overlap is not None and dp is not None:
-            raise ValueError("overlap= is not supported together with data-parallel training (dp=)")
-        self.boundary, self.overlap = boundary, overlap
+        given = dict(boundary=boundary, overlap=overlap)
+        self.terms = []                 # the terms that are on, in TERMS' order
+        for key, tag, _, issue in TERMS:
+            if given[key] is not None:
+                if dp is not None:
+                    raise ValueError("%s= is not supported together with data-parallel training (dp=)" % key)
+                self.terms.append(LossTerm(key, tag, given[key], issue, next(model_od.parameters()).device))
         self.full = bool(hparams['whitening'])
         self.nets = [model_od, model_oc] + ([shape_od, shape_oc] if self.full else [])
         self.model_od, self.shape_od, self.model_oc, self.shape_oc = model_od, shape_od, model_oc, shape_oc
@@ -241,23 +258,14 @@ class TrainStep:
                                  % (len(trained), [k for k in NET_KEYS if k in self.by_key]))
         self.log = log
         if log is not None:
-            want = self.log_names(hparams, boundary=boundary is not None, overlap=overlap is not None)
+            want = self.log_names(hparams, **{t.key: True for t in self.terms})
             if list(log.names) != want:
-                raise ValueError("the loss log's names must be TrainStep.log_names(hparams%s%s) = %s, got %s"
-                                 % (", boundary=True" if boundary is not None else "", ", overlap=True" if overlap is not None else "",
-                                    want, list(log.names)))
+                raise ValueError("the loss log's names must be TrainStep.log_names(hparams%s) = %s, got %s"
+                                 % ("".join(", %s=True" % t.key for t in self.terms), want, list(log.names)))
         for o in self.opt.values():
             o.ready()
             o.hold = None if log is None else log.flag
         self.last_od_pred = None
-        self._bd_weight, self.bd_alpha = None, None
-        if boundary is not None:
-            self._bd_weight = float(boundary.weight_at(0))
-            self.bd_alpha = torch.full((1,), self._bd_weight, dtype=torch.float32, device=next(model_od.parameters()).device)
-        self._ov_weight, self.ov_w = None, None
-        if overlap is not None:
-            self._ov_weight = float(overlap.weight_at(0))
-            self.ov_w = torch.full((1,), self._ov_weight, dtype=torch.float32, device=next(model_od.parameters()).device)
         # exact data-parallel mode runs ~100 small collectives inside every forward: it stays eager
         self.graph = bool(graph) and not (dp is not None and dp.exact)
         self.plan = self.graph and graph == "plan"
@@ -285,16 +293,11 @@ class TrainStep:
         r = {"seg": loss}
         if self.full:
             r["ins"], r["dom"] = res[2][0], res[2][3]
-        check_n = len(r)
-        if self.boundary is not None:       # alpha * L_B on top: its gradient joins the region loss's, its value the call's NaN test
-            r["bd"] = ops.boundary_loss(out, ops.signed_distance(target.contiguous()), self.bd_alpha, mask=od_pred, dx=d_out)
-            check_n |= 16
-        if self.overlap is not None:        # w * L_ov on top, in the same way; one more scalar behind the tested ones
-            r["ov"] = ops.overlap_loss(out, target.contiguous(), self.ov_w, self.overlap, mask=od_pred, dx=d_out)
-            # (1 | 32 is no check_n of wtpse_loss_log: "s0 and the scalar behind it" is written 17)
-            check_n = 17 if check_n == 1 else check_n | 32
-        # the reference's running sums and NaN test of this call (Trainer.py:788-800 / 874-885), in front of backward and Adam
-        self._log("seg_od" if od_pred is None else "seg_oc", list(r.values()), check_n, model)
+        for t in self.terms:            # w * L_term on top: its gradient joins the region loss's, its value the call's NaN test
+            r[t.tag] = t.issue(out, target, od_pred, d_out)
+        # the reference's running sums and NaN test of this call (Trainer.py:788-800 / 874-885), in front of backward and Adam: every
+        # scalar of the call is tested
+        self._log("seg_od" if od_pred is None else "seg_oc", list(r.values()), ops.loss_log_code(len(r)), model)
         model._backward_update(tape, d_out, None, None, w_ins=gi, w_dom=gd)
         del tape
         yield model
@@ -321,13 +324,7 @@ class TrainStep:
     def _schedule(self, image, target_od, target_oc, noise):
         """The step as a generator that yields at the points where a network's gradient is complete and not yet used."""
         out, ra = yield from self._seg_call(self.model_od, image, target_od, noise.get("a"), None)
-        res = {"seg_od": ra["seg"]}
-        if self.full:
-            res.update(ins_od=ra["ins"], dom_od=ra["dom"])
-        if self.boundary is not None:
-            res["bd_od"] = ra["bd"]
-        if self.overlap is not None:
-            res["ov_od"] = ra["ov"]
+        res = self._call_names(ra, "od")
         if self.full:
             rb = yield from self._shape_call(self.shape_od, self.model_od, image, target_od)
             res.update(kd_od=rb["kd"], ins_shape_od=rb["ins_total"], ins_ij_od=rb["ins_off"], ins_ii_od=rb["ins_diag"],
@@ -335,13 +332,7 @@ class TrainStep:
         roi, od_pred = ops.roi(image, out)
         self.last_od_pred = od_pred          # [B,1,H,W] in {0,1}: lets a caller see how much of the image the ROI keeps
         out_oc, rc = yield from self._seg_call(self.model_oc, roi, target_oc, noise.get("c"), od_pred)
-        res["seg_oc"] = rc["seg"]
-        if self.full:
-            res.update(ins_oc=rc["ins"], dom_oc=rc["dom"])
-        if self.boundary is not None:
-            res["bd_oc"] = rc["bd"]
-        if self.overlap is not None:
-            res["ov_oc"] = rc["ov"]
+        res.update(self._call_names(rc, "oc"))
         if self.full:
             rd = yield from self._shape_call(self.shape_oc, self.model_oc, roi, target_oc)
             res.update(kd_oc=rd["kd"], ins_shape_oc=rd["ins_total"], dom_shape_oc=rd["dom"])
@@ -350,23 +341,22 @@ class TrainStep:
         return res
 
     @staticmethod
+    def _call_names(r, call):
+        """A segmentation call's scalars {tag: value} under their names in the result and in the log: tag + "_od" / tag + "_oc"."""
+        return {tag + "_" + call: v for tag, v in r.items()}
+
+    @staticmethod
     def log_names(hparams, boundary=False, overlap=False):
         """The loss names in the order a LossLog for this step holds them: the keys of step()'s result, call by call (A-D).
-        boundary: with the boundary term's `bd_od` / `bd_oc`, each directly behind the last name of its call (A / C), so that the
-        call's one wtpse_loss_log launch covers it.  overlap: with the overlap term's `ov_od` / `ov_oc`, directly behind `bd_*` when
-        present, else where `bd_*` would go."""
-        if not bool(hparams['whitening']):
-            names = ["seg_od", "seg_oc"]
-        else:
-            names = ["seg_od", "ins_od", "dom_od", "kd_od", "ins_shape_od", "ins_ij_od", "ins_ii_od", "dom_shape_od",
-                     "seg_oc", "ins_oc", "dom_oc", "kd_oc", "ins_shape_oc", "dom_shape_oc"]
-        if boundary:
-            for last, new in (("dom_od", "bd_od"), ("dom_oc", "bd_oc")) if bool(hparams['whitening']) else (("seg_od", "bd_od"), ("seg_oc", "bd_oc")):
-                names.insert(names.index(last) + 1, new)
-        if overlap:
-            for call in ("od", "oc"):
-                last = "bd_" + call if boundary else ("dom_" if bool(hparams['whitening']) else "seg_") + call
-                names.insert(names.index(last) + 1, "ov_" + call)
+        boundary, overlap: with the term's `bd_*` / `ov_*`; the terms that are on follow the other names of their call (A / C) in TERMS'
+        order, so that the call's one wtpse_loss_log launch covers them."""
+        full = bool(hparams['whitening'])
+        given = dict(boundary=boundary, overlap=overlap)
+        tags = (["seg", "ins", "dom"] if full else ["seg"]) + [tag for key, tag, _, _ in TERMS if given[key]]
+        shape = {"od": ["kd_od", "ins_shape_od", "ins_ij_od", "ins_ii_od", "dom_shape_od"], "oc": ["kd_oc", "ins_shape_oc", "dom_shape_oc"]}
+        names = []
+        for call in ("od", "oc"):
+            names += [tag + "_" + call for tag in tags] + (shape[call] if full else [])
         return names
 
     def _log(self, first, scalars, check_n, net):
@@ -455,46 +445,47 @@ class TrainStep:
         """{network key: rate} as last set (host values)."""
         return {k: self.opt[id(n)].lr for k, n in self.by_key.items()}
 
+    def _term(self, key, attr):
+        """An attribute of the term `key`; None when the term is off."""
+        return next((getattr(t, attr) for t in self.terms if t.key == key), None)
+
+    def set_term_weight(self, key, w):
+        """The weight of the term `key` from the next step on, recorded or not: a stream-ordered write of the device float the kernel
+        reads (rounded to fp32), no host sync."""
+        set_weight = self._term(key, "set_weight")
+        if set_weight is None:
+            raise ValueError("this TrainStep has no %s term (TrainStep(%s=...))" % (key, key))
+        set_weight(w)
+
+    def get_term_weight(self, key):
+        """The weight as last set (the host value; None when the term is off)."""
+        return self._term(key, "weight")
+
+    # the two terms under their public names: the schedule object, the device weight, the weight's setter and getter
+    boundary = property(lambda self: self._term("boundary", "schedule"))
+    overlap = property(lambda self: self._term("overlap", "schedule"))
+    bd_alpha = property(lambda self: self._term("boundary", "dev"))
+    ov_w = property(lambda self: self._term("overlap", "dev"))
+
     def set_boundary_weight(self, a):
-        """The boundary term's weight alpha from the next step on, recorded or not: a stream-ordered write of the device float the
-        kernel reads (rounded to fp32), no host sync."""
-        if self.boundary is None:
-            raise ValueError("this TrainStep has no boundary term (TrainStep(boundary=...))")
-        a = float(a)
-        if not (a >= 0.0 and a != float("inf")):
-            raise ValueError("the boundary weight must be a finite number >= 0, got %r" % (a,))
-        self._bd_weight = a
-        self.bd_alpha.fill_(a)
+        self.set_term_weight("boundary", a)
 
     def get_boundary_weight(self):
-        """The weight as last set (the host value; None without a boundary term)."""
-        return self._bd_weight
+        return self.get_term_weight("boundary")
 
     def set_overlap_weight(self, w):
-        """The overlap term's weight from the next step on, recorded or not: a stream-ordered write of the device float the kernel
-        reads (rounded to fp32), no host sync."""
-        if self.overlap is None:
-            raise ValueError("this TrainStep has no overlap term (TrainStep(overlap=...))")
-        w = float(w)
-        if not (w >= 0.0 and w != float("inf")):
-            raise ValueError("the overlap weight must be a finite number >= 0, got %r" % (w,))
-        self._ov_weight = w
-        self.ov_w.fill_(w)
+        self.set_term_weight("overlap", w)
 
     def get_overlap_weight(self):
-        """The weight as last set (the host value; None without an overlap term)."""
-        return self._ov_weight
+        return self.get_term_weight("overlap")
 
     def state_dict(self):
         """What a run needs beside the networks' own state_dict()s to continue where it stopped: per network the optimiser state
-        (torch.optim.Adam's layout, FlatAdam.state_dict) and the Philox seed and position of its sampling noise; with a boundary /
-        an overlap term its current weight.  Synchronises."""
+        (torch.optim.Adam's layout, FlatAdam.state_dict) and the Philox seed and position of its sampling noise; per term that is on
+        its current weight.  Synchronises."""
         sd = {"optim": {k: self.opt[id(n)].state_dict() for k, n in self.by_key.items()},
               "noise": {k: {"seed": int(n._noise_seed), "ctr": int(n._noise_ctr.item())} for k, n in self.by_key.items()}}
-        if self.boundary is not None:
-            sd["boundary_weight"] = float(self._bd_weight)
-        if self.overlap is not None:
-            sd["overlap_weight"] = float(self._ov_weight)
+        sd.update({t.key + "_weight": float(t.weight) for t in self.terms})
         return sd
 
     def load_state_dict(self, sd):
@@ -515,10 +506,9 @@ class TrainStep:
             n.ensure_ready()
             object.__setattr__(n, "_noise_seed", int(sd["noise"][k]["seed"]))
             n._noise_ctr.fill_(int(sd["noise"][k]["ctr"]))
-        if self.boundary is not None and "boundary_weight" in sd:
-            self.set_boundary_weight(sd["boundary_weight"])
-        if self.overlap is not None and "overlap_weight" in sd:
-            self.set_overlap_weight(sd["overlap_weight"])
+        for t in self.terms:
+            if t.key + "_weight" in sd:         # (a state from before the term: the weight stays)
+                t.set_weight(sd[t.key + "_weight"])
 
     def close(self):
         """Release the native launch plans (and their hipEvents) of a recorded step."""

@@ -31,7 +31,7 @@ import torch
 
 from . import ops
 from .averaging import LossValley, WeightAverage
-from .step import NET_KEYS, TrainStep
+from .step import NET_KEYS, TERMS, TrainStep
 from .validate import best_checkpoint, eval_mode, predict_pair
 
 CKPT_KEYS = ("model", "model_shape", "model_oc", "model_oc_shape")     # Trainer.py:282-288, in the order (od, od_shape, oc, oc_shape)
@@ -208,31 +208,27 @@ class TrainRun:
     valley's parameters and swad_every, state() / restore() the WeightAverage's and the LossValley's state: a resumed run writes the
     same swad_checkpoint bit for bit.  A checkpoint from before the field loads with swad off; one that carries swad state is refused
     by a run without swad.
-    boundary: a `boundary.BoundaryLoss` (or a saved config()'s dict form of one) adds the boundary term to calls A and C
-    (TrainStep(boundary=)); None, the default: off, nothing is added.  The device weight is set to boundary.weight_at(epoch) at the
-    start of every epoch and again by restore(), so a resumed run continues the schedule bit for bit; the loss table gets the
-    columns bd_od / bd_oc through the log's names and every epoch's result carries "boundary_weight".
-    overlap: an `overlap.OverlapLoss` (or a saved config()'s dict form of one) adds the soft Dice / Tversky term to calls A and C
-    (TrainStep(overlap=)) in the same way: None, the default, is off; the weight follows overlap.weight_at(epoch) and restore(); the
-    loss table gets ov_od / ov_oc, every epoch's result "overlap_weight".
+    Extra terms of calls A and C (step.TERMS; TrainStep's docstring says how a term is issued): the keyword takes the term's schedule
+    object or a saved config()'s dict form of one; None, the default: off, nothing is added.  The device weight is set to the
+    schedule's weight_at(epoch) at the start of every epoch and again by restore(), so a resumed run continues the schedule bit for
+    bit; the loss table gets the term's two columns through the log's names, every epoch's result carries "<keyword>_weight", and the
+    schedule stays readable as the attribute of the keyword's name.
+    boundary: a `boundary.BoundaryLoss`; columns bd_od / bd_oc.
+    overlap: an `overlap.OverlapLoss` (soft Dice / Tversky); columns ov_od / ov_oc.
     """
 
     swad, swad_every, average = None, 0, None        # averaging is off unless the constructor switches it on
-    boundary = None                                  # so is the boundary term
-    overlap = None                                   # and the overlap term
+    boundary = overlap = None                        # so are the terms of step.TERMS
 
     def __init__(self, model_od, shape_od, model_oc, shape_oc, hparams, next_batch, iter_per_epoch, max_epoch, lr=(1e-3, 1e-3, 1e-3, 1e-3),
                  stop_epoch=-1, val_batches=None, validator=None, interval_validate=10, lr_schedule=None, out_dir=None, graph="plan",
                  seed=0, checkpoint_every=0, betas=(0.9, 0.99), freeze_bn=False, swad=None, swad_every=0, swad_batches=None, swad_loss=None,
                  boundary=None, overlap=None):
-        if isinstance(overlap, dict):               # a saved config()'s form ({}: off)
-            from .overlap import OverlapLoss
-            overlap = OverlapLoss(**overlap) if overlap else None
-        self.overlap = overlap
-        if isinstance(boundary, dict):              # a saved config()'s form ({}: off)
-            from .boundary import BoundaryLoss
-            boundary = BoundaryLoss(**boundary) if boundary else None
-        self.boundary = boundary
+        terms = dict(boundary=boundary, overlap=overlap)
+        for key, _, cls, _ in TERMS:
+            if isinstance(terms[key], dict):        # a saved config()'s form ({}: off)
+                terms[key] = cls(**terms[key]) if terms[key] else None
+            setattr(self, key, terms[key])
         if isinstance(swad, dict):                  # a saved config()'s form of the valley's parameters ({}: off)
             swad = LossValley(**swad) if swad else None
         if swad is not None and int(swad_every) <= 0:
@@ -255,14 +251,14 @@ class TrainRun:
         if hasattr(next_batch, "set_seed"):            # a feed with a device noise stream of its own (FundusBatches with augment=)
             next_batch.set_seed(self.seed)
         device = next(model_od.parameters()).device
-        self.log = LossLog(device, TrainStep.log_names(hparams, boundary=boundary is not None, overlap=overlap is not None))
+        self.log = LossLog(device, TrainStep.log_names(hparams, **{key: s is not None for key, s in terms.items()}))
         self.swad, self.swad_every, self.swad_batches, self.swad_loss = swad, int(swad_every) if swad is not None else 0, swad_batches, swad_loss
         self.average = None
         if swad is not None:
             full = bool(hparams['whitening'])
             self.average = WeightAverage([n for k, n in zip(NET_KEYS, self.nets) if full or k in ("od", "oc")])
         self.train_step = TrainStep(model_od, shape_od, model_oc, shape_oc, hparams, lr=self.base_lr, betas=betas, graph=graph, log=self.log,
-                                    freeze_bn=self.freeze_bn, average=self.average, boundary=boundary, overlap=overlap)
+                                    freeze_bn=self.freeze_bn, average=self.average, **terms)
         self.epoch = 0                 # epochs completed = index of the epoch train_epoch() runs next
         self.iteration = 0             # iterations completed
         self.last = None               # what the last train_epoch() returned
@@ -279,6 +275,11 @@ class TrainRun:
         """Reads the NaN flag (one small copy, synchronises) and raises the reference's error when it is set."""
         self._raise_if_nan(self.log.read()[1])
 
+    def _set_term_weights(self):
+        """Every term's device weight to its schedule's value for the epoch that runs next."""
+        for t in self.train_step.terms:
+            t.set_weight(t.schedule.weight_at(self.epoch))
+
     def train_epoch(self):
         """`iter_per_epoch` steps without a host synchronisation, then ONE read of the loss log.  Raises
         ValueError('loss is nan while training ...') naming the 0-based iteration when the NaN test of Trainer.py:794-800 / 878-885
@@ -290,10 +291,7 @@ class TrainRun:
                 n.train(not self.freeze_bn)
         start = time.perf_counter()
         self.log.reset()
-        if self.boundary is not None:
-            self.train_step.set_boundary_weight(self.boundary.weight_at(self.epoch))
-        if self.overlap is not None:
-            self.train_step.set_overlap_weight(self.overlap.weight_at(self.epoch))
+        self._set_term_weights()
         for i in range(self.iter_per_epoch):
             image, target_od, target_oc = self.next_batch(self.py_rng, self.np_rng)
             self.train_step.step(image, target_od, target_oc)
@@ -305,10 +303,7 @@ class TrainRun:
         seconds = time.perf_counter() - start
         self.last = {"epoch": self.epoch, "sums": sums, "means": {k: v / self.iter_per_epoch for k, v in sums.items()},
                      "lr": self.train_step.get_lr(), "seconds": seconds}
-        if self.boundary is not None:
-            self.last["boundary_weight"] = self.train_step.get_boundary_weight()
-        if self.overlap is not None:
-            self.last["overlap_weight"] = self.train_step.get_overlap_weight()
+        self.last.update({t.key + "_weight": t.weight for t in self.train_step.terms})
         if self.out_dir is not None:
             path = os.path.join(self.out_dir, "train_log.csv")
             new = not os.path.isfile(path)
@@ -477,12 +472,13 @@ class TrainRun:
 
     # ------------------------------------------------------------------------------------------------ checkpoints
     def config(self):
-        return {"lr": list(self.base_lr), "iter_per_epoch": self.iter_per_epoch, "max_epoch": self.max_epoch, "stop_epoch": self.stop_epoch,
-                "interval_validate": self.interval_validate, "lr_schedule": self.lr_schedule or "", "seed": self.seed,
-                "checkpoint_every": self.checkpoint_every, "graph": self.graph, "betas": list(self.betas), "freeze_bn": self.freeze_bn,
-                "swad": self.swad.config() if self.swad is not None else {}, "swad_every": self.swad_every,
-                "boundary": self.boundary.config() if self.boundary is not None else {},
-                "overlap": self.overlap.config() if self.overlap is not None else {}}
+        cfg = {"lr": list(self.base_lr), "iter_per_epoch": self.iter_per_epoch, "max_epoch": self.max_epoch, "stop_epoch": self.stop_epoch,
+               "interval_validate": self.interval_validate, "lr_schedule": self.lr_schedule or "", "seed": self.seed,
+               "checkpoint_every": self.checkpoint_every, "graph": self.graph, "betas": list(self.betas), "freeze_bn": self.freeze_bn,
+               "swad": self.swad.config() if self.swad is not None else {}, "swad_every": self.swad_every}
+        for key, *_ in TERMS:           # a term's schedule in its dict form ({}: off)
+            cfg[key] = getattr(self, key).config() if getattr(self, key) is not None else {}
+        return cfg
 
     @staticmethod
     def config_kwargs(config):
@@ -494,8 +490,8 @@ class TrainRun:
         cfg["freeze_bn"] = bool(cfg.get("freeze_bn", False))
         cfg["swad"] = LossValley(**cfg["swad"]) if cfg.get("swad") else None      # (a checkpoint from before the field: off)
         cfg["swad_every"] = int(cfg.get("swad_every", 0))
-        cfg["boundary"] = dict(cfg.get("boundary") or {})       # (a checkpoint from before the field: off)
-        cfg["overlap"] = dict(cfg.get("overlap") or {})         # (likewise)
+        for key, *_ in TERMS:
+            cfg[key] = dict(cfg.get(key) or {})                 # (a checkpoint from before the field: off)
         return cfg
 
     def state(self):
@@ -545,10 +541,7 @@ class TrainRun:
         are dropped: the resumed run writes them again."""
         self.train_step.load_state_dict(d["train_step"])
         self.epoch, self.iteration = int(d["epoch"]), int(d["iteration"])
-        if self.boundary is not None:       # the schedule's value for the epoch that runs next (train_epoch() sets it again)
-            self.train_step.set_boundary_weight(self.boundary.weight_at(self.epoch))
-        if self.overlap is not None:
-            self.train_step.set_overlap_weight(self.overlap.weight_at(self.epoch))
+        self._set_term_weights()            # the schedules' values for the epoch that runs next (train_epoch() sets them again)
         if self.validator is not None:
             self.validator.best_mean_dice, self.validator.best_epoch = float(d["best_mean_dice"]), int(d["best_epoch"])
         self.py_rng.setstate(_py_state_from_lists(d["py_rng"]))
