@@ -1004,7 +1004,9 @@ struct WgradArgs {
 
 // __launch_bounds__(256, 2): two workgroups per CU (2 waves per SIMD) so that one loads while the other runs MFMAs;
 // the 9 x 16 accumulators of the 32-wide path leave ~110 VGPRs for staging
-template <int KS, bool P32, int TWL, int NBLK>
+// FULL: cg == MB, i.e. N block nb holds tap nb of the group's MB channels (the 9-block form of the wide layers).  The 9-block form also
+// serves the channel counts with 6 to 9 blocks of MIXED slots (Cin 9..15 at Cout <= 16, Cin 18..31 above): those take the slot table.
+template <int KS, bool P32, int TWL, int NBLK, bool FULL = false>
 __global__ __launch_bounds__(256, 2) void conv_wgrad_k(WgradArgs a) {
   constexpr int TAPS = KS * KS, PAD = KS / 2;
   constexpr int TW = 1 << TWL, TH = 256 / TW;
@@ -1146,8 +1148,8 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_k(WgradArgs a) {
       const int pbase = wave * 64 + s * KQ;
       const int rowbase = (pbase >> TWL) * PITCH + (pbase & (TW - 1)) + kl;
       av = yrow[s * KQ];
-      if constexpr (KS == 3 && NBLK == 9) {
-        // 9 blocks <=> cg == MB: block nb is tap nb of channel j, a compile-time offset from one per-lane address
+      if constexpr (KS == 3 && NBLK == 9 && FULL) {
+        // cg == MB: block nb is tap nb of channel j, a compile-time offset from one per-lane address
         const float* xb = Xs + j * SX + rowbase;
 #pragma unroll
         for (int nb = 0; nb < MAXNB; ++nb) bv[nb] = xb[(nb / 3) * PITCH + (nb % 3)];
@@ -1353,14 +1355,15 @@ extern "C" int wtpse_conv_wgrad(const float* dy, const float* x0, int C0, const 
   dim3 grid((unsigned)(ceil_div(Cout, MB) * a.ngroups), (unsigned)ksplit);
   // instantiated N-block counts: 3x3 -> {1, 2, 5, 9}, 1x1 -> {1}
   const int nb_inst = ksize == 1 ? 1 : (a.nblk <= 1 ? 1 : a.nblk <= 2 ? 2 : a.nblk <= 5 ? 5 : 9);
-#define WG_LAUNCH(KS, P, T, N) hipLaunchKernelGGL((conv_wgrad_k<KS, P, T, N>), grid, dim3(256), 0, st, a)
-#define WG_TW(KS, P, N) do { if (narrow) WG_LAUNCH(KS, P, 4, N); else WG_LAUNCH(KS, P, 5, N); } while (0)
-#define WG_NB(KS, P) do { if (nb_inst == 1) WG_TW(KS, P, 1); else if (nb_inst == 2) WG_TW(KS, P, 2); \
-                          else if (nb_inst == 5) WG_TW(KS, P, 5); else WG_TW(KS, P, 9); } while (0)
+#define WG_LAUNCH(KS, P, T, N, F) hipLaunchKernelGGL((conv_wgrad_k<KS, P, T, N, F>), grid, dim3(256), 0, st, a)
+#define WG_TW(KS, P, N, F) do { if (narrow) WG_LAUNCH(KS, P, 4, N, F); else WG_LAUNCH(KS, P, 5, N, F); } while (0)
+#define WG_NB(KS, P) do { if (nb_inst == 1) WG_TW(KS, P, 1, false); else if (nb_inst == 2) WG_TW(KS, P, 2, false); \
+                          else if (nb_inst == 5) WG_TW(KS, P, 5, false); else if (a.cg == MB) WG_TW(KS, P, 9, true); \
+                          else WG_TW(KS, P, 9, false); } while (0)
   if (ksize == 3) {
     if (p32) WG_NB(3, true); else WG_NB(3, false);
   } else {
-    if (p32) WG_TW(1, true, 1); else WG_TW(1, false, 1);
+    if (p32) WG_TW(1, true, 1, false); else WG_TW(1, false, 1, false);
   }
 #undef WG_NB
 #undef WG_TW

@@ -13,8 +13,8 @@
 //   * the horizontal taps kx = 0 / 2 need the same row shifted by one pixel: the packed bf16 pairs are re-paired with
 //     v_alignbit and the pixel that crosses an 8-pixel group comes from the neighbouring lane group (ds_bpermute, lane +-16);
 //     the pixel beyond the 32-pixel strip is loaded by the lane groups at the strip's ends (one dword per channel and row);
-//   * the vertical taps pair the X row r with the dY rows r+1, r, r-1: the split dY rows are kept in a 3-slot ring of registers
-//     (rows unrolled by three, so that the slots are static).
+//   * the vertical taps pair the X row r with the dY rows r+1, r, r-1: the split dY rows are kept in a 4-slot ring of registers
+//     (rows unrolled by four, so that the slots are static).
 // A wave owns a [16 MF couts] x [16 NF cins] x 9 taps accumulator set (MF x NF x 9 tiles of 16x16) over its share of the pixels;
 // the four waves of a workgroup work on different pixels of the same block and meet in LDS at the very end; per-workgroup
 // slabs are folded in fp64 in fixed order by wgrad_reduce_k / wgrad_fold4_k (conv.hip): bitwise reproducible, no atomics.
