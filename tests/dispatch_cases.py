@@ -3,6 +3,7 @@ the bandwidth-bound kernels behind csrc/pointwise.hip, csrc/bn.hip and csrc/wt_l
 table in prose).  Imports neither the product nor the GPU: test_dispatch_paths_cpu.py proves the tables on the host
 (predicate == expected branch == the library's host query; the kink conditions of the references), test_dispatch_paths_gpu.py
 runs them.  A case names the branch it is there for; a retune that moves a case onto another branch fails both files."""
+import numpy as np
 import torch
 import torch.nn.functional as F
 
@@ -83,6 +84,10 @@ def bn_bwd_nsplit(B, C, HW):
     return max(1, min(2048 // max(C, 1), B * bn_bwd_segs(B, C, HW)))
 
 
+def bn_fold_width(nrows):                         # BN_LAUNCH_FOLD: threads of the kernels that fold `nrows` partial rows per channel
+    return 1024 if nrows >= 2048 else 256
+
+
 def bn_bwd_branch(B, C, HW, in_aligned=True, dy_aligned=True, halves=False):
     """wtpse_bn_bwd -> the launches it makes.  reduce: vec needs dz | y; apply and the one-launch form need dz | y | dy.
     halves: through wtpse_bn_bwd_reduce + wtpse_bn_bwd_apply (the synchronised-BatchNorm pair), which have no one-launch form."""
@@ -93,7 +98,7 @@ def bn_bwd_branch(B, C, HW, in_aligned=True, dy_aligned=True, halves=False):
     segs, ns = bn_bwd_segs(B, C, HW), bn_bwd_nsplit(B, C, HW)
     SL = HW // segs
     return {"path": "three", "reduce": "vec" if vec_in else "scalar", "apply": "vec" if vec_all else "scalar", "segs": segs,
-            "nsplit": ns, "units_per_split": ceil_div(B * segs, ns), "finalize": 1024 if ns >= 2048 else 256,
+            "nsplit": ns, "units_per_split": ceil_div(B * segs, ns), "finalize": bn_fold_width(ns),
             # bn_bwd_reduce_k<true>: threads whose last float4 is taken by the `if (p < SL)` remainder instead of the paired loop
             "remainder": vec_in and any(_reduce_remainder(SL, t) for t in range(256))}
 
@@ -201,6 +206,14 @@ for _hw in BN_VEC_HW:
 for _hw in BN_SCALAR_HW:
     BN_CASES["scalar_%d" % _hw] = ((5, 3, 1, _hw), _hw != 63, {"path": "three", "reduce": "scalar", "apply": "scalar"})
 
+# ---- the finishers of the BatchNorm backward (csrc/bn_math.h: bn_bwd_store, bn_bwd_channel) on sums that are exact
+BN_EXACT_SHAPE = (2, 96, 4, 4)                 # wtpse_bn_bwd: the one-launch kernel; cut to BN_EXACT_CUT channels: reduce, finalize<256>, apply
+BN_EXACT_CUT = 95
+BN_EXACT_ROWS = (3, 2051)                      # rows of host-built partials: bn_bwd_finalize_k<256> and <1024>
+BN_EXACT_C = 3
+BN_EXACT_TAIL = 6                              # exact_cases.TABLES["bnb"]: the smallest case (B * Cl * H * W) of the fp32 layout
+BN_EXACT_FORMS = ("one_launch", "three", "finalize", "finalize_frozen", "tail", "tail_frozen")
+
 # ---- WT loss: name -> (shape, per_domain, expected subset of wt_branch()); the seeds: WT_SEEDS
 WT_CASES = {
     "hw2052":   ((3, 16, 36, 57), 1, {"S": 2, "last_chunk": 4, "fwd": "vec", "bwd": "vec", "bwd_blocks": 3, "finalize": 4}),
@@ -305,6 +318,87 @@ def bn_inputs(shape, relu, seed=100, channels=None):
     return {"y": y, "dz": dz, "gamma": gamma, "beta": beta, "mean": mean.float().contiguous(), "invstd": invstd.float().contiguous(),
             "ss": ss, "relu": relu, "dy": y64.grad, "dgamma": g64.grad, "dbeta": b64.grad, "on_kink": on_kink, "g_masked": gm,
             "shape": (B, C, H, W)}
+
+
+def _ints(shape, seed, lim=3):
+    return torch.randint(-lim, lim + 1, tuple(shape), generator=torch.Generator().manual_seed(seed)).double()
+
+
+def bn_exact_channels(C, seed):
+    """Per channel: gamma and invstd arbitrary fp32, the mean an integer or a half.  -> gamma, invstd, mean (fp32)"""
+    return rnd(C, seed=seed) * 0.2 + 1, rnd(C, seed=seed + 1).abs() * 0.7 + 0.4, (_ints((C,), seed + 2, 4) * 0.5).float()
+
+
+def bn_exact_inputs(channels=None, seed=700):
+    """Operands of wtpse_bn_bwd on BN_EXACT_SHAPE whose sums are exact in EVERY kernel, whatever the order: dz = g and y - mean are
+    integers |v| <= 3, the mean and the shift are halves and the scale is one of (1, 2, -1, 0.5), so the ReLU decision, the products
+    g (y - mean) and all their fp32 sums are exact.  bn_bwd_reduce_k multiplies a THREAD's sum by invstd in fp32 before its butterfly
+    (bn_bwd_small_k does the same in fp64): for that to be exact too, the products of an (image, channel) plane are non-zero in one
+    float4 (one row: W = 4) only and add up to +-2^k there — chosen by rejection among seeded candidates; in the other rows g or
+    y - mean is 0 element by element.  -> as bn_inputs, with the exact sums s1 = sum g [z > 0] and n2 = sum g [z > 0] (y - mean)."""
+    B, C, H, W = BN_EXACT_SHAPE
+    assert W == 4
+    gamma, invstd, mean = bn_exact_channels(C, seed)
+    sc = torch.tensor([1.0, 2.0, -1.0, 0.5], dtype=torch.float64)[torch.randint(0, 4, (C,), generator=torch.Generator().manual_seed(seed + 3))]
+    sf = _ints((C,), seed + 4) * 0.5
+    ch = lambda v: v.view(1, C, 1, 1)
+    g, d = _ints((B, C, H, W), seed + 5), _ints((B, C, H, W), seed + 6)
+    coin = torch.randint(0, 2, (B, C, H, W), generator=torch.Generator().manual_seed(seed + 7)).bool()
+    g, d = torch.where(coin, g, torch.zeros_like(g)), torch.where(coin, torch.zeros_like(d), d)          # g (y - mean) = 0 everywhere ...
+    K = 64                                                                                               # ... but in one row per plane
+    cg, cd = _ints((B, C, K, W), seed + 8), _ints((B, C, K, W), seed + 9)
+    live = ((cd + mean.double().view(1, C, 1, 1)) * ch(sc) + ch(sf)) > 0
+    n = (cg * live * cd).sum(3)
+    pow2 = torch.log2(n.abs().clamp(min=1)) % 1 == 0
+    score = 2 * ((n != 0) & pow2).long() + (n == 0).long()               # (a channel whose ReLU is never live has only zero sums)
+    assert bool((score.max(2).values > 0).all()), "no candidate row with a power-of-two sum"
+    pick = score.argmax(2)                                                                                # the first of the best
+    row = torch.randint(0, H, (B, C), generator=torch.Generator().manual_seed(seed + 10))
+    bi, ci = torch.meshgrid(torch.arange(B), torch.arange(C), indexing="ij")
+    g[bi, ci, row], d[bi, ci, row] = cg[bi, ci, pick], cd[bi, ci, pick]
+    y = d + ch(mean.double())
+    gm = g * ((y * ch(sc) + ch(sf)) > 0)
+    r = {"y": y.float(), "dz": g.float(), "gamma": gamma, "mean": mean, "invstd": invstd, "ss": torch.stack([sc, sf], 1).float().contiguous(),
+         "relu": True, "g_masked": gm, "s1": gm.sum((0, 2, 3)), "n2": (gm * d).sum((0, 2, 3)), "shape": BN_EXACT_SHAPE,
+         "on_kink": torch.zeros(B, C, H, W, dtype=torch.bool)}
+    if channels is not None:
+        r = {k: (v if k in ("relu", "shape") else (v[:, :channels] if v.dim() == 4 else v[:channels]).contiguous()) for k, v in r.items()}
+        r["shape"] = (B, channels, H, W)
+    return r
+
+
+def bn_exact_rows(seed=720):
+    """Host-built partial rows (sum g, sum g (y - mean)) for the finalize kernels: BN_EXACT_ROWS[1] rows of integers |v| <= 3 and the
+    same sums in BN_EXACT_ROWS[0] rows (contiguous groups added up).  -> {rows: fp32 [rows, C, 2]}, s1, n2 (fp64 [C])"""
+    few, many = BN_EXACT_ROWS
+    rows = _ints((many, BN_EXACT_C, 2), seed)
+    cut = [many * i // few for i in range(few + 1)]
+    grouped = torch.stack([rows[cut[i]:cut[i + 1]].sum(0) for i in range(few)])
+    return {many: rows.float().contiguous(), few: grouped.float().contiguous()}, rows[:, :, 0].sum(0), rows[:, :, 1].sum(0)
+
+
+def bn_finish_ref(s1, n2, count, gamma, mean, invstd, frozen=False):
+    """csrc/bn_math.h (bn_bwd_store, bn_bwd_channel) in numpy float64, in the order the functions write the expressions, from the
+    exact sums s1 = sum g and n2 = sum g (y - mean); the fp32 operands enter as they are.  Nothing is rounded to fp32 here.
+    k3_tol: k3 is a difference of two terms — 2^-23 (|k1 s1 / N| + |k2 mean|)."""
+    f = lambda t: np.asarray(t.detach().cpu().double().numpy() if torch.is_tensor(t) else t, dtype=np.float64)
+    s1, n2, gamma, mean, invstd, count = f(s1), f(n2), f(gamma), f(mean), f(invstd), float(count)
+    s2 = n2 * invstd
+    k1 = gamma * invstd
+    k2 = -gamma * invstd * invstd * s2 / count
+    k3 = -k1 * s1 / count - k2 * mean
+    out = {"dbeta": s1, "dgamma": s2, "k3_tol": 2.0 ** -23 * (np.abs(k1 * s1 / count) + np.abs(k2 * mean))}
+    if frozen:
+        k2, k3 = np.zeros_like(k2), np.zeros_like(k3)
+        out["dbias"] = k1 * s1
+    out.update(k1=k1, k2=k2, k3=k3)
+    return {k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in out.items()}
+
+
+def ulps_apart(got, ref64):
+    """Largest distance, in fp32 steps, between `got` (fp32) and the fp64 reference rounded once to fp32."""
+    key = lambda t: (lambda i: torch.where(i < 0, -(i & 0x7FFFFFFF), i))(t.detach().cpu().contiguous().view(torch.int32).long())
+    return int((key(got.float()) - key(ref64.float())).abs().max())
 
 
 def kink_cap(numel):

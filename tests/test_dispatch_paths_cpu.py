@@ -80,6 +80,46 @@ def test_batchnorm_cases_take_the_named_branch(L):
     assert D.bn_bwd_branch(2, 96, 256, dy_aligned=False)["path"] == "three"
 
 
+def test_batchnorm_exact_sum_cases_take_the_named_branch(L):
+    import exact_cases as E
+    B, C, H, W = D.BN_EXACT_SHAPE
+    assert D.bn_bwd_branch(B, C, H * W)["path"] == "small" and C == 96 and B * H * W <= 32768       # the smallest C of the one-launch form
+    br = D.bn_bwd_branch(B, D.BN_EXACT_CUT, H * W)
+    assert (br["path"], br["reduce"], br["apply"], br["finalize"], br["nsplit"]) == ("three", "vec", "vec", 256, B)
+    assert L.query("wtpse_bn_bwd_nsplit", B, D.BN_EXACT_CUT, H * W) == B
+    assert [D.bn_fold_width(n) for n in D.BN_EXACT_ROWS] == [256, 1024] and D.bn_fold_width(2047) == 256 and D.bn_fold_width(2048) == 1024
+    # the operands: integers |v| <= 3, a mean of halves; per (image, channel) the products g (y - mean) are non-zero in at most one
+    # float4, where they add up to +-2^k — the fp32 `* invstd` of a thread of bn_bwd_reduce_k and its butterfly are then exact
+    r = D.bn_exact_inputs()
+    d = r["y"].double() - r["mean"].double().view(1, C, 1, 1)
+    assert float(d.abs().max()) <= 3 and float(r["dz"].abs().max()) <= 3 and bool((r["mean"] * 2 == (r["mean"] * 2).round()).all())
+    assert bool((d == d.round()).all()) and bool((r["dz"] == r["dz"].round()).all())
+    z = r["y"].double() * r["ss"][:, 0].double().view(1, C, 1, 1) + r["ss"][:, 1].double().view(1, C, 1, 1)
+    assert torch.equal(r["g_masked"], r["dz"].double() * (z > 0)) and bool((z.float().double() == z).all())
+    n = (r["g_masked"] * d).reshape(B, C, H * W // 4, 4).sum(3)
+    assert bool(((n != 0).sum(2) <= 1).all()) and bool((torch.log2(n.abs().clamp(min=1)) % 1 == 0).all())
+    assert int((r["n2"] != 0).sum()) > C // 2 and int((r["s1"] != 0).sum()) > C // 2
+    cut = D.bn_exact_inputs(channels=D.BN_EXACT_CUT)
+    assert cut["shape"] == (B, D.BN_EXACT_CUT, H, W) and torch.equal(cut["y"], r["y"][:, :D.BN_EXACT_CUT]) and torch.equal(cut["n2"], r["n2"][:D.BN_EXACT_CUT])
+    rows, s1, n2 = D.bn_exact_rows()
+    few, many = D.BN_EXACT_ROWS
+    assert rows[many].shape == (many, D.BN_EXACT_C, 2) and rows[few].shape == (few, D.BN_EXACT_C, 2) and float(rows[many].abs().max()) <= 3
+    assert torch.equal(rows[few].double().sum(0), rows[many].double().sum(0)) and torch.equal(rows[many].double().sum(0), torch.stack([s1, n2], 1))
+    # the tail: the smallest case of the fp32 layout among the data gradients with the BatchNorm-backward epilogue
+    fp32 = [(c[0] * c[1] * c[5] * c[6], i) for i, c in enumerate(E.TABLES["bnb"]) if not c[9]]
+    assert min(fp32)[1] == D.BN_EXACT_TAIL and E.bnb_layouts(E.TABLES["bnb"][D.BN_EXACT_TAIL])[0] == 0
+    # the reference helper: against the formulas written out independently, in fp64
+    g, iv, mu = D.bn_exact_channels(D.BN_EXACT_C, 730)
+    ref = D.bn_finish_ref(s1, n2, 100, g, mu, iv)
+    k1 = g.double() * iv.double()
+    k2 = -g.double() * iv.double() ** 2 * (n2 * iv.double()) / 100
+    assert torch.allclose(ref["k1"], k1, rtol=1e-15) and torch.allclose(ref["k2"], k2, rtol=1e-14)
+    assert torch.allclose(ref["k3"], -k1 * s1 / 100 - k2 * mu.double(), rtol=1e-12, atol=1e-18)
+    fz = D.bn_finish_ref(s1, n2, 100, g, mu, iv, frozen=True)
+    assert not bool(fz["k2"].any()) and not bool(fz["k3"].any()) and torch.allclose(fz["dbias"], k1 * s1, rtol=1e-15)
+    assert D.ulps_apart(torch.tensor([1.0, -2.0]), torch.tensor([1.0 + 2.0 ** -23, -2.0], dtype=torch.float64)) == 1
+
+
 def test_batchnorm_references_stay_off_the_relu_kink():
     for name, (shape, relu, _) in D.BN_CASES.items():
         r = D.bn_inputs(shape, relu)

@@ -475,6 +475,7 @@ def run_bn_bwd(r, offs=(0, 0, 0), halves=False, relu=None):
                  P(tab), S())
     guards_ok(dy, dg, db, part, coef, tab, dz, y)
     assert amax_value(tab) == float(dy.abs().max()), "amax table of dy"
+    dy.coef = coef.view(C, 3)                         # (the one-launch kernel leaves it untouched)
     return dy, dg, db
 
 
@@ -578,6 +579,104 @@ def test_batchnorm_backward_misaligned_operands():
         dys.append(dy)
     assert all(torch.equal(d, dys[0]) for d in dys[1:])
     close(dys[0], a[0], rtol=1e-4, atol=2e-5 * float(a[0].abs().max()), what="two halves vs one call")     # (sums rounded to fp32 between)
+
+
+def check_finish(ref, what, coef=None, dgamma=None, dbeta=None, dbias=None):
+    """The outputs of a BatchNorm-backward finisher against D.bn_finish_ref (bn_math.h in numpy float64, rounded once to fp32).  The
+    bounds are derived, not measured: the sums are exact, so dbeta is; k1, k2, dgamma and dbias are one fp64 expression each, within a
+    few 2^-53 of the reference fused or not, and the single rounding to fp32 can differ at a tie only: 1 ulp; k3 is a difference of
+    two terms: 2^-23 (|k1 s1 / N| + |k2 mean|); frozen statistics: k2 == k3 == 0."""
+    frozen = "dbias" in ref
+    got = {"dgamma": dgamma, "dbeta": dbeta, "dbias": dbias}
+    if coef is not None:
+        got.update(k1=coef[:, 0], k2=coef[:, 1], k3=coef[:, 2])
+    for k, v in got.items():
+        if v is None:
+            continue
+        v = v.detach().cpu()
+        assert bool(torch.isfinite(v).all()), (what, k, "not finite (unwritten or NaN)")
+        n = D.ulps_apart(v, ref[k])
+        err = float((v.double() - ref[k]).abs().max())
+        print("%s %s: %d ulp, max |got - ref| %.3g" % (what, k, n, err))
+        if k == "dbeta" or (frozen and k in ("k2", "k3")):
+            assert torch.equal(v.double(), ref[k]), (what, k, "exact")
+        elif k == "k3":
+            assert bool(((v.double() - ref[k]).abs() <= ref["k3_tol"]).all()), (what, k, err, float(ref["k3_tol"].max()))
+        else:
+            assert n <= 1, (what, k, n)
+
+
+@pytest.mark.parametrize("form", D.BN_EXACT_FORMS)
+def test_batchnorm_backward_finishers_on_exact_sums(form):
+    """Every place that finishes a BatchNorm backward — bn_bwd_small_k, bn_bwd_finalize_k<256> behind the reduction, <256> and <1024>
+    on host-built rows (batch and frozen statistics), the tail of a data gradient (batch and frozen) — calls csrc/bn_math.h; here each
+    runs on sums that are exact in any order (D.bn_exact_inputs, D.bn_exact_rows, class I of exact_cases) with arbitrary fp32 gamma and
+    invstd, against the header's expressions in numpy float64 (check_finish); dy at check_bn's tolerances.  The 3-row and the 2051-row
+    finalize are one template on the same sums: bitwise equal.  Whether a tail and the finalize kernel on the statistics the same launch
+    left agree bitwise is printed, not asserted (profiles/bn_one_text.md records it)."""
+    if form in ("one_launch", "three"):
+        B, C0, H, W = D.BN_EXACT_SHAPE
+        C = C0 if form == "one_launch" else D.BN_EXACT_CUT
+        br = D.bn_bwd_branch(B, C, H * W)
+        subset(br, {"path": "small"} if form == "one_launch" else {"path": "three", "reduce": "vec", "apply": "vec", "finalize": 256}, form)
+        r = D.bn_exact_inputs(channels=None if form == "one_launch" else C)
+        ref = D.bn_finish_ref(r["s1"], r["n2"], B * H * W, r["gamma"], r["mean"], r["invstd"])
+        dy, dg, db = run_bn_bwd(r)
+        check_finish(ref, form, coef=dy.coef if form == "three" else None, dgamma=dg, dbeta=db)
+        ch = lambda k: ref[k].view(1, C, 1, 1)
+        r.update(dy=ch("k1") * r["g_masked"] + ch("k2") * r["y"].double() + ch("k3"), dgamma=ref["dgamma"], dbeta=ref["dbeta"])
+        check_bn(r, dy, dg, db, what=form)
+    elif form in ("finalize", "finalize_frozen"):
+        frozen = form == "finalize_frozen"
+        C, count = D.BN_EXACT_C, 4 * D.BN_EXACT_ROWS[1]
+        rows, s1, n2 = D.bn_exact_rows()
+        gamma, invstd, mean = D.bn_exact_channels(C, 730)
+        ref = D.bn_finish_ref(s1, n2, count, gamma, mean, invstd, frozen)
+        gm, mu, iv = dev(gamma), dev(mean), dev(invstd)
+        res = []
+        for n in D.BN_EXACT_ROWS:
+            assert D.bn_fold_width(n) == (1024 if n == D.BN_EXACT_ROWS[1] else 256)
+            st, coef, dg, db, dbias = dev(rows[n]), out((C, 3)), out((C,)), out((C,)), out((C,))
+            if frozen:
+                L().call("wtpse_bn_bwd_finalize_coef_frozen", P(st), n, C, P(gm), P(iv), P(coef), P(dg), P(db), P(dbias), 0, S())
+            else:
+                L().call("wtpse_bn_bwd_finalize_coef", P(st), n, C, count, P(gm), P(mu), P(iv), P(coef), P(dg), P(db), 0, S())
+            guards_ok(coef, dg, db, dbias, st)
+            check_finish(ref, "%s, %d rows" % (form, n), coef=coef, dgamma=dg, dbeta=db, dbias=dbias if frozen else None)
+            res.append((coef, dg, db) + ((dbias,) if frozen else ()))
+        for a, b in zip(*res):
+            assert torch.equal(a, b), "the same sums in 3 and in 2051 rows: one template, the same bits"
+    else:
+        import exact_cases as E
+        from test_kernels_gpu import pack
+        frozen = form == "tail_frozen"
+        o = ops()
+        p = E.bnb_problem(D.BN_EXACT_TAIL, "I")
+        B, Cl, Co, bn_second, Cn, H, W, k, relu, x3 = p["case"]
+        assert not x3 and p["d"] is not None and bool(p["check_stats"])
+        gamma, invstd, _ = D.bn_exact_channels(Cl, 740)
+        ref = D.bn_finish_ref(p["stats"][:, 0], p["stats"][:, 1], B * H * W, gamma, p["mean"], invstd, frozen)
+        packed, _, off = pack(p["w"].float())
+        gm, iv, mu = gamma.to(DEV), invstd.to(DEV), p["mean"].float().to(DEV)
+        dg, db, dbias = out((Cl,)), out((Cl,)), out((Cl,))
+        g0, g1, stats, coef = o.dgrad_bnb(p["du"].float().to(DEV), packed.data_ptr() + 4 * off, 0, Cl + Co, k, p["y"].float().to(DEV),
+                                          p["ss"].float().to(DEV), mu, relu, p["split"], bn_second,
+                                          tail=(gm, iv, dg, db) + ((dbias,) if frozen else ()))
+        guards_ok(dg, db, dbias)
+        assert torch.equal((g1 if (Co and bn_second) else g0).cpu().double(), p["g"]), "masked gradient: class I is exact"
+        check_finish(ref, form, coef=coef, dgamma=dg, dbeta=db, dbias=dbias if frozen else None)
+        # the finalize kernel on the partials the same launch left
+        coef_f, dg_f, db_f, dbias_f = out((Cl, 3)), out((Cl,)), out((Cl,)), out((Cl,))
+        if frozen:
+            L().call("wtpse_bn_bwd_finalize_coef_frozen", P(stats), stats.shape[0], Cl, P(gm), P(iv), P(coef_f), P(dg_f), P(db_f), P(dbias_f), 0, S())
+        else:
+            L().call("wtpse_bn_bwd_finalize_coef", P(stats), stats.shape[0], Cl, B * H * W, P(gm), P(mu), P(iv), P(coef_f), P(dg_f), P(db_f), 0, S())
+        guards_ok(coef_f, dg_f, db_f, dbias_f)
+        check_finish(ref, form + ", finalize kernel on the launch's partials", coef=coef_f, dgamma=dg_f, dbeta=db_f, dbias=dbias_f if frozen else None)
+        same = torch.equal(coef, coef_f) and torch.equal(dg, dg_f) and torch.equal(db, db_f) and (not frozen or torch.equal(dbias, dbias_f))
+        print("%s: tail and finalize kernel agree bitwise: %s (%d rows of partials)" % (form, same, stats.shape[0]))
+        torch.cuda.synchronize()
+        E.clear_caches()
 
 
 @pytest.mark.parametrize("hw", D.BN_VEC_HW + D.BN_SCALAR_HW)

@@ -3,9 +3,8 @@
 // (sum, sum of squares) partials; these kernels turn them into the per-channel (scale, shift) pair that
 // consumers apply on load, keep the running statistics, and run the two-reduction backward.
 //
-//   forward : y = conv output, mean/var over (B,H,W);  z = act(y * scale + shift), scale = gamma*invstd, shift = beta - mean*scale
-//   backward: dzh = dz * [z > 0];  dbeta = sum dzh;  dgamma = sum dzh * xhat;  dy = k1*dzh + k2*y + k3
-//             k1 = gamma*invstd,  k2 = -gamma*invstd^2*dgamma/N,  k3 = -k1*dbeta/N - k2*mean
+// The arithmetic — moments, scale / shift, running statistics, the ReLU decision, the two backward sums, (k1, k2, k3), the apply
+// expression — is bn_math.h's (formulas there); the kernels here load, fold in their own fixed order, call it and store.
 #include "common.h"
 
 // one workgroup per channel; partial sums are folded in fp64 in a fixed order.  NT threads: 1024 for the launches with thousands of
@@ -13,8 +12,8 @@
 // the launch sits between two convolutions of a dependency chain (54 + 40 times per step with its backward twin) and its 9 us were
 // four rounds of strided loads that miss this XCD's L2 (the partials were written by workgroups all over the chip)
 //
-// bn_fold_partials: the fold itself, shared by bn_finalize_k and bn_finalize_blend_k (one text: the two cannot drift apart) — every
-// thread of the workgroup calls; lane-strided loads, butterfly within the wave, the waves in order; thread 0 returns with the sums
+// bn_fold_partials: the fold itself, shared by bn_finalize_k, bn_finalize_blend_k and bn_bwd_finalize_k (one text: they cannot drift
+// apart) — every thread of the workgroup calls; lane-strided loads, butterfly within the wave, the waves in order; thread 0 returns with the sums
 template <int NT>
 __device__ __forceinline__ void bn_fold_partials(const float* __restrict__ part, int nblk, int C, int c, int t, double& s1, double& s2) {
   __shared__ double shs[2][NT / 64];
@@ -52,6 +51,13 @@ __device__ __forceinline__ void bn_fold_partials(const float* __restrict__ part,
   }
 }
 
+// the launch of a kernel<NT> that folds `nrows` partial rows with bn_fold_partials: one workgroup per channel, NT as described above
+#define BN_LAUNCH_FOLD(kernel, nrows, C, st, ...)                                             \
+  do {                                                                                        \
+    if ((nrows) >= 2048) hipLaunchKernelGGL(kernel<1024>, dim3(C), dim3(1024), 0, st, __VA_ARGS__); \
+    else hipLaunchKernelGGL(kernel<256>, dim3(C), dim3(256), 0, st, __VA_ARGS__);             \
+  } while (0)
+
 template <int NT>
 __global__ __launch_bounds__(NT) void bn_finalize_k(const float* __restrict__ part, int nblk, int C, double count,
                                                     const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -63,21 +69,13 @@ __global__ __launch_bounds__(NT) void bn_finalize_k(const float* __restrict__ pa
   double s1, s2;
   bn_fold_partials<NT>(part, nblk, C, c, t, s1, s2);
   if (t == 0) {
-    double mean = s1 / count;
-    double var = s2 / count - mean * mean;
-    if (var < 0.0) var = 0.0;
-    double invstd = 1.0 / sqrt(var + (double)eps);
-    float sc = (float)(gamma[c] * invstd);
-    scale_shift[2 * c] = sc;
-    scale_shift[2 * c + 1] = (float)(beta[c] - mean * gamma[c] * invstd);
+    double mean, var;
+    bn_moments(s1, s2, count, mean, var);
+    const double invstd = bn_fwd_channel(mean, var, gamma, beta, eps, scale_shift, c);
     save_mean[c] = (float)mean;
     save_invstd[c] = (float)invstd;
     if (act_amax) amax_put(act_amax, bn_act_bound(gamma[c], beta[c], count), (unsigned)c);     // common.h: the consumers' x2h input scale
-    if (rmean) {
-      double unbiased = count > 1.0 ? var * count / (count - 1.0) : var;
-      rmean[c] = (float)((1.0 - momentum) * rmean[c] + momentum * mean);
-      rvar[c] = (float)((1.0 - momentum) * rvar[c] + momentum * unbiased);
-    }
+    if (rmean) bn_running_update(rmean, rvar, c, mean, var, count, momentum);
     if (nbt && c == 0) *nbt += 1;
   }
 }
@@ -107,17 +105,12 @@ __global__ __launch_bounds__(NT) void bn_finalize_blend_k(const float* __restric
       acc[2 * c] = p1;
       acc[2 * c + 1] = p2;
     }
-    const double n = acc_count + count;
-    double mean = p1 / n;
-    double var = p2 / n - mean * mean;
-    if (var < 0.0) var = 0.0;
+    double mean, var;
+    bn_moments(p1, p2, acc_count + count, mean, var);
     const double mean_s = rmean[c], var_s = rvar[c];
     const double mean_b = (1.0 - w) * mean_s + w * mean;
     const double var_b = (1.0 - w) * var_s + w * var;
-    double invstd = 1.0 / sqrt(var_b + (double)eps);
-    float sc = (float)(gamma[c] * invstd);
-    scale_shift[2 * c] = sc;
-    scale_shift[2 * c + 1] = (float)(beta[c] - mean_b * gamma[c] * invstd);
+    const double invstd = bn_fwd_channel(mean_b, var_b, gamma, beta, eps, scale_shift, c);
     if (moments) {
       moments[4 * c] = mean;
       moments[4 * c + 1] = var;
@@ -129,9 +122,8 @@ __global__ __launch_bounds__(NT) void bn_finalize_blend_k(const float* __restric
       div[c] = 0.5 * (log(vs / vt) + (vt + dm * dm) / vs - 1.0);
     }
     if (act_amax) {
-      const double mean_c = s1 / count;
-      double var_c = s2 / count - mean_c * mean_c;
-      if (var_c < 0.0) var_c = 0.0;
+      double mean_c, var_c;
+      bn_moments(s1, s2, count, mean_c, var_c);
       const double dev = sqrt(var_c * (count > 1.0 ? count - 1.0 : 1.0)) + fabs(mean_c - mean_b);
       // (clamped to the largest float: a bound beyond it would enter the table as inf, which the consumers' x3_scale_from_amax reads
       // as "no scale" (1) like any unknown amax — the finite maximum gives them the smallest scale instead; an activation of that size
@@ -213,14 +205,8 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_k(const float* __restrict__
   const int SL = HW / segs;                        // elements of a segment (segs > 1: a multiple of 2048)
   float s1 = 0.f, s2 = 0.f;
   auto fold4 = [&](float4 yv, float4 g) __attribute__((always_inline)) {
-    if (relu) {
-      if (!(fmaf(yv.x, sc, sf) > 0.f)) g.x = 0.f;
-      if (!(fmaf(yv.y, sc, sf) > 0.f)) g.y = 0.f;
-      if (!(fmaf(yv.z, sc, sf) > 0.f)) g.z = 0.f;
-      if (!(fmaf(yv.w, sc, sf) > 0.f)) g.w = 0.f;
-    }
-    s1 += (g.x + g.y) + (g.z + g.w);
-    s2 += (g.x * (yv.x - mu) + g.y * (yv.y - mu)) + (g.z * (yv.z - mu) + g.w * (yv.w - mu));
+    if (relu) bn_relu_mask4(g, yv, sc, sf);
+    bn_bwd_fold4(s1, s2, g, yv, mu);
   };
   for (int u = split; u < B * segs; u += nsplit) {
     const int b = u / segs, sg = u - b * segs;
@@ -237,9 +223,8 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_k(const float* __restrict__
     } else {
       for (int p = threadIdx.x; p < SL; p += 256) {
         float yv = y[base + p], g = dz[base + p];
-        if (relu && !(fmaf(yv, sc, sf) > 0.f)) g = 0.f;
-        s1 += g;
-        s2 += g * (yv - mu);
+        if (relu && !bn_relu_live(yv, sc, sf)) g = 0.f;
+        bn_bwd_fold(s1, s2, g, yv, mu);
       }
     }
   }
@@ -268,63 +253,23 @@ __global__ __launch_bounds__(NT) void bn_bwd_finalize_k(const float* __restrict_
                                                          float* __restrict__ coef, const float* __restrict__ global_sums,
                                                          float* __restrict__ sums_out, int centred_s2,
                                                          float* __restrict__ dbias) {
-  // one workgroup per channel; fp64 fold in a fixed order (lane-strided, butterfly, the waves in order); NT: see bn_finalize_k
-  __shared__ double shs[2][NT / 64];
   const int c = blockIdx.x, t = threadIdx.x;
-  double s1 = 0.0, s2 = 0.0;
-  for (int k0 = t; k0 < nsplit; k0 += NT * 8) {
-    float2 p2[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      const int k = k0 + NT * u;
-      p2[u] = k < nsplit ? *reinterpret_cast<const float2*>(partial + ((size_t)k * C + c) * 2) : make_float2(0.f, 0.f);
-    }
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      s1 += p2[u].x;
-      s2 += p2[u].y;
-    }
-  }
-  for (int m = 1; m < 64; m <<= 1) {
-    s1 += __shfl_xor(s1, m, 64);
-    s2 += __shfl_xor(s2, m, 64);
-  }
-  if ((t & 63) == 0) {
-    shs[0][t >> 6] = s1;
-    shs[1][t >> 6] = s2;
-  }
-  __syncthreads();
-  s1 = s2 = 0.0;
-#pragma unroll
-  for (int w = 0; w < NT / 64; ++w) {
-    s1 += shs[0][w];
-    s2 += shs[1][w];
-  }
-  if (centred_s2) s2 *= (double)invstd[c];     // partials of a data-gradient epilogue: sum g * (y - mean), not yet / std
+  double s1, s2;
+  bn_fold_partials<NT>(partial, nsplit, C, c, t, s1, s2);
   if (t == 0) {
+    if (centred_s2) s2 *= (double)invstd[c];     // partials of a data-gradient epilogue: sum g * (y - mean), not yet / std
     if (sums_out) {
       sums_out[2 * c] = (float)s1;
       sums_out[2 * c + 1] = (float)s2;
     }
-    if (dbeta) {
-      dbeta[c] = accumulate ? dbeta[c] + (float)s1 : (float)s1;
-      dgamma[c] = accumulate ? dgamma[c] + (float)s2 : (float)s2;
-    }
+    if (dbeta) bn_bwd_store(c, s1, s2, accumulate, dbeta, dgamma);
     if (!coef) return;
     if (global_sums) {
       s1 = global_sums[2 * c];
       s2 = global_sums[2 * c + 1];
     }
-    double k1 = (double)gamma[c] * invstd[c];
-    double k2 = -(double)gamma[c] * invstd[c] * invstd[c] * s2 / count;
-    double k3 = -k1 * s1 / count - k2 * mean[c];
-    if (dbias) {      // frozen statistics (common.h: bnb_tail): dy = k1 g, and the conv bias in front has the gradient k1 sum g
-      k2 = k3 = 0.0;
-      dbias[c] = accumulate ? dbias[c] + (float)(k1 * s1) : (float)(k1 * s1);
-    }
-    coef[3 * c] = (float)k1;
-    coef[3 * c + 1] = (float)k2;
-    coef[3 * c + 2] = (float)k3;
+    // (dbias: frozen statistics — the conv bias in front has the gradient k1 sum g)
+    bn_bwd_channel(c, invstd[c], gamma[c], s1, s2, count, mean, accumulate, dbias, coef);
   }
 }
 
@@ -346,11 +291,8 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_k(const float* __restrict__ 
     if (p < HW) {
       float4 g = *reinterpret_cast<const float4*>(dz + base + p);
       float4 v = *reinterpret_cast<const float4*>(y + base + p);
-      float4 o;
-      o.x = fmaf(k1, (relu && !(fmaf(v.x, sc, sf) > 0.f)) ? 0.f : g.x, fmaf(k2, v.x, k3));
-      o.y = fmaf(k1, (relu && !(fmaf(v.y, sc, sf) > 0.f)) ? 0.f : g.y, fmaf(k2, v.y, k3));
-      o.z = fmaf(k1, (relu && !(fmaf(v.z, sc, sf) > 0.f)) ? 0.f : g.z, fmaf(k2, v.z, k3));
-      o.w = fmaf(k1, (relu && !(fmaf(v.w, sc, sf) > 0.f)) ? 0.f : g.w, fmaf(k2, v.w, k3));
+      if (relu) bn_relu_mask4(g, v, sc, sf);
+      const float4 o = bn_dy4(k1, k2, k3, g, v);
       *reinterpret_cast<float4*>(dy + base + p) = o;
       am = max(max(amax_bits(o.x), amax_bits(o.y)), max(amax_bits(o.z), amax_bits(o.w)));
     }
@@ -358,8 +300,8 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_k(const float* __restrict__ 
     int p = blk * 256 + threadIdx.x;
     if (p < HW) {
       float g = dz[base + p], v = y[base + p];
-      if (relu && !(fmaf(v, sc, sf) > 0.f)) g = 0.f;
-      const float o = fmaf(k1, g, fmaf(k2, v, k3));
+      if (relu && !bn_relu_live(v, sc, sf)) g = 0.f;
+      const float o = bn_dy(k1, k2, k3, g, v);
       dy[base + p] = o;
       am = amax_bits(o);
     }
@@ -383,13 +325,7 @@ __global__ __launch_bounds__(256) void bn_bwd_scale_k(const float* __restrict__ 
     int p = (blk * 256 + threadIdx.x) * 4;
     if (p < HW) {
       float4 g = *reinterpret_cast<const float4*>(dz + base + p);
-      if (mask) {
-        const float4 v = *reinterpret_cast<const float4*>(y + base + p);
-        if (!(fmaf(v.x, sc, sf) > 0.f)) g.x = 0.f;
-        if (!(fmaf(v.y, sc, sf) > 0.f)) g.y = 0.f;
-        if (!(fmaf(v.z, sc, sf) > 0.f)) g.z = 0.f;
-        if (!(fmaf(v.w, sc, sf) > 0.f)) g.w = 0.f;
-      }
+      if (mask) bn_relu_mask4(g, *reinterpret_cast<const float4*>(y + base + p), sc, sf);
       float4 o;
       o.x = k1 * g.x; o.y = k1 * g.y; o.z = k1 * g.z; o.w = k1 * g.w;
       *reinterpret_cast<float4*>(dy + base + p) = o;
@@ -399,7 +335,7 @@ __global__ __launch_bounds__(256) void bn_bwd_scale_k(const float* __restrict__ 
     int p = blk * 256 + threadIdx.x;
     if (p < HW) {
       float g = dz[base + p];
-      if (mask && !(fmaf(y[base + p], sc, sf) > 0.f)) g = 0.f;
+      if (mask && !bn_relu_live(y[base + p], sc, sf)) g = 0.f;
       const float o = k1 * g;
       dy[base + p] = o;
       am = amax_bits(o);
@@ -410,7 +346,7 @@ __global__ __launch_bounds__(256) void bn_bwd_scale_k(const float* __restrict__ 
 
 // Small maps (the 16x16 / 32x32 levels): the three launches above cost 23-30 us of mostly launch latency for a few MB.
 // One workgroup per channel does all of it: pass 1 folds (sum dzh, sum dzh*xhat) over the channel's B*HW elements, the
-// coefficients are computed in place (same formulas as bn_bwd_finalize_k), pass 2 re-reads the channel (L2 / Infinity
+// coefficients are computed in place (bn_bwd_channel, as bn_bwd_finalize_k), pass 2 re-reads the channel (L2 / Infinity
 // Cache resident) and writes dy.  HW % 4 == 0, 16-byte aligned tensors.
 __global__ __launch_bounds__(1024) void bn_bwd_small_k(const float* __restrict__ dz, const float* __restrict__ y,
                                                        const float* __restrict__ ss, int relu, const float* __restrict__ gamma,
@@ -428,14 +364,8 @@ __global__ __launch_bounds__(1024) void bn_bwd_small_k(const float* __restrict__
     const size_t off = ((size_t)b * C + c) * HW + p;
     const float4 yv = *reinterpret_cast<const float4*>(y + off);
     float4 g = *reinterpret_cast<const float4*>(dz + off);
-    if (relu) {
-      if (!(fmaf(yv.x, sc, sf) > 0.f)) g.x = 0.f;
-      if (!(fmaf(yv.y, sc, sf) > 0.f)) g.y = 0.f;
-      if (!(fmaf(yv.z, sc, sf) > 0.f)) g.z = 0.f;
-      if (!(fmaf(yv.w, sc, sf) > 0.f)) g.w = 0.f;
-    }
-    s1 += (g.x + g.y) + (g.z + g.w);
-    s2 += (g.x * (yv.x - mu) + g.y * (yv.y - mu)) + (g.z * (yv.z - mu) + g.w * (yv.w - mu));
+    if (relu) bn_relu_mask4(g, yv, sc, sf);
+    bn_bwd_fold4(s1, s2, g, yv, mu);
   }
   double d1 = (double)s1, d2 = (double)s2 * (double)is;
   for (int m = 1; m < 64; m <<= 1) {
@@ -453,15 +383,8 @@ __global__ __launch_bounds__(1024) void bn_bwd_small_k(const float* __restrict__
       a1 += sh[0][w];
       a2 += sh[1][w];
     }
-    dbeta[c] = accumulate ? dbeta[c] + (float)a1 : (float)a1;
-    dgamma[c] = accumulate ? dgamma[c] + (float)a2 : (float)a2;
-    const double count = (double)B * HW;
-    const double k1 = (double)gamma[c] * is;
-    const double k2 = -(double)gamma[c] * is * is * a2 / count;
-    const double k3 = -k1 * a1 / count - k2 * mu;
-    kc[0] = (float)k1;
-    kc[1] = (float)k2;
-    kc[2] = (float)k3;
+    bn_bwd_store(c, a1, a2, accumulate, dbeta, dgamma);
+    bn_bwd_channel(0, is, gamma[c], a1, a2, (double)B * HW, &mu, 0, nullptr, kc);      // (index 0: kc and mu are this channel's own)
   }
   __syncthreads();
   const float k1 = kc[0], k2 = kc[1], k3 = kc[2];
@@ -470,12 +393,9 @@ __global__ __launch_bounds__(1024) void bn_bwd_small_k(const float* __restrict__
     const int b = e / q, p = (e - b * q) * 4;
     const size_t off = ((size_t)b * C + c) * HW + p;
     const float4 v = *reinterpret_cast<const float4*>(y + off);
-    const float4 g = *reinterpret_cast<const float4*>(dz + off);
-    float4 o;
-    o.x = fmaf(k1, (relu && !(fmaf(v.x, sc, sf) > 0.f)) ? 0.f : g.x, fmaf(k2, v.x, k3));
-    o.y = fmaf(k1, (relu && !(fmaf(v.y, sc, sf) > 0.f)) ? 0.f : g.y, fmaf(k2, v.y, k3));
-    o.z = fmaf(k1, (relu && !(fmaf(v.z, sc, sf) > 0.f)) ? 0.f : g.z, fmaf(k2, v.z, k3));
-    o.w = fmaf(k1, (relu && !(fmaf(v.w, sc, sf) > 0.f)) ? 0.f : g.w, fmaf(k2, v.w, k3));
+    float4 g = *reinterpret_cast<const float4*>(dz + off);
+    if (relu) bn_relu_mask4(g, v, sc, sf);
+    const float4 o = bn_dy4(k1, k2, k3, g, v);
     *reinterpret_cast<float4*>(dy + off) = o;
     am = max(am, max(max(amax_bits(o.x), amax_bits(o.y)), max(amax_bits(o.z), amax_bits(o.w))));
   }
@@ -485,12 +405,8 @@ __global__ __launch_bounds__(1024) void bn_bwd_small_k(const float* __restrict__
 static void bwd_finalize(hipStream_t st, const float* partial, int nsplit, int C, double count, const float* gamma, const float* mean,
                          const float* invstd, float* dgamma, float* dbeta, int accumulate, float* coef, const float* global_sums,
                          float* sums_out, int centred_s2, float* dbias = nullptr) {
-  if (nsplit >= 2048)
-    hipLaunchKernelGGL(bn_bwd_finalize_k<1024>, dim3(C), dim3(1024), 0, st, partial, nsplit, C, count, gamma, mean, invstd, dgamma, dbeta,
-                       accumulate, coef, global_sums, sums_out, centred_s2, dbias);
-  else
-    hipLaunchKernelGGL(bn_bwd_finalize_k<256>, dim3(C), dim3(256), 0, st, partial, nsplit, C, count, gamma, mean, invstd, dgamma, dbeta,
-                       accumulate, coef, global_sums, sums_out, centred_s2, dbias);
+  BN_LAUNCH_FOLD(bn_bwd_finalize_k, nsplit, C, st, partial, nsplit, C, count, gamma, mean, invstd, dgamma, dbeta, accumulate, coef, global_sums,
+                 sums_out, centred_s2, dbias);
 }
 
 static inline bool vec_ok(int HW, const void* a, const void* b, const void* c) {
@@ -514,14 +430,8 @@ extern "C" int wtpse_bn_finalize(const float* stats_partial, int nblk, int C, lo
                                  unsigned* act_amax, void* stream) {
   WTPSE_REQUIRE(stats_partial && gamma && beta && scale_shift && save_mean && save_invstd && nblk > 0 && C > 0 && count > 0);
   WTPSE_REQUIRE((running_mean == nullptr) == (running_var == nullptr));
-  if (nblk >= 2048)
-    hipLaunchKernelGGL(bn_finalize_k<1024>, dim3(C), dim3(1024), 0, (hipStream_t)stream, stats_partial, nblk, C, (double)count,
-                       gamma, beta, running_mean, running_var, num_batches, momentum, eps, scale_shift, save_mean,
-                       save_invstd, act_amax);
-  else
-    hipLaunchKernelGGL(bn_finalize_k<256>, dim3(C), dim3(256), 0, (hipStream_t)stream, stats_partial, nblk, C, (double)count,
-                       gamma, beta, running_mean, running_var, num_batches, momentum, eps, scale_shift, save_mean,
-                       save_invstd, act_amax);
+  BN_LAUNCH_FOLD(bn_finalize_k, nblk, C, (hipStream_t)stream, stats_partial, nblk, C, (double)count, gamma, beta, running_mean, running_var,
+                 num_batches, momentum, eps, scale_shift, save_mean, save_invstd, act_amax);
   return wtpse_status();
 }
 
@@ -531,12 +441,8 @@ extern "C" int wtpse_bn_finalize_blend(const float* stats_partial, int nblk, int
                                        unsigned* act_amax, void* stream) {
   WTPSE_REQUIRE(stats_partial && gamma && beta && running_mean && running_var && scale_shift && nblk > 0 && C > 0 && count > 0);
   WTPSE_REQUIRE(w >= 0.0 && w <= 1.0 && acc_count >= 0.0 && (acc != nullptr || acc_count == 0.0));
-  if (nblk >= 2048)
-    hipLaunchKernelGGL(bn_finalize_blend_k<1024>, dim3(C), dim3(1024), 0, (hipStream_t)stream, stats_partial, nblk, C, (double)count,
-                       gamma, beta, running_mean, running_var, w, eps, acc, acc_count, scale_shift, moments, div, act_amax);
-  else
-    hipLaunchKernelGGL(bn_finalize_blend_k<256>, dim3(C), dim3(256), 0, (hipStream_t)stream, stats_partial, nblk, C, (double)count,
-                       gamma, beta, running_mean, running_var, w, eps, acc, acc_count, scale_shift, moments, div, act_amax);
+  BN_LAUNCH_FOLD(bn_finalize_blend_k, nblk, C, (hipStream_t)stream, stats_partial, nblk, C, (double)count, gamma, beta, running_mean,
+                 running_var, w, eps, acc, acc_count, scale_shift, moments, div, act_amax);
   return wtpse_status();
 }
 

@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <math.h>
 #include "wtpse_hip.h"   // the C ABI: every definition in csrc/ is compiled against its declaration
+#include "bn_math.h"     // the BatchNorm arithmetic, one text: the tails below, bn.hip and the epilogues call it
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -262,7 +263,8 @@ __device__ __forceinline__ f32x4 wt_mfma16x32h(u32x4 a, u32x4 b, f32x4 c) {
 // arrives last: groups of 64 consecutive tiles take a ticket, the last arriver of a group folds the group in index order
 // (fp64) into partial2, then the groups of one output-channel block take a second ticket and the last of them folds the
 // group sums — again in index order, so the result does not depend on who arrives when — and writes (k1, k2, k3), dgamma,
-// dbeta exactly as bn_bwd_finalize_k does.  Nobody waits for anybody: no spinning.  Tickets are zero on entry and are left zero.
+// dbeta through the functions bn_bwd_finalize_k calls (bn_math.h: bn_bwd_store, bn_bwd_channel).  Nobody waits for anybody: no
+// spinning.  Tickets are zero on entry and are left zero.
 struct BnbTail {
   double* partial2;        // [ngroups][ctot][2]
   unsigned* tickets;       // [t2_off + blocks along y]; null: no tail (stats only)
@@ -418,23 +420,14 @@ __device__ __forceinline__ void bnb_tail(const TailTicket& tk, const BnbTail& tl
     const int cb = c - bn_c0;
     const double is = (double)tl.invstd[cb], ga = (double)tl.gamma[cb];
     const double s1 = sh[tid], s2 = sh[tid + 1] * is;          // the partials hold sum g (y - mean): not yet / std
-    tl.dbeta[cb] = tl.accumulate ? tl.dbeta[cb] + (float)s1 : (float)s1;
-    tl.dgamma[cb] = tl.accumulate ? tl.dgamma[cb] + (float)s2 : (float)s2;
-    const double k1 = ga * is;
-    double k2 = -ga * is * is * s2 / tl.count;
-    double k3 = -k1 * s1 / tl.count - k2 * (double)bn_mean[cb];
-    if (tl.dbias) {          // frozen statistics (mean / invstd = the running ones): no term through them, dy = k1 g
-      k2 = k3 = 0.0;
-      tl.dbias[cb] = tl.accumulate ? tl.dbias[cb] + (float)(k1 * s1) : (float)(k1 * s1);
-    }
-    tl.coef[3 * cb] = (float)k1;
-    tl.coef[3 * cb + 1] = (float)k2;
-    tl.coef[3 * cb + 2] = (float)k3;
+    bn_bwd_store(cb, s1, s2, tl.accumulate, tl.dbeta, tl.dgamma);
+    // (frozen statistics — dbias set, mean / invstd = the running ones: no term through them, dy = k1 g)
+    bn_bwd_channel(cb, is, ga, s1, s2, tl.count, bn_mean, tl.accumulate, tl.dbias, tl.coef);
   }
 }
 
 // ---- the same for the FORWARD statistics: the convolution that forms the BatchNorm (sum, sum^2) partials of its output
-// (stats[tile][Cout][2]) also finishes them — scale/shift, saved mean / invstd, running statistics: what bn_finalize_k does
+// (stats[tile][Cout][2]) also finishes them — scale/shift, saved mean / invstd, running statistics: bn_finalize_k's calls into bn_math.h
 // (reference: nn.BatchNorm2d in train mode, algorithms.py:883-889) — 198 dependent launches of ~6 us per step otherwise.
 struct BnfTail {
   double* partial2;        // [ngroups][ctot][2]
@@ -470,20 +463,13 @@ __device__ __forceinline__ void bnf_tail(const TailTicket& tk, const BnfTail& tl
     return;
   const int c = cout0 + (tid >> 1);
   if (tid < CB * 2 && (tid & 1) == 0 && c < Cout) {
-    const double mean = sh[tid] / tl.count;
-    double var = sh[tid + 1] / tl.count - mean * mean;
-    if (var < 0.0) var = 0.0;
-    const double invstd = 1.0 / sqrt(var + (double)tl.eps);
-    tl.scale_shift[2 * c] = (float)(tl.gamma[c] * invstd);
-    tl.scale_shift[2 * c + 1] = (float)(tl.beta[c] - mean * tl.gamma[c] * invstd);
+    double mean, var;
+    bn_moments(sh[tid], sh[tid + 1], tl.count, mean, var);
+    const double invstd = bn_fwd_channel(mean, var, tl.gamma, tl.beta, tl.eps, tl.scale_shift, c);
     tl.save_mean[c] = (float)mean;
     tl.save_invstd[c] = (float)invstd;
     if (tl.act_amax) amax_put(tl.act_amax, bn_act_bound(tl.gamma[c], tl.beta[c], tl.count), (unsigned)c);
-    if (tl.rmean) {
-      const double unbiased = tl.count > 1.0 ? var * tl.count / (tl.count - 1.0) : var;
-      tl.rmean[c] = (float)((1.0 - tl.momentum) * tl.rmean[c] + tl.momentum * mean);
-      tl.rvar[c] = (float)((1.0 - tl.momentum) * tl.rvar[c] + tl.momentum * unbiased);
-    }
+    if (tl.rmean) bn_running_update(tl.rmean, tl.rvar, c, mean, var, tl.count, tl.momentum);
     if (tl.nbt && c == 0) *tl.nbt += 1;
   }
 }

@@ -136,14 +136,7 @@ __global__ __launch_bounds__(256, 3) void conv_fwd_k(ConvArgs a) {
   const int cout0 = cblk * CB;
   const int HW = a.H * a.W;
   if (tid < CB) bias_s[tid] = (a.bias && cout0 + tid < a.Cout) ? a.bias[cout0 + tid] : 0.f;
-  if (BNB && tid < CB) {
-    const int c = cout0 + tid;
-    const bool bn = c >= a.bn_c0 && c < a.bn_c1;
-    float* q = bias_s + CB + tid;          // three planes [scale | shift | mean] of CB floats
-    q[0] = (bn && a.bn_relu) ? a.bn_ss[2 * (c - a.bn_c0)] : 0.f;
-    q[CB] = (bn && a.bn_relu) ? a.bn_ss[2 * (c - a.bn_c0) + 1] : 1.f;
-    q[2 * CB] = bn ? a.bn_mean[c - a.bn_c0] : 0.f;
-  }
+  if (BNB && tid < CB) bnb_stage<CB>(bias_s + CB + tid, cout0 + tid, a);
 
   int off[NT];
 #pragma unroll
@@ -566,10 +559,8 @@ __global__ __launch_bounds__(256, 3) void conv_fwd_k(ConvArgs a) {
       for (int nt = 0; nt < NT; ++nt) {
         float v = acc[mt][nt][r];
         if (MASK && !(mk[r][nt] > 0.f)) v = 0.f;
-        if (BNB) {     // the ReLU decision of the forward pass: fmaf(y, scale, shift) > 0
-          float zz = __builtin_fmaf(mk[r][nt], bsc, bsh);
-          asm volatile("" : "+v"(zz));     // no v_pk_fma_f32 here: see x3_epilogue (conv_x3.hip)
-          if (!(zz > 0.f)) v = 0.f;
+        if (BNB) {     // the ReLU decision of the forward pass (no v_pk_fma_f32 here: bn_math.h)
+          if (!bn_relu_live_opaque(mk[r][nt], bsc, bsh)) v = 0.f;
           acc[mt][nt][r] = v;
         }
         if (!defer) buf_store(rs_o, pvo[nt], soff, v);

@@ -301,13 +301,8 @@ __device__ __forceinline__ void x3_epilogue(const ConvX3Args& a, f32x16 (&acc)[M
       for (int nt = 0; nt < NT; ++nt) {
         float v = acc[mt][nt][r];
         if (MASK && !(mk[r][nt] > 0.f)) v = 0.f;
-        if (BNB) {     // the ReLU decision of the forward pass: fmaf(y, scale, shift) > 0 (channels outside [bn_c0, bn_c1): 0, 1)
-          // (opaque to the vectoriser on purpose: with the two pixels' decisions fused into one v_pk_fma_f32 the masks of a few
-          // lanes of the upper half-wave came out wrong in ~10 % of the launches — tools/probe/dbg_bnb.py; scalar
-          // v_fma_f32 has been bitwise reproducible over thousands of launches)
-          float zz = __builtin_fmaf(mk[r][nt], bsc, bsh);
-          asm volatile("" : "+v"(zz));
-          if (!(zz > 0.f)) v = 0.f;
+        if (BNB) {     // the ReLU decision of the forward pass (channels outside [bn_c0, bn_c1): 0, 1); opaque on purpose: bn_math.h
+          if (!bn_relu_live_opaque(mk[r][nt], bsc, bsh)) v = 0.f;
           acc[mt][nt][r] = v;
         }
         if (!defer) buf_store(rs_o, pvo[nt], soff, v);
@@ -443,14 +438,7 @@ __global__ __launch_bounds__(256, 2) void conv_x3_k(ConvX3Args a) {
   const int cout0 = cblk * CB;
   const int HW = a.H * a.W;
   if (tid < CB) bias_s[tid] = (a.bias && cout0 + tid < a.Cout) ? a.bias[cout0 + tid] : 0.f;
-  if (EPI == 2 && tid < CB) {                     // (scale, shift, mean) of the BatchNorm'd output channels; (0, 1, 0) elsewhere
-    const int c = cout0 + tid;
-    const bool bn = c >= a.bn_c0 && c < a.bn_c1;
-    float* q = bias_s + CB + tid;          // three planes [scale | shift | mean] of CB floats
-    q[0] = (bn && a.bn_relu) ? a.bn_ss[2 * (c - a.bn_c0)] : 0.f;
-    q[CB] = (bn && a.bn_relu) ? a.bn_ss[2 * (c - a.bn_c0) + 1] : 1.f;
-    q[2 * CB] = bn ? a.bn_mean[c - a.bn_c0] : 0.f;
-  }
+  if (EPI == 2 && tid < CB) bnb_stage<CB>(bias_s + CB + tid, cout0 + tid, a);
 
   float sx = 1.f;                                  // power of two applied to the input on load (1 unless TERMS 2): set below
 
@@ -784,14 +772,7 @@ __global__ __launch_bounds__(256, 2) void conv_x3r_k(ConvX3Args a) {
   const int HW = a.H * a.W;
   float sx = 1.f;                                  // power of two applied to the input on load (1 for TERMS 3): set behind the first loads
   if (tid < CB) bias_s[tid] = (a.bias && cout0 + tid < a.Cout) ? a.bias[cout0 + tid] : 0.f;
-  if (EPI == 2 && tid < CB) {
-    const int c = cout0 + tid;
-    const bool bn = c >= a.bn_c0 && c < a.bn_c1;
-    float* q = bias_s + CB + tid;
-    q[0] = (bn && a.bn_relu) ? a.bn_ss[2 * (c - a.bn_c0)] : 0.f;
-    q[CB] = (bn && a.bn_relu) ? a.bn_ss[2 * (c - a.bn_c0) + 1] : 1.f;
-    q[2 * CB] = bn ? a.bn_mean[c - a.bn_c0] : 0.f;
-  }
+  if (EPI == 2 && tid < CB) bnb_stage<CB>(bias_s + CB + tid, cout0 + tid, a);
 
   int off[NT];                                    // halo position of this lane's pixel (tap 0,0 corner)
 #pragma unroll

@@ -297,8 +297,8 @@ __global__ __launch_bounds__(256) void upsample2x_bwd_k(const float* __restrict_
 
 // plane-per-blockIdx.y form, 4 consecutive dx of one row per thread (W % 4 == 0): the 4 x 10 window of dout comes in
 // as 2 x 16-byte + 2 scalar loads per row; per output the same loops and summation order as the scalar kernel
-// BN: dout is not materialised — it is the second half of a BatchNorm backward, dout = fmaf(k1, g, fmaf(k2, y, k3)) per channel
-// (bn_bwd_apply_k's expression, bn.hip: the same bits) with g = `dout`, y = `bn_y`, (k1, k2, k3) = `bn_coef`[C][3]
+// BN: dout is not materialised — it is the second half of a BatchNorm backward, dout = bn_dy(k1, k2, k3, g, y) per channel
+// (bn_math.h: the call bn_bwd_apply_k makes, the same bits) with g = `dout`, y = `bn_y`, (k1, k2, k3) = `bn_coef`[C][3]
 template <bool BN>
 __global__ __launch_bounds__(256) void upsample2x_bwd_v_k(const float* __restrict__ dout, float* __restrict__ dx, int accumulate,
                                                           int BC, int H, int W, const float* __restrict__ bn_y,
@@ -334,7 +334,7 @@ __global__ __launch_bounds__(256) void upsample2x_bwd_v_k(const float* __restric
         const float4 y0 = *reinterpret_cast<const float4*>(yrow), y1 = *reinterpret_cast<const float4*>(yrow + 4);
         const float v[10] = {xb > 0 ? yrow[-1] : 0.f, y0.x, y0.y, y0.z, y0.w, y1.x, y1.y, y1.z, y1.w, 2 * xb + 8 < Wo ? yrow[8] : 0.f};
 #pragma unroll
-        for (int t = 0; t < 10; ++t) w[t] = fmaf(k1, w[t], fmaf(k2, v[t], k3));
+        for (int t = 0; t < 10; ++t) w[t] = bn_dy(k1, k2, k3, w[t], v[t]);
         if (xb == 0) w[0] = 0.f;                    // outside the map: no gradient (not k3)
         if (2 * xb + 8 >= Wo) w[9] = 0.f;
       }

@@ -290,8 +290,8 @@ __global__ __launch_bounds__((64 * WgradRGeom<MF, NF>::NW), 1) void wgrad_r_k(Wg
       constexpr int m = Q / 4, q = Q % 4;
       float v0 = rawy[SA][m][q >> 1][2 * (q & 1)], v1 = rawy[SA][m][q >> 1][2 * (q & 1) + 1];
       if (AFF) {   // rows outside [y0, y1) load g = y = 0 and would come out as k3: the row validity rides in ak3v
-        v0 = fmaf(ak1[m], v0, fmaf(ak2[m], rawb[SA][m][q >> 1][2 * (q & 1)], ak3v[SA][m]));
-        v1 = fmaf(ak1[m], v1, fmaf(ak2[m], rawb[SA][m][q >> 1][2 * (q & 1) + 1], ak3v[SA][m]));
+        v0 = bn_dy(ak1[m], ak2[m], ak3v[SA][m], v0, rawb[SA][m][q >> 1][2 * (q & 1)]);
+        v1 = bn_dy(ak1[m], ak2[m], ak3v[SA][m], v1, rawb[SA][m][q >> 1][2 * (q & 1) + 1]);
       }
       if (BIAS) bsum[m] += (double)v0 + (double)v1;
       if (TERMS == 2) { v0 *= sdy; v1 *= sdy; }

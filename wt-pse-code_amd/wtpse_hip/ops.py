@@ -514,6 +514,13 @@ def affine_act(y, ss, relu):
     return z
 
 
+def _dy_like(t):
+    """The dy of a BatchNorm backward: shaped like t, with the amax table its x2h consumers read (filled by the launch)."""
+    dy = torch.empty_like(t)
+    dy.wt_amax = _amax_table(t.device)
+    return dy
+
+
 def bn_bwd(dz, y, ss, relu, gamma, mean, invstd, dgamma, dbeta, accumulate=False):
     _chk(dz, "dz"); _chk(y, "y")
     B, C, H, W = y.shape
@@ -521,8 +528,7 @@ def bn_bwd(dz, y, ss, relu, gamma, mean, invstd, dgamma, dbeta, accumulate=False
     ns = L.query("wtpse_bn_bwd_nsplit", B, C, H * W)
     partial = workspace("bn_bwd_partial", ns * C * 2, y.device)
     coef = workspace("bn_bwd_coef", C * 3, y.device)
-    dy = torch.empty_like(y)
-    dy.wt_amax = _amax_table(y.device)
+    dy = _dy_like(y)
     L.call("wtpse_bn_bwd", ptr(dz), ptr(y), ptr(ss), int(relu), ptr(gamma), ptr(mean), ptr(invstd), ptr(partial),
            ptr(coef), ptr(dgamma), ptr(dbeta), int(accumulate), ptr(dy), B, C, H * W, ptr(dy.wt_amax), stream_ptr())
     return dy
@@ -534,8 +540,7 @@ def bn_bwd_from_stats(g, y, stats, gamma, mean, invstd, dgamma, dbeta, accumulat
     B, C, H, W = y.shape
     assert stats.shape[1] == C
     coef = workspace("bn_bwd_coef", C * 3, y.device)
-    dy = torch.empty_like(y)
-    dy.wt_amax = _amax_table(y.device)
+    dy = _dy_like(y)
     lib().call("wtpse_bn_bwd_from_stats", ptr(g), ptr(y), ptr(stats), stats.shape[0], ptr(gamma), ptr(mean), ptr(invstd), ptr(coef),
                ptr(dgamma), ptr(dbeta), int(accumulate), ptr(dy), B, C, H * W, ptr(dy.wt_amax), stream_ptr())
     return dy
@@ -550,8 +555,7 @@ def bn_bwd_frozen(dz, y, ss, relu, gamma, mean, invstd, dgamma, dbeta, dbias, ac
     ns = L.query("wtpse_bn_bwd_nsplit", B, C, H * W)
     partial = workspace("bn_bwd_partial", ns * C * 2, y.device)
     coef = workspace("bn_bwd_coef", C * 3, y.device)
-    dy = torch.empty_like(y)
-    dy.wt_amax = _amax_table(y.device)
+    dy = _dy_like(y)
     L.call("wtpse_bn_bwd_frozen", ptr(dz), ptr(y), ptr(ss), int(relu), ptr(gamma), ptr(mean), ptr(invstd), ptr(partial), ptr(coef),
            ptr(dgamma), ptr(dbeta), ptr(dbias), int(accumulate), ptr(dy), B, C, H * W, ptr(dy.wt_amax), stream_ptr())
     return dy
@@ -563,8 +567,7 @@ def bn_bwd_from_stats_frozen(g, stats, gamma, invstd, dgamma, dbeta, dbias, accu
     B, C, H, W = g.shape
     assert stats.shape[1] == C
     coef = workspace("bn_bwd_coef", C * 3, g.device)
-    dy = torch.empty_like(g)
-    dy.wt_amax = _amax_table(g.device)
+    dy = _dy_like(g)
     lib().call("wtpse_bn_bwd_from_stats_frozen", ptr(g), ptr(stats), stats.shape[0], ptr(gamma), ptr(invstd), ptr(coef), ptr(dgamma),
                ptr(dbeta), ptr(dbias), int(accumulate), ptr(dy), B, C, H * W, ptr(dy.wt_amax), stream_ptr())
     return dy
@@ -584,8 +587,7 @@ def bn_bwd_scale_coef(g, coef):
     """dy = k1 g with the coefficients a frozen dgrad_bnb(..., tail=) launch left (k2 = k3 = 0: y is not read)."""
     _chk(g, "g"); _chk(coef, "coef")
     B, C, H, W = g.shape
-    dy = torch.empty_like(g)
-    dy.wt_amax = _amax_table(g.device)
+    dy = _dy_like(g)
     lib().call("wtpse_bn_bwd_scale_coef", ptr(g), ptr(coef), ptr(dy), B, C, H * W, ptr(dy.wt_amax), stream_ptr())
     return dy
 
@@ -610,8 +612,7 @@ def bn_bwd_apply_coef(g, y, coef):
     """dy = k1 g + k2 y + k3 with the coefficients a dgrad_bnb(..., tail=) launch left."""
     _chk(g, "g"); _chk(y, "y")
     B, C, H, W = y.shape
-    dy = torch.empty_like(y)
-    dy.wt_amax = _amax_table(y.device)
+    dy = _dy_like(y)
     lib().call("wtpse_bn_bwd_apply_coef", ptr(g), ptr(y), ptr(coef), ptr(dy), B, C, H * W, ptr(dy.wt_amax), stream_ptr())
     return dy
 
