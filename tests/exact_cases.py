@@ -214,7 +214,7 @@ def wgrad_r_slabs(B, H, W, Cin, Cout):
 
 
 def wgrad_r_terms(mode, plan, v):
-    """16-bit terms per operand of the wgrad_r_k a call runs (the selection at the end of wgrad_r_impl): 2 = x2h (PRO always on),
+    """16-bit terms per operand of the wgrad_r_k a call runs (csrc/wgrad_r.hip: wgrad_r_variant): 2 = x2h (PRO always on),
     1 = one bf16 term, 3 = x3.  v: the call's variant."""
     big = plan["mf"] * plan["nf"] >= 2
     if mode == 2 and not v.bn and (v.amax != "" or big):

@@ -1276,31 +1276,24 @@ __global__ __launch_bounds__(256) void wgrad_fold4_k(const float* __restrict__ s
   }
 }
 
-// fold of the k-split slabs for other translation units (conv_x3.hip)
-void wgrad_reduce_launch(const float* slab, int ksplit, int n, float* dw, int accumulate, void* stream) {
-  if (n % 4 == 0)
-    hipLaunchKernelGGL(wgrad_fold4_k, dim3(ceil_div(n, 128)), dim3(256), 0, (hipStream_t)stream, slab, ksplit, n, dw, accumulate);
+// The fold of a weight gradient's slabs, for all three families.  Which kernel a family gets (both add in the same order):
+//   FP32   wgrad_reduce_k, always: the weight blocks and (with a bias gradient) the bias blocks in one grid;
+//   X3, R  wgrad_fold4_k where n % 4 == 0 and there is no bias gradient, else wgrad_reduce_k as above.
+static void wgrad_fold(const WgradCall& c, int family, hipStream_t st) {
+  const int n = c.Cout * (c.C0 + c.C1) * c.ksize * c.ksize;
+  const int nblk_w = ceil_div(n, 32), nblk_b = c.dbias ? ceil_div(c.Cout, 32) : 0;
+  if (family != WGRAD_FP32 && !c.dbias && n % 4 == 0)
+    hipLaunchKernelGGL(wgrad_fold4_k, dim3(ceil_div(n, 128)), dim3(256), 0, st, c.slab, c.nslab, n, c.dw, c.accumulate);
   else
-    hipLaunchKernelGGL(wgrad_reduce_k, dim3(ceil_div(n, 32)), dim3(256), 0, (hipStream_t)stream, slab, ksplit, n, dw, accumulate,
-                       ceil_div(n, 32), (const float*)nullptr, 0, (float*)nullptr);
-}
-
-// the same with the bias-gradient slabs folded in the same launch (wgrad_r.hip)
-void wgrad_reduce_launch2(const float* slab, int ksplit, int n, float* dw, int accumulate, const float* slab_b, int n_b,
-                          float* db, void* stream) {
-  if (!db) {
-    wgrad_reduce_launch(slab, ksplit, n, dw, accumulate, stream);
-    return;
-  }
-  const int nblk_w = ceil_div(n, 32), nblk_b = ceil_div(n_b, 32);
-  hipLaunchKernelGGL(wgrad_reduce_k, dim3(nblk_w + nblk_b), dim3(256), 0, (hipStream_t)stream, slab, ksplit, n, dw, accumulate, nblk_w,
-                     slab_b, n_b, db);
+    hipLaunchKernelGGL(wgrad_reduce_k, dim3(nblk_w + nblk_b), dim3(256), 0, st, c.slab, c.nslab, n, c.dw, c.accumulate, nblk_w,
+                       c.dbias_slab, c.Cout, c.dbias);
 }
 
 // conv_wgrad_k: the tiles of the forward kernels; MB couts x (ngroups groups of cg cins) per workgroup along x
 struct WgradGeometry {
   Tiling t;
-  int MB, cg, ngroups;
+  int MB, cg, ngroups, nx;    // nx: (cout block, cin group) pairs, the grid's x extent
+  int ksplit;                 // the default: ~2 workgroups per CU (LDS-limited residency of the 32-wide path), at most one per tile
 };
 static WgradGeometry wgrad_geometry(int B, int H, int W, int Cin, int Cout) {
   WgradGeometry g;
@@ -1308,50 +1301,62 @@ static WgradGeometry wgrad_geometry(int B, int H, int W, int Cin, int Cout) {
   g.MB = Cout > 16 ? 32 : 16;
   g.cg = Cin < g.MB ? Cin : g.MB;
   g.ngroups = ceil_div(Cin, g.cg);   // a ragged last group re-reads valid planes; its slots are never stored
+  g.nx = ceil_div(Cout, g.MB) * g.ngroups;
+  g.ksplit = 512 / g.nx;
+  if (g.ksplit < 1) g.ksplit = 1;
+  if (g.ksplit > g.t.tiles) g.ksplit = g.t.tiles;
   return g;
 }
 
-extern "C" int wtpse_wgrad_ksplit(int B, int H, int W, int Cin, int Cout) {
-  const WgradGeometry g = wgrad_geometry(B, H, W, Cin, Cout);
-  const int nx = ceil_div(Cout, g.MB) * g.ngroups;
-  int ks = 512 / nx;   // ~2 workgroups per CU (LDS-limited residency of the 32-wide path)
-  if (ks < 1) ks = 1;
-  if (ks > g.t.tiles) ks = g.t.tiles;
-  return ks;
+extern "C" int wtpse_wgrad_ksplit(int B, int H, int W, int Cin, int Cout) { return wgrad_geometry(B, H, W, Cin, Cout).ksplit; }
+
+// Every precondition of the four weight-gradient entry points, once: the clauses all families share, then what only one of them asks.
+static int wgrad_check(const WgradCall& c, int family) {
+  WTPSE_REQUIRE(c.dy && c.x0 && c.slab && c.dw && c.B > 0 && c.H > 0 && c.W > 0 && c.C0 > 0 && c.C1 >= 0 && c.Cout > 0);
+  WTPSE_REQUIRE((c.C1 == 0) == (c.x1 == nullptr));
+  WTPSE_REQUIRE((c.dbias == nullptr) == (c.dbias_slab == nullptr));
+  const int Cin = c.C0 + c.C1;
+  if (family == WGRAD_FP32) {
+    WTPSE_REQUIRE(c.ksize == 1 || c.ksize == 3);
+    WTPSE_REQUIRE(c.C1 == 0 || c.C0 % 16 == 0);   // a 16-channel half group must not straddle the two inputs
+    WTPSE_REQUIRE(c.nslab > 0 && c.nslab <= wgrad_geometry(c.B, c.H, c.W, Cin, c.Cout).t.tiles);
+  } else if (family == WGRAD_X3) {
+    WTPSE_REQUIRE(wtpse_wgrad_x3_supported(Cin, c.Cout, c.ksize, c.C1 ? c.C0 : 8));
+    WTPSE_REQUIRE(c.nslab > 0 && c.nslab <= wgrad_x3_geometry(c.B, c.H, c.W, Cin, c.Cout).t.tiles);
+  } else {
+    WTPSE_REQUIRE((c.bn_y == nullptr) == (c.bn_coef == nullptr));
+    WTPSE_REQUIRE(wtpse_wgrad_r_supported(Cin, c.Cout, c.ksize, c.C1 ? c.C0 : 16, c.W));
+    WgradRPlan p;
+    WTPSE_REQUIRE(wgrad_r_plan(c.B, c.H, c.W, Cin, c.Cout, p));
+    WTPSE_REQUIRE(c.nslab == p.nslab);
+    WTPSE_REQUIRE(!c.dbias || p.mf * p.nf == 1);            // bias gradient: the 16 -> 16 layers without BatchNorm (DeepWT)
+    WTPSE_REQUIRE(!(c.dbias && c.bn_y));
+    // 16-pixel-wide maps (twin): instantiated for the 32 x 32 blocks only, without a bias gradient, dY materialised
+    WTPSE_REQUIRE(c.W != 16 || (p.mf == 2 && p.nf == 2 && !c.dbias && !c.bn_y));
+    // wgrad_r_k marks a row out of range in the top bit of its buffer offset: every valid offset is below 2^31
+    WTPSE_REQUIRE((long long)(c.C0 > c.C1 ? c.C0 : c.C1) * c.H * c.W * 4 < (1ll << 31) && (long long)c.Cout * c.H * c.W * 4 < (1ll << 31));
+  }
+  return 0;
 }
 
-extern "C" int wtpse_conv_wgrad(const float* dy, const float* x0, int C0, const float* x1, int C1, const float* pro0,
-                                const float* pro1, int pro_relu, float* slab, float* dbias_slab, int ksplit, float* dw, float* dbias,
-                                int accumulate, int B, int H, int W, int Cout, int ksize, void* stream) {
-  WTPSE_REQUIRE(dy && x0 && slab && dw && B > 0 && H > 0 && W > 0 && C0 > 0 && C1 >= 0 && Cout > 0 && ksplit > 0);
-  WTPSE_REQUIRE(ksize == 1 || ksize == 3);
-  WTPSE_REQUIRE((C1 == 0) == (x1 == nullptr));
-  WTPSE_REQUIRE((dbias == nullptr) == (dbias_slab == nullptr));
+// The launcher of conv_wgrad_k.
+static int wgrad_launch_fp32(const WgradCall& c, hipStream_t st) {
+  const WgradGeometry g = wgrad_geometry(c.B, c.H, c.W, c.C0 + c.C1, c.Cout);
   WgradArgs a;
-  a.dy = dy; a.x0 = x0; a.x1 = x1; a.pro0 = pro0; a.pro1 = pro1; a.slab = slab; a.dbias = dbias_slab;
-  a.B = B; a.H = H; a.W = W; a.C0 = C0; a.C1 = C1; a.Cin = C0 + C1; a.Cout = Cout; a.pro_relu = pro_relu;
-  const WgradGeometry g = wgrad_geometry(B, H, W, a.Cin, Cout);
-  const int MB = g.MB, taps = ksize * ksize;
-  const bool p32 = MB == 32;
-  a.cg = g.cg;
-  a.ngroups = g.ngroups;
-  WTPSE_REQUIRE(C1 == 0 || C0 % 16 == 0);   // a 16-channel half group must not straddle the two inputs
-  a.nblk = ceil_div(a.cg * taps, MB);
-  const bool narrow = g.t.TW == 16;
-  a.tiles_x = g.t.tiles_x;
-  a.tiles_y = g.t.tiles_y;
-  a.ntiles = g.t.tiles;
-  WTPSE_REQUIRE(ksplit <= a.ntiles);
-  hipStream_t st = (hipStream_t)stream;
-  dim3 grid((unsigned)(ceil_div(Cout, MB) * a.ngroups), (unsigned)ksplit);
+  a.dy = c.dy; a.x0 = c.x0; a.x1 = c.x1; a.pro0 = c.pro0; a.pro1 = c.pro1; a.slab = c.slab; a.dbias = c.dbias_slab;
+  a.B = c.B; a.H = c.H; a.W = c.W; a.C0 = c.C0; a.C1 = c.C1; a.Cin = c.C0 + c.C1; a.Cout = c.Cout; a.pro_relu = c.pro_relu;
+  a.tiles_x = g.t.tiles_x; a.tiles_y = g.t.tiles_y; a.ntiles = g.t.tiles;
+  a.cg = g.cg; a.ngroups = g.ngroups; a.nblk = ceil_div(g.cg * c.ksize * c.ksize, g.MB);
+  const bool p32 = g.MB == 32, narrow = g.t.TW == 16;
+  dim3 grid((unsigned)g.nx, (unsigned)c.nslab);
   // instantiated N-block counts: 3x3 -> {1, 2, 5, 9}, 1x1 -> {1}
-  const int nb_inst = ksize == 1 ? 1 : (a.nblk <= 1 ? 1 : a.nblk <= 2 ? 2 : a.nblk <= 5 ? 5 : 9);
+  const int nb_inst = c.ksize == 1 ? 1 : (a.nblk <= 1 ? 1 : a.nblk <= 2 ? 2 : a.nblk <= 5 ? 5 : 9);
 #define WG_LAUNCH(KS, P, T, N, F) hipLaunchKernelGGL((conv_wgrad_k<KS, P, T, N, F>), grid, dim3(256), 0, st, a)
 #define WG_TW(KS, P, N, F) do { if (narrow) WG_LAUNCH(KS, P, 4, N, F); else WG_LAUNCH(KS, P, 5, N, F); } while (0)
 #define WG_NB(KS, P) do { if (nb_inst == 1) WG_TW(KS, P, 1, false); else if (nb_inst == 2) WG_TW(KS, P, 2, false); \
-                          else if (nb_inst == 5) WG_TW(KS, P, 5, false); else if (a.cg == MB) WG_TW(KS, P, 9, true); \
+                          else if (nb_inst == 5) WG_TW(KS, P, 5, false); else if (a.cg == g.MB) WG_TW(KS, P, 9, true); \
                           else WG_TW(KS, P, 9, false); } while (0)
-  if (ksize == 3) {
+  if (c.ksize == 3) {
     if (p32) WG_NB(3, true); else WG_NB(3, false);
   } else {
     if (p32) WG_TW(1, true, 1, false); else WG_TW(1, false, 1, false);
@@ -1359,11 +1364,24 @@ extern "C" int wtpse_conv_wgrad(const float* dy, const float* x0, int C0, const 
 #undef WG_NB
 #undef WG_TW
 #undef WG_LAUNCH
-  int rc = wtpse_status();
-  if (rc) return rc;
-  const int n = Cout * a.Cin * taps;
-  const int nblk_w = ceil_div(n, 32), nblk_b = dbias ? ceil_div(Cout, 32) : 0;
-  hipLaunchKernelGGL(wgrad_reduce_k, dim3(nblk_w + nblk_b), dim3(256), 0, st, slab, ksplit, n, dw, accumulate, nblk_w,
-                     dbias_slab, Cout, dbias);
+  return 0;
+}
+
+int wgrad_run(const WgradCall& c, int family, hipStream_t st) {
+  if (const int rc = wgrad_check(c, family)) return rc;
+  if (const int rc = family == WGRAD_FP32 ? wgrad_launch_fp32(c, st) : family == WGRAD_X3 ? wgrad_launch_x3(c, st) : wgrad_launch_r(c, st))
+    return rc;
+  if (const int rc = wtpse_status()) return rc;
+  wgrad_fold(c, family, st);
   return wtpse_status();
+}
+
+extern "C" int wtpse_conv_wgrad(const float* dy, const float* x0, int C0, const float* x1, int C1, const float* pro0,
+                                const float* pro1, int pro_relu, float* slab, float* dbias_slab, int ksplit, float* dw, float* dbias,
+                                int accumulate, int B, int H, int W, int Cout, int ksize, void* stream) {
+  WgradCall c;
+  c.dy = dy; c.x0 = x0; c.C0 = C0; c.x1 = x1; c.C1 = C1; c.pro0 = pro0; c.pro1 = pro1; c.pro_relu = pro_relu;
+  c.slab = slab; c.dbias_slab = dbias_slab; c.nslab = ksplit; c.dw = dw; c.dbias = dbias; c.accumulate = accumulate;
+  c.B = B; c.H = H; c.W = W; c.Cout = Cout; c.ksize = ksize;
+  return wgrad_run(c, WGRAD_FP32, (hipStream_t)stream);
 }

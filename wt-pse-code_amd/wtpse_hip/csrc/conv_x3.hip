@@ -514,52 +514,35 @@ static bool wgrad_x3_tw16(int W) {
   return !tw32;
 }
 
-// conv_wgrad_x3_k: blk x blk channels per workgroup (quadrants: 64 on 64-pixel tiles, else 32 on 128-pixel tiles)
-struct WgradX3Geometry {
-  Tiling t;
-  int q, blk;
-};
-static WgradX3Geometry wgrad_x3_geometry(int B, int H, int W, int Cin, int Cout) {
+WgradX3Geometry wgrad_x3_geometry(int B, int H, int W, int Cin, int Cout) {
   WgradX3Geometry g;
   g.q = wgrad_x3_quadrants(Cin, Cout) ? 1 : 0;
   g.blk = g.q ? 64 : 32;
   g.t = make_tiling(B, H, W, wgrad_x3_tw16(W), g.q ? 64 : 128);
-  return g;
-}
-
-extern "C" int wtpse_wgrad_x3_ksplit(int B, int H, int W, int Cin, int Cout) {
-  const WgradX3Geometry g = wgrad_x3_geometry(B, H, W, Cin, Cout);
-  const int nx = (Cout / g.blk) * (Cin / g.blk);
+  g.nci = Cin / g.blk;
+  g.nx = (Cout / g.blk) * g.nci;
   int target = 512;    // two workgroups per CU
   // tuning override, read once per process and range-checked (the slab buffer is sized from this query)
   static const int wgs_override = [] { const char* e = getenv("WTPSE_X3_WGS"); const int v = e ? atoi(e) : 0; return (v >= 1 && v <= 65536) ? v : 0; }();
   if (wgs_override) target = wgs_override;
-  int ks = target / nx;
-  if (ks < 1) ks = 1;
-  if (ks > g.t.tiles) ks = g.t.tiles;
-  return ks;
+  g.ksplit = target / g.nx;
+  if (g.ksplit < 1) g.ksplit = 1;
+  if (g.ksplit > g.t.tiles) g.ksplit = g.t.tiles;
+  return g;
 }
 
-// Same contract as wtpse_conv_wgrad (include/wtpse_hip.h) without the bias gradient; requires wtpse_wgrad_x3_supported().
-extern "C" int wtpse_conv_wgrad_x3(const float* dy, const float* x0, int C0, const float* x1, int C1, const float* pro0,
-                                   const float* pro1, int pro_relu, float* slab, int ksplit, float* dw, int accumulate, int B,
-                                   int H, int W, int Cout, int ksize, void* stream) {
-  WTPSE_REQUIRE(dy && x0 && slab && dw && B > 0 && H > 0 && W > 0 && C0 > 0 && C1 >= 0 && Cout > 0 && ksplit > 0);
-  WTPSE_REQUIRE((C1 == 0) == (x1 == nullptr));
-  const int Cin = C0 + C1;
-  WTPSE_REQUIRE(wtpse_wgrad_x3_supported(Cin, Cout, ksize, C1 ? C0 : 8));
-  const WgradX3Geometry g = wgrad_x3_geometry(B, H, W, Cin, Cout);
+extern "C" int wtpse_wgrad_x3_ksplit(int B, int H, int W, int Cin, int Cout) { return wgrad_x3_geometry(B, H, W, Cin, Cout).ksplit; }
+
+// The launcher of conv_wgrad_x3_k.
+int wgrad_launch_x3(const WgradCall& c, hipStream_t st) {
+  const int Cin = c.C0 + c.C1;
+  const WgradX3Geometry g = wgrad_x3_geometry(c.B, c.H, c.W, Cin, c.Cout);
   const bool q = g.q != 0, narrow = g.t.TW == 16;
   WgradX3Args a;
-  a.dy = dy; a.x0 = x0; a.x1 = x1; a.pro0 = pro0; a.pro1 = pro1; a.slab = slab;
-  a.B = B; a.H = H; a.W = W; a.C0 = C0; a.C1 = C1; a.Cin = Cin; a.Cout = Cout; a.pro_relu = pro_relu;
-  a.tiles_x = g.t.tiles_x;
-  a.tiles_y = g.t.tiles_y;
-  a.ntiles = g.t.tiles;
-  WTPSE_REQUIRE(ksplit <= a.ntiles);
-  a.nci = Cin / g.blk;
-  dim3 grid((unsigned)((Cout / g.blk) * a.nci), (unsigned)ksplit);
-  hipStream_t st = (hipStream_t)stream;
+  a.dy = c.dy; a.x0 = c.x0; a.x1 = c.x1; a.pro0 = c.pro0; a.pro1 = c.pro1; a.slab = c.slab;
+  a.B = c.B; a.H = c.H; a.W = c.W; a.C0 = c.C0; a.C1 = c.C1; a.Cin = Cin; a.Cout = c.Cout; a.pro_relu = c.pro_relu;
+  a.tiles_x = g.t.tiles_x; a.tiles_y = g.t.tiles_y; a.ntiles = g.t.tiles; a.nci = g.nci;
+  dim3 grid((unsigned)g.nx, (unsigned)c.nslab);
   if (q) {
     if (narrow) hipLaunchKernelGGL((conv_wgrad_x3_k<3, 4, true>), grid, dim3(256), 0, st, a);
     else hipLaunchKernelGGL((conv_wgrad_x3_k<3, 5, true>), grid, dim3(256), 0, st, a);
@@ -567,8 +550,16 @@ extern "C" int wtpse_conv_wgrad_x3(const float* dy, const float* x0, int C0, con
     if (narrow) hipLaunchKernelGGL((conv_wgrad_x3_k<3, 4, false>), grid, dim3(256), 0, st, a);
     else hipLaunchKernelGGL((conv_wgrad_x3_k<3, 5, false>), grid, dim3(256), 0, st, a);
   }
-  int rc = wtpse_status();
-  if (rc) return rc;
-  wgrad_reduce_launch(slab, ksplit, Cout * Cin * 9, dw, accumulate, stream);
-  return wtpse_status();
+  return 0;
+}
+
+// Same contract as wtpse_conv_wgrad (include/wtpse_hip.h) without the bias gradient; requires wtpse_wgrad_x3_supported().
+extern "C" int wtpse_conv_wgrad_x3(const float* dy, const float* x0, int C0, const float* x1, int C1, const float* pro0,
+                                   const float* pro1, int pro_relu, float* slab, int ksplit, float* dw, int accumulate, int B,
+                                   int H, int W, int Cout, int ksize, void* stream) {
+  WgradCall c;
+  c.dy = dy; c.x0 = x0; c.C0 = C0; c.x1 = x1; c.C1 = C1; c.pro0 = pro0; c.pro1 = pro1; c.pro_relu = pro_relu;
+  c.slab = slab; c.nslab = ksplit; c.dw = dw; c.accumulate = accumulate;
+  c.B = B; c.H = H; c.W = W; c.Cout = Cout; c.ksize = ksize;
+  return wgrad_run(c, WGRAD_X3, (hipStream_t)stream);
 }

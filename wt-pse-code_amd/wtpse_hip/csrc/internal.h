@@ -1,7 +1,7 @@
 // What crosses translation units of the library without being part of the C ABI (include/wtpse_hip.h): declared once, here.
 // C++ linkage, so the linker checks the types, and hidden visibility: the library exports the header's names only.
-// The host side of the convolutions lives here: ConvCall (what an entry point asks for), conv_run (check, then the launcher of the
-// kernel family) and the tiling functions that size queries and launches share.
+// The host side of the convolutions lives here: ConvCall / WgradCall (what an entry point asks for), conv_run / wgrad_run (check, then
+// the launcher of the kernel family) and the tiling functions that size queries and launches share.
 #pragma once
 #include <cstdlib>
 #include "common.h"
@@ -63,10 +63,36 @@ struct X3Tiling {
 };
 WTPSE_INTERNAL X3Tiling x3_tiling(int B, int H, int W, int Cout, int ksize);
 
-// conv.hip: fold of the k-split weight-gradient slabs; the second with the bias-gradient slabs folded in the same launch
-WTPSE_INTERNAL void wgrad_reduce_launch(const float* slab, int ksplit, int n, float* dw, int accumulate, void* stream);
-WTPSE_INTERNAL void wgrad_reduce_launch2(const float* slab, int ksplit, int n, float* dw, int accumulate, const float* slab_b,
-                                         int n_b, float* db, void* stream);
+// One weight gradient as its entry point describes it, like ConvCall: the four extern "C" entry points (conv.hip, conv_x3.hip,
+// wgrad_r.hip) fill the fields by name and return wgrad_run(): wgrad_check (every precondition once, the per-family ones keyed on the
+// family), the family's launcher (the only place that fills its kernel argument struct), the fold of the slabs (wgrad_fold).
+struct WgradCall {
+  const float* dy = nullptr;                      // the _bn form of WGRAD_R (bn_y, bn_coef): the masked incoming gradient g
+  const float* x0 = nullptr; int C0 = 0;
+  const float* x1 = nullptr; int C1 = 0;          // virtual concat behind x0
+  const float* pro0 = nullptr; const float* pro1 = nullptr; int pro_relu = 0;
+  float* slab = nullptr; float* dbias_slab = nullptr; int nslab = 0;       // the k-split (FP32, X3) or slab count (R) the caller sized them for
+  float* dw = nullptr; float* dbias = nullptr; int accumulate = 0;
+  const float* bn_y = nullptr; const float* bn_coef = nullptr; const unsigned* dy_amax = nullptr;
+  const unsigned* x_amax0 = nullptr; const unsigned* x_amax1 = nullptr;
+  int B = 0, H = 0, W = 0, Cout = 0, ksize = 0;
+};
+enum { WGRAD_FP32 = 0, WGRAD_X3 = 1, WGRAD_R = 2 };
+WTPSE_INTERNAL int wgrad_run(const WgradCall& c, int family, hipStream_t st);    // conv.hip
+WTPSE_INTERNAL int wgrad_launch_x3(const WgradCall& c, hipStream_t st);          // conv_x3.hip
+WTPSE_INTERNAL int wgrad_launch_r(const WgradCall& c, hipStream_t st);           // wgrad_r.hip
+
+// Geometry of a weight-gradient launch, one function per kernel family: the size query answers its default `ksplit` / its `nslab`,
+// wgrad_check bounds the caller's count with it, the launcher takes its grid from it.
+struct WgradX3Geometry {   // conv_wgrad_x3_k: blk x blk channels per workgroup (quadrants: 64 on 64-pixel tiles, else 32 on 128-pixel tiles)
+  Tiling t;
+  int q, blk, nci, nx, ksplit;     // nci: cin blocks; nx: (cout block, cin block) pairs, the grid's x extent
+};
+WTPSE_INTERNAL WgradX3Geometry wgrad_x3_geometry(int B, int H, int W, int Cin, int Cout);     // conv_x3.hip
+struct WgradRPlan {        // wgrad_r_k; nslab = wpp / nw: workgroups, and so slabs, per (cout block, cin block) pair
+  int mf, nf, nw, pairs, nci, wpp, nseg, rseg, units, strips, nslab;
+};
+WTPSE_INTERNAL bool wgrad_r_plan(int B, int H, int W, int Cin, int Cout, WgradRPlan& p);      // wgrad_r.hip
 
 // Folding the statistics inside the launch makes every workgroup live ~2.5 us longer (its partials must be visible before it takes
 // its ticket: store acknowledgement + one L2 atomic round trip).  Measured on the step (back to back, profiles/r03_*): with the

@@ -517,16 +517,12 @@ __global__ __launch_bounds__((64 * WgradRGeom<MF, NF>::NW), 1) void wgrad_r_k(Wg
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
-struct WgradRPlan {
-  int mf, nf, nw, pairs, nci, wpp, nseg, rseg, units, strips;
-};
-
 // W == 16 (the deepest level's maps): two images side by side per 32-pixel k-step (WgradRArgs::twin).  WTPSE_WGRAD_R_TWIN=0: those
 // layers stay on the LDS kernel (conv_wgrad_x3_k).
 static const bool g_wgrad_r_twin = [] { const char* e = getenv("WTPSE_WGRAD_R_TWIN"); return !(e && e[0] == '0'); }();
 static bool wgrad_r_width_ok(int W) { return W % 32 == 0 || (W == 16 && g_wgrad_r_twin); }
 
-static bool wgrad_r_plan(int B, int H, int W, int Cin, int Cout, WgradRPlan& p) {
+bool wgrad_r_plan(int B, int H, int W, int Cin, int Cout, WgradRPlan& p) {
   if (!wgrad_r_width_ok(W) || H < 1 || Cin % 16 != 0 || Cout % 16 != 0) return false;
   p.mf = Cout % 32 == 0 ? 2 : 1;
   p.nf = Cin % 32 == 0 ? 2 : 1;
@@ -550,6 +546,7 @@ static bool wgrad_r_plan(int B, int H, int W, int Cin, int Cout, WgradRPlan& p) 
   p.units = cols * p.nseg;
   if (wpp > p.units) wpp = (p.units + p.nw - 1) / p.nw * p.nw;   // trailing waves get no unit: they contribute zero slabs
   p.wpp = wpp;
+  p.nslab = wpp / p.nw;
   return true;
 }
 
@@ -561,88 +558,56 @@ extern "C" int wtpse_wgrad_r_supported(int Cin, int Cout, int ksize, int C0, int
 // slabs of a wtpse_conv_wgrad_r launch: `slab` holds that many [Cout][Cin][9] partial gradients, `dbias_slab` as many [Cout]
 extern "C" int wtpse_wgrad_r_slabs(int B, int H, int W, int Cin, int Cout) {
   WgradRPlan p;
-  if (!wgrad_r_plan(B, H, W, Cin, Cout, p)) return 0;
-  return p.wpp / p.nw;
+  return wgrad_r_plan(B, H, W, Cin, Cout, p) ? p.nslab : 0;
 }
 
-static int wgrad_r_impl(const float* dy, const float* x0, int C0, const float* x1, int C1, const float* pro0,
-                        const float* pro1, int pro_relu, float* slab, float* dbias_slab, int nslab, float* dw,
-                        float* dbias, int accumulate, int B, int H, int W, int Cout, const float* bn_y, const float* bn_coef,
-                        const unsigned* dy_amax, const unsigned* x_amax0, const unsigned* x_amax1, void* stream) {
-  WTPSE_REQUIRE(dy && x0 && slab && dw && B > 0 && H > 0 && W > 0 && C0 > 0 && C1 >= 0 && Cout > 0);
-  WTPSE_REQUIRE((C1 == 0) == (x1 == nullptr));
-  WTPSE_REQUIRE((dbias == nullptr) == (dbias_slab == nullptr));
-  WTPSE_REQUIRE((bn_y == nullptr) == (bn_coef == nullptr));
-  const int Cin = C0 + C1;
-  WTPSE_REQUIRE(wtpse_wgrad_r_supported(Cin, Cout, 3, C1 ? C0 : 16, W));
+// Which wgrad_r_k a call runs.  mode = wtpse_x3_terms(); big: 32 channels on at least one side of the block (the MFMA-bound layers).
+//   x2h (mode 2): PRO always on (the X scale rides in the prologue coefficients); the 16 x 16 blocks, HBM-bound, only with an amax table
+//     of dY (see wtpse_hip.h); never the fused-BatchNorm form (nothing knows the largest magnitude of a dY that is never materialised);
+//   one term (mode 1, bf16 mode): the big blocks; the 16 x 16 blocks (the 16-channel layers, which keep three terms in their forward
+//     pass too) and the fused-BatchNorm form stay on three; three terms otherwise.
+// The twin form (16-pixel-wide maps) is 2 x 2 blocks of a materialised dY (wgrad_check), so it follows the mode: 1 / 2 / 3.
+struct WgradRVariant { int mf, nf; bool pro, bias, aff; int terms; bool twin; };
+static WgradRVariant wgrad_r_variant(const WgradRPlan& p, int mode, bool pro, bool bias, bool aff, bool dy_table, bool twin) {
+  const bool big = p.mf * p.nf >= 2;
+  WgradRVariant v = {p.mf, p.nf, pro, bias, aff, 3, twin};
+  if (mode == 2 && !aff && (dy_table || big)) { v.terms = 2; v.pro = true; }
+  else if (mode == 1 && !aff && big) v.terms = 1;
+  return v;
+}
+
+// Every instantiated wgrad_r_k, once, in the code object's order: X(MF, NF, PRO, BIAS, AFF, TERMS, TWIN); WR_PRO: with and without PRO.
+#define WR_PRO(X, M, N, B, A, T, W) X(M, N, true, B, A, T, W) X(M, N, false, B, A, T, W)
+#define WGRAD_R_VARIANTS(X) \
+  X(2, 2, true, false, false, 2, true) \
+  X(2, 2, true, false, false, 2, false) X(2, 1, true, false, false, 2, false) X(1, 2, true, false, false, 2, false) \
+  X(1, 1, true, true, false, 2, false) X(1, 1, true, false, false, 2, false) \
+  WR_PRO(X, 2, 2, false, false, 1, true) WR_PRO(X, 2, 2, false, false, 3, true) \
+  WR_PRO(X, 2, 2, false, false, 1, false) WR_PRO(X, 2, 1, false, false, 1, false) WR_PRO(X, 1, 2, false, false, 1, false) \
+  WR_PRO(X, 2, 2, false, true, 3, false) WR_PRO(X, 2, 2, false, false, 3, false) \
+  WR_PRO(X, 2, 1, false, true, 3, false) WR_PRO(X, 2, 1, false, false, 3, false) \
+  WR_PRO(X, 1, 2, false, true, 3, false) WR_PRO(X, 1, 2, false, false, 3, false) \
+  WR_PRO(X, 1, 1, true, false, 3, false) WR_PRO(X, 1, 1, false, true, 3, false) WR_PRO(X, 1, 1, false, false, 3, false)
+
+// The launcher of wgrad_r_k.
+int wgrad_launch_r(const WgradCall& c, hipStream_t st) {
+  const int Cin = c.C0 + c.C1;
   WgradRPlan p;
-  WTPSE_REQUIRE(wgrad_r_plan(B, H, W, Cin, Cout, p));
-  WTPSE_REQUIRE(nslab == p.wpp / p.nw);
-  WTPSE_REQUIRE(!dbias || p.mf * p.nf == 1);               // bias gradient: the 16 -> 16 layers without BatchNorm (DeepWT)
-  WTPSE_REQUIRE(!(dbias && bn_y));
-  WTPSE_REQUIRE((long long)(C0 > C1 ? C0 : C1) * H * W * 4 < (1ll << 31) && (long long)Cout * H * W * 4 < (1ll << 31));
+  if (!wgrad_r_plan(c.B, c.H, c.W, Cin, c.Cout, p)) return WTPSE_EINVAL;
   WgradRArgs a;
-  a.dy = dy; a.x0 = x0; a.x1 = x1; a.pro0 = pro0; a.pro1 = pro1; a.slab = slab; a.slab_b = dbias_slab;
-  a.bn_y = bn_y; a.bn_coef = bn_coef; a.dy_amax = dy_amax; a.x_amax0 = x_amax0; a.x_amax1 = x1 ? x_amax1 : nullptr;
-  a.B = B; a.H = H; a.W = W; a.C0 = C0; a.C1 = C1; a.Cin = Cin; a.Cout = Cout; a.pro_relu = pro_relu;
-  a.strips = p.strips; a.nseg = p.nseg; a.rseg = p.rseg; a.units = p.units; a.wpp = p.wpp; a.nci = p.nci; a.twin = W == 16 ? 1 : 0;
-  const bool pro = pro0 != nullptr || pro1 != nullptr || pro_relu != 0;
-  const bool bias = dbias != nullptr, aff = bn_y != nullptr;
-  dim3 grid((unsigned)(p.pairs * (p.wpp / p.nw)));
-  const dim3 blk((unsigned)(64 * p.nw));
-  hipStream_t st = (hipStream_t)stream;
-#define WR_LAUNCH(M, N) do { \
-    if (aff) { if (pro) hipLaunchKernelGGL((wgrad_r_k<M, N, true, false, true>), grid, blk, 0, st, a); \
-               else hipLaunchKernelGGL((wgrad_r_k<M, N, false, false, true>), grid, blk, 0, st, a); } \
-    else if (pro) hipLaunchKernelGGL((wgrad_r_k<M, N, true, false>), grid, blk, 0, st, a); \
-    else hipLaunchKernelGGL((wgrad_r_k<M, N, false, false>), grid, blk, 0, st, a); } while (0)
-  // bf16 mode (wtpse_x3_terms(1), conv_x3.hip): one term per operand in the blocks of the MFMA-bound layers; the 16 x 16 blocks (the
-  // 16-channel layers, which keep three terms in their forward pass too) and the fused-BatchNorm form stay on three
-#define WR_LAUNCH1(M, N) do { \
-    if (pro) hipLaunchKernelGGL((wgrad_r_k<M, N, true, false, false, 1>), grid, blk, 0, st, a); \
-    else hipLaunchKernelGGL((wgrad_r_k<M, N, false, false, false, 1>), grid, blk, 0, st, a); } while (0)
-  // x2h (wtpse_x3_terms(2)): every block shape, PRO always on (the X scale rides in the prologue coefficients); the fused-BatchNorm
-  // form (aff) stays on three bf16 terms (nothing knows the largest magnitude of a dY that is never materialised)
-#define WR_LAUNCH2(M, N) hipLaunchKernelGGL((wgrad_r_k<M, N, true, false, false, 2>), grid, blk, 0, st, a)
-  if (g_x3_terms == 2 && !aff && (dy_amax || p.mf * p.nf >= 2)) {     // (16 x 16 blocks without an amax table: x3, see wtpse_hip.h)
-    if (a.twin) {
-      WTPSE_REQUIRE(p.mf == 2 && p.nf == 2 && !bias);
-      hipLaunchKernelGGL((wgrad_r_k<2, 2, true, false, false, 2, true>), grid, blk, 0, st, a);
-    } else if (p.mf == 2 && p.nf == 2) WR_LAUNCH2(2, 2);
-    else if (p.mf == 2) WR_LAUNCH2(2, 1);
-    else if (p.nf == 2) WR_LAUNCH2(1, 2);
-    else if (bias) hipLaunchKernelGGL((wgrad_r_k<1, 1, true, true, false, 2>), grid, blk, 0, st, a);
-    else WR_LAUNCH2(1, 1);
-  } else
-#undef WR_LAUNCH2
-  if (a.twin) {        // 16-pixel-wide maps: 32 x 32 blocks, no bias gradient, dY materialised
-    WTPSE_REQUIRE(p.mf == 2 && p.nf == 2 && !bias && !aff);
-    if (g_x3_terms == 1) {
-      if (pro) hipLaunchKernelGGL((wgrad_r_k<2, 2, true, false, false, 1, true>), grid, blk, 0, st, a);
-      else hipLaunchKernelGGL((wgrad_r_k<2, 2, false, false, false, 1, true>), grid, blk, 0, st, a);
-    } else {
-      if (pro) hipLaunchKernelGGL((wgrad_r_k<2, 2, true, false, false, 3, true>), grid, blk, 0, st, a);
-      else hipLaunchKernelGGL((wgrad_r_k<2, 2, false, false, false, 3, true>), grid, blk, 0, st, a);
-    }
-  } else
-  if (g_x3_terms == 1 && !aff && p.mf * p.nf >= 2) {
-    if (p.mf == 2 && p.nf == 2) WR_LAUNCH1(2, 2);
-    else if (p.mf == 2) WR_LAUNCH1(2, 1);
-    else WR_LAUNCH1(1, 2);
-  } else
-  if (p.mf == 2 && p.nf == 2) WR_LAUNCH(2, 2);
-  else if (p.mf == 2) WR_LAUNCH(2, 1);
-  else if (p.nf == 2) WR_LAUNCH(1, 2);
-  else if (bias) {
-    if (pro) hipLaunchKernelGGL((wgrad_r_k<1, 1, true, true>), grid, blk, 0, st, a);
-    else hipLaunchKernelGGL((wgrad_r_k<1, 1, false, true>), grid, blk, 0, st, a);
-  } else WR_LAUNCH(1, 1);
-#undef WR_LAUNCH
-#undef WR_LAUNCH1
-  int rc = wtpse_status();
-  if (rc) return rc;
-  wgrad_reduce_launch2(slab, nslab, Cout * Cin * 9, dw, accumulate, dbias_slab, Cout, dbias, stream);
-  return wtpse_status();
+  a.dy = c.dy; a.x0 = c.x0; a.x1 = c.x1; a.pro0 = c.pro0; a.pro1 = c.pro1; a.slab = c.slab; a.slab_b = c.dbias_slab;
+  a.bn_y = c.bn_y; a.bn_coef = c.bn_coef; a.dy_amax = c.dy_amax; a.x_amax0 = c.x_amax0; a.x_amax1 = c.x1 ? c.x_amax1 : nullptr;
+  a.B = c.B; a.H = c.H; a.W = c.W; a.C0 = c.C0; a.C1 = c.C1; a.Cin = Cin; a.Cout = c.Cout; a.pro_relu = c.pro_relu;
+  a.strips = p.strips; a.nseg = p.nseg; a.rseg = p.rseg; a.units = p.units; a.wpp = p.wpp; a.nci = p.nci; a.twin = c.W == 16 ? 1 : 0;
+  const WgradRVariant v = wgrad_r_variant(p, g_x3_terms, c.pro0 != nullptr || c.pro1 != nullptr || c.pro_relu != 0, c.dbias != nullptr,
+                                          c.bn_y != nullptr, c.dy_amax != nullptr, a.twin != 0);
+  const dim3 grid((unsigned)(p.pairs * p.nslab)), blk((unsigned)(64 * p.nw));
+#define WR_CASE(M, N, P, BI, A, T, TW) \
+  if (v.mf == M && v.nf == N && v.pro == P && v.bias == BI && v.aff == A && v.terms == T && v.twin == TW) { \
+    hipLaunchKernelGGL((wgrad_r_k<M, N, P, BI, A, T, TW>), grid, blk, 0, st, a); return 0; }
+  WGRAD_R_VARIANTS(WR_CASE)
+#undef WR_CASE
+  return WTPSE_EINVAL;      // not instantiated
 }
 
 // Same contract as wtpse_conv_wgrad (include/wtpse_hip.h), 3x3 only; requires wtpse_wgrad_r_supported().
@@ -650,8 +615,11 @@ extern "C" int wtpse_conv_wgrad_r(const float* dy, const float* x0, int C0, cons
                                   const float* pro1, int pro_relu, float* slab, float* dbias_slab, int nslab, float* dw,
                                   float* dbias, int accumulate, int B, int H, int W, int Cout, const unsigned* dy_amax,
                                   const unsigned* x_amax0, const unsigned* x_amax1, void* stream) {
-  return wgrad_r_impl(dy, x0, C0, x1, C1, pro0, pro1, pro_relu, slab, dbias_slab, nslab, dw, dbias, accumulate, B, H, W, Cout,
-                      nullptr, nullptr, dy_amax, x_amax0, x_amax1, stream);
+  WgradCall c;
+  c.dy = dy; c.x0 = x0; c.C0 = C0; c.x1 = x1; c.C1 = C1; c.pro0 = pro0; c.pro1 = pro1; c.pro_relu = pro_relu;
+  c.slab = slab; c.dbias_slab = dbias_slab; c.nslab = nslab; c.dw = dw; c.dbias = dbias; c.accumulate = accumulate;
+  c.dy_amax = dy_amax; c.x_amax0 = x_amax0; c.x_amax1 = x_amax1; c.B = B; c.H = H; c.W = W; c.Cout = Cout; c.ksize = 3;
+  return wgrad_run(c, WGRAD_R, (hipStream_t)stream);
 }
 
 // The same with dY given as the un-applied second half of a BatchNorm backward: dY = k1[c] * g + k2[c] * bn_y + k3[c],
@@ -660,6 +628,9 @@ extern "C" int wtpse_conv_wgrad_r_bn(const float* g, const float* bn_y, const fl
                                      const float* x1, int C1, const float* pro0, const float* pro1, int pro_relu, float* slab,
                                      int nslab, float* dw, int accumulate, int B, int H, int W, int Cout, void* stream) {
   WTPSE_REQUIRE(bn_y && bn_coef);
-  return wgrad_r_impl(g, x0, C0, x1, C1, pro0, pro1, pro_relu, slab, nullptr, nslab, dw, nullptr, accumulate, B, H, W, Cout, bn_y,
-                      bn_coef, nullptr, nullptr, nullptr, stream);
+  WgradCall c;
+  c.dy = g; c.bn_y = bn_y; c.bn_coef = bn_coef; c.x0 = x0; c.C0 = C0; c.x1 = x1; c.C1 = C1; c.pro0 = pro0; c.pro1 = pro1;
+  c.pro_relu = pro_relu; c.slab = slab; c.nslab = nslab; c.dw = dw; c.accumulate = accumulate;
+  c.B = B; c.H = H; c.W = W; c.Cout = Cout; c.ksize = 3;
+  return wgrad_run(c, WGRAD_R, (hipStream_t)stream);
 }

@@ -376,21 +376,21 @@ def dgrad_bnb(dy, wpacked_ptr, layout, cout, ksize, bn_y, bn_ss, bn_mean, bn_rel
     return out0, out1, stats, None
 
 
-def _wgrad_dims(dy, x0, x1):
-    """The prelude of the weight-gradient wrappers: -> (lib, B, cout, H, W, C0, C1, cin) of dy [B,cout,H,W] and the inputs x0 (, x1)."""
+def _wgrad_prelude(query, dy, x0, x1, taps, want_dbias=False):
+    """The prelude of the weight-gradient wrappers, for dy [B,cout,H,W] and the inputs x0 (, x1): the slab count the family's size
+    `query` gives and the workspaces of that many slabs -> (lib, n, slab, dbias_slab | None, B, cout, H, W, C0, C1)."""
     _chk(dy, "dy"); _chk(x0, "x0"); _chk(x1, "x1")
     B, cout, H, W = dy.shape
-    C0 = x0.shape[1]
-    C1 = 0 if x1 is None else x1.shape[1]
-    return lib(), B, cout, H, W, C0, C1, C0 + C1
+    L, C0, C1 = lib(), x0.shape[1], 0 if x1 is None else x1.shape[1]
+    n = L.query(query, B, H, W, C0 + C1, cout)
+    slab = workspace("wgrad_slab", n * cout * (C0 + C1) * taps, dy.device)
+    dbs = workspace("wgrad_dbias", n * cout, dy.device) if want_dbias else None
+    return L, n, slab, dbs, B, cout, H, W, C0, C1
 
 
 def conv_wgrad(dy, x0, x1, ksize, dw, dbias, pro0=None, pro_relu=0, accumulate=False, pro1=None):
     """dw / dbias are views into the flat gradient buffer ([Cout,Cin,k,k] / [Cout] or None)."""
-    L, B, cout, H, W, C0, C1, cin = _wgrad_dims(dy, x0, x1)
-    ks = L.query("wtpse_wgrad_ksplit", B, H, W, cin, cout)
-    slab = workspace("wgrad_slab", ks * cout * cin * ksize * ksize, dy.device)
-    dbs = workspace("wgrad_dbias", ks * cout, dy.device) if dbias is not None else None
+    L, ks, slab, dbs, B, cout, H, W, C0, C1 = _wgrad_prelude("wtpse_wgrad_ksplit", dy, x0, x1, ksize * ksize, dbias is not None)
     L.call("wtpse_conv_wgrad", ptr(dy), ptr(x0), C0, ptr(x1), C1, ptr(pro0), ptr(pro1), int(pro_relu), ptr(slab), ptr(dbs), ks,
            ptr(dw), ptr(dbias), int(accumulate), B, H, W, cout, ksize, stream_ptr())
 
@@ -401,9 +401,7 @@ def wgrad_x3_supported(cin, cout, ksize, c0):
 
 def conv_wgrad_x3(dy, x0, x1, ksize, dw, pro0=None, pro_relu=0, accumulate=False, pro1=None):
     """conv_wgrad in the x3 arithmetic (csrc/conv_x3.hip); no bias gradient."""
-    L, B, cout, H, W, C0, C1, cin = _wgrad_dims(dy, x0, x1)
-    ks = L.query("wtpse_wgrad_x3_ksplit", B, H, W, cin, cout)
-    slab = workspace("wgrad_slab", ks * cout * cin * ksize * ksize, dy.device)
+    L, ks, slab, _, B, cout, H, W, C0, C1 = _wgrad_prelude("wtpse_wgrad_x3_ksplit", dy, x0, x1, ksize * ksize)
     L.call("wtpse_conv_wgrad_x3", ptr(dy), ptr(x0), C0, ptr(x1), C1, ptr(pro0), ptr(pro1), int(pro_relu), ptr(slab), ks, ptr(dw),
            int(accumulate), B, H, W, cout, ksize, stream_ptr())
 
@@ -416,10 +414,7 @@ def conv_wgrad_r(dy, x0, x1, dw, dbias=None, pro0=None, pro_relu=0, accumulate=F
                  x_amax1=None):
     """3x3 conv_wgrad in the x3 arithmetic with register-resident operands (csrc/wgrad_r.hip); with bias gradient.
     dy_amax: amax_of(dy) (x2h: the scale of the gradient operand); x_amax0 / x_amax1: the bounds of x0 / x1 as loaded."""
-    L, B, cout, H, W, C0, C1, cin = _wgrad_dims(dy, x0, x1)
-    ns = L.query("wtpse_wgrad_r_slabs", B, H, W, cin, cout)
-    slab = workspace("wgrad_slab", ns * cout * cin * 9, dy.device)
-    dbs = workspace("wgrad_dbias", ns * cout, dy.device) if dbias is not None else None
+    L, ns, slab, dbs, B, cout, H, W, C0, C1 = _wgrad_prelude("wtpse_wgrad_r_slabs", dy, x0, x1, 9, dbias is not None)
     L.call("wtpse_conv_wgrad_r", ptr(dy), ptr(x0), C0, ptr(x1), C1, ptr(pro0), ptr(pro1), int(pro_relu), ptr(slab), ptr(dbs), ns,
            ptr(dw), ptr(dbias), int(accumulate), B, H, W, cout, ptr(dy_amax), ptr(x_amax0), ptr(x_amax1), stream_ptr())
 
@@ -427,9 +422,7 @@ def conv_wgrad_r(dy, x0, x1, dw, dbias=None, pro0=None, pro_relu=0, accumulate=F
 def conv_wgrad_r_bn(g, bn_y, coef, x0, x1, dw, pro0=None, pro_relu=0, accumulate=False, pro1=None):
     """conv_wgrad_r with dY = coef[:,0] * g + coef[:,1] * bn_y + coef[:,2] formed on load (no bias gradient)."""
     _chk(bn_y, "bn_y")
-    L, B, cout, H, W, C0, C1, cin = _wgrad_dims(g, x0, x1)
-    ns = L.query("wtpse_wgrad_r_slabs", B, H, W, cin, cout)
-    slab = workspace("wgrad_slab", ns * cout * cin * 9, g.device)
+    L, ns, slab, _, B, cout, H, W, C0, C1 = _wgrad_prelude("wtpse_wgrad_r_slabs", g, x0, x1, 9)
     L.call("wtpse_conv_wgrad_r_bn", ptr(g), ptr(bn_y), ptr(coef), ptr(x0), C0, ptr(x1), C1, ptr(pro0), ptr(pro1), int(pro_relu),
            ptr(slab), ns, ptr(dw), int(accumulate), B, H, W, cout, stream_ptr())
 
