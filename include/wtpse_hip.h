@@ -433,6 +433,7 @@ int wtpse_adam_dev(float* p, const float* g, float* m, float* v, long long n, co
  *     3, 49     3   (s0 + s1) + s2
  *     19, 35    4   ((s0 + s1) + s2) + s3
  *     51        5   (((s0 + s1) + s2) + s3) + s4
+ *     115       6   ((((s0 + s1) + s2) + s3) + s4) + s5
  * The codes are historical names for the count k: both names of k = 3 and of k = 4 are accepted, every other value is refused.
  * flag: two device ints, sticky (never cleared here): when the test holds and flag[0] == 0,
  * flag[0] = 1 and flag[1] = *step_dev (the calling network's count of completed steps = the failing iteration; NULL: 0). */
@@ -472,6 +473,27 @@ int wtpse_boundary_loss(const float* x, const float* mask, const float* phi, con
 int wtpse_overlap_loss_ws(int B, int hw);
 int wtpse_overlap_loss(const float* x, const float* mask, const float* t, const float* w_dev, int B, int hw, float fp, float fn,
                        float focal, float smooth, void* ws, float* plane_loss, float* loss, float* dx, void* stream);
+
+/* ---- Lovász hinge loss per image: a segmented stable sort on the device (csrc/lovasz.hip; specification: wtpse_hip/lovasz.py) ----
+ * x, t, mask (NULL: every pixel kept), dx: [B][hw] fp32, one plane per image.  A pixel is kept iff mask == NULL or m_i != 0 (an
+ * ignored pixel is out of the set; a kept pixel's logit is x_i itself).  Per plane: sign_i = t_i > 0 ? +1 : -1,
+ * e_i = fmaf(-x_i, sign_i, 1) in fp32; the kept pixels ordered by e descending, ties by ascending pixel index; G = kept foreground
+ * pixels, c_r = foreground among the first r of the order, and in fp64 from these integers
+ *     J_r = 1 - (G - c_r) / (G + r - c_r),  g_1 = J_1,  g_r = J_r - J_{r-1},  L_b = sum_r max(e_(r), 0) g_r   (0 without a kept pixel)
+ * plane_loss[b] = L_b (fp32 [B], or NULL: not wanted), *loss = mean over b of L_b; the weight is NOT applied to either.  A kept
+ * pixel with a non-finite logit makes L_b NaN, and that plane adds nothing into dx.  ranks (int32 [B][hw], or NULL: not wanted):
+ * the 0-based place in its plane's order of every kept pixel with e > 0, -1 elsewhere.  With dx != NULL the gradient of
+ * (*w_dev) * loss, the order and g held constant, is added into dx in place, in fp64 and rounded once on the add:
+ *     dx_i += (*w_dev / B) (-sign_i) g_rank(i)     for a kept pixel with e_i > 0
+ * and no other element is written; an increment of exactly 0 leaves the element's bits alone.  w_dev: one device float (a schedule
+ * changes the weight of a recorded call between replays); may be NULL when dx is.  ws: wtpse_lovasz_loss_ws(B, hw) BYTES, 8-byte
+ * aligned (-1: refused shape; 1 <= B < 65536, 1 <= hw <= 2^30, B hw < 2^31, and the bytes — about 16 B hw — below 2^31).
+ * The sort is an LSD radix sort of (key, pixel) pairs over four 8-bit digits, a plane cut into chunks whose number depends on hw
+ * alone; every place comes from digit counts and their prefixes, never from the arrival order of an atomic, so the order is stable
+ * and the results do not depend on scheduling, nor on a plane's place in the batch or on B.  Allocates nothing, never synchronises. */
+int wtpse_lovasz_loss_ws(int B, int hw);
+int wtpse_lovasz_loss(const float* x, const float* mask, const float* t, const float* w_dev, int B, int hw, void* ws,
+                      float* plane_loss, int* ranks, float* loss, float* dx, void* stream);
 
 /* ---- weight averaging (csrc/average.hip; specification: wtpse_hip/averaging.py) --------------------------------------
  * wtpse_avg_step folds one iterate into running means, up to four segments (a_s, p_s, n_s) in ONE launch; a segment with

@@ -698,7 +698,7 @@ __global__ __launch_bounds__(256) void adam_k(float* __restrict__ p, const float
 
 // ------------------------------------------------------------------------------------------------ loss log (Trainer.py:788-800, 874-885)
 // One wave: lane j < 6 folds scalar j into its running sum (the reference's `running_x += loss.item()`: an fp32 value widened to
-// double, added to a double); lane 0 evaluates the reference's NaN test on the first k scalars (0..5), summed left to right in
+// double, added to a double); lane 0 evaluates the reference's NaN test on the first k scalars (0..6), summed left to right in
 // fp32, and raises the sticky flag.
 __global__ __launch_bounds__(64) void loss_log_k(const float* s0, const float* s1, const float* s2, const float* s3, const float* s4,
                                                  const float* s5, double* __restrict__ acc, int k, int* __restrict__ flag,
@@ -714,6 +714,7 @@ __global__ __launch_bounds__(64) void loss_log_k(const float* s0, const float* s
     if (k > 2) t = t + *s2;
     if (k > 3) t = t + *s3;
     if (k > 4) t = t + *s4;
+    if (k > 5) t = t + *s5;
     if (isnan(t) && flag[0] == 0) {
       flag[0] = 1;
       flag[1] = step_dev ? *step_dev : 0;
@@ -1036,11 +1037,11 @@ extern "C" int wtpse_adam_dev(float* p, const float* g, float* m, float* v, long
 extern "C" int wtpse_loss_log(const float* s0, const float* s1, const float* s2, const float* s3, const float* s4, const float* s5,
                               double* acc, int check_n, int* flag, const int* step_dev, void* stream) {
   // check_n -> the number of tested scalars (the table of include/wtpse_hip.h); every other value is refused
-  static const int codes[][2] = {{0, 0}, {1, 1}, {17, 2}, {3, 3}, {49, 3}, {19, 4}, {35, 4}, {51, 5}};
+  static const int codes[][2] = {{0, 0}, {1, 1}, {17, 2}, {3, 3}, {49, 3}, {19, 4}, {35, 4}, {51, 5}, {115, 6}};
   int k = -1;
   for (const auto& c : codes)
     if (c[0] == check_n) k = c[1];
-  const float* const s[5] = {s0, s1, s2, s3, s4};
+  const float* const s[6] = {s0, s1, s2, s3, s4, s5};
   WTPSE_REQUIRE(s0 && acc && flag && k >= 0);
   for (int j = 1; j < k; ++j) WTPSE_REQUIRE(s[j]);
   WTPSE_REQUIRE((((uintptr_t)acc) & 7) == 0);

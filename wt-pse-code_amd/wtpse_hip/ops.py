@@ -1048,6 +1048,36 @@ def overlap_loss(x, t, w_dev, cfg, mask=None, dx=None, want_planes=False):
     return (loss, planes) if want_planes else loss
 
 
+def lovasz_loss(x, t, w_dev, mask=None, dx=None, want_planes=False, want_ranks=False):
+    """-> the unweighted Lovász hinge loss of x [B, ...] against t, one plane per image: lovasz.lovasz_loss_host, the pixels with
+    mask == 0 taken out of the set (mask None: the disc form) — 0-dim device fp32; want_planes: also the per-plane losses [B];
+    want_ranks: also every pixel's place in its plane's order (int32 of x's shape, lovasz.lovasz_ranks_host), in that order behind
+    the loss.  With dx the call adds the gradient of (*w_dev) * loss into dx IN PLACE (w_dev: device fp32 scalar, read by the kernel)."""
+    _chk(x, "x"); _chk(t, "t"); _chk(mask, "mask"); _chk(dx, "dx"); _chk(w_dev, "w_dev")
+    if x.dim() < 2 or x.numel() == 0:
+        raise ValueError("lovasz_loss: logits [B, ..., H, W], got shape %s" % (tuple(x.shape),))
+    n, B = x.numel(), int(x.shape[0])
+    for name, v in (("t", t), ("mask", mask), ("dx", dx)):
+        if v is not None and v.numel() != n:
+            raise ValueError("lovasz_loss: %s has %d elements, x has %d" % (name, v.numel(), n))
+    if dx is not None and w_dev is None:
+        raise ValueError("lovasz_loss: dx needs the device weight w_dev")
+    L = lib()
+    nbytes = L.query("wtpse_lovasz_loss_ws", B, n // B)
+    if nbytes <= 0:
+        raise ValueError("lovasz_loss: unsupported size %s" % (tuple(x.shape),))
+    # an amax table that describes the region loss's gradient alone no longer bounds dx
+    _amax_stale(dx)
+    loss = torch.empty((), dtype=torch.float32, device=x.device)
+    planes = torch.empty((B,), dtype=torch.float32, device=x.device) if want_planes else None
+    ranks = torch.empty(x.shape, dtype=torch.int32, device=x.device) if want_ranks else None
+    ws = workspace("lovasz_loss", (nbytes + 3) // 4, x.device)
+    L.call("wtpse_lovasz_loss", ptr(x), ptr(mask), ptr(t), ptr(w_dev), B, n // B, ptr(ws), ptr(planes), ptr(ranks), ptr(loss), ptr(dx),
+           stream_ptr())
+    out = (loss,) + ((planes,) if want_planes else ()) + ((ranks,) if want_ranks else ())
+    return out if len(out) > 1 else loss
+
+
 def roi(image, logit):
     B, C, H, W = image.shape
     out = torch.empty_like(image)
@@ -1071,9 +1101,9 @@ def adam_step_dev(p, g, m, v, lr_dev, beta1, beta2, eps, step, step_dev=None, ho
 
 def loss_log_code(k):
     """wtpse_loss_log's check_n for "NaN-test the first k scalars" (the table of include/wtpse_hip.h)."""
-    if not 0 <= k <= 5:
-        raise ValueError("loss_log: the NaN test covers the first 0 to 5 scalars of a call, got %d" % k)
-    return (0, 1, 17, 3, 19, 51)[k]
+    if not 0 <= k <= 6:
+        raise ValueError("loss_log: the NaN test covers the first 0 to 6 scalars of a call, got %d" % k)
+    return (0, 1, 17, 3, 19, 51, 115)[k]
 
 
 def loss_log(scalars, acc, offset, check_n, flag, step_dev):

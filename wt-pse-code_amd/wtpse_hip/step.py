@@ -34,6 +34,7 @@ import torch
 
 from . import ops
 from .boundary import BoundaryLoss
+from .lovasz import LovaszLoss
 from .overlap import OverlapLoss
 from .terms import LossTerm
 
@@ -49,10 +50,15 @@ def _issue_overlap(term, out, target, mask, dx):
     return ops.overlap_loss(out, target.contiguous(), term.dev, term.schedule, mask=mask, dx=dx)
 
 
+def _issue_lovasz(term, out, target, mask, dx):
+    return ops.lovasz_loss(out, target.contiguous(), term.dev, mask=mask, dx=dx)
+
+
 # The extra terms of calls A and C, in the order they are issued and named: (constructor keyword = stem of the state key, log tag,
 # schedule class, issue function (LossTerm.issue)).  TrainStep and TrainRun take everything about a term from here.
 TERMS = (("boundary", "bd", BoundaryLoss, _issue_boundary),
-         ("overlap", "ov", OverlapLoss, _issue_overlap))
+         ("overlap", "ov", OverlapLoss, _issue_overlap),
+         ("lovasz", "lv", LovaszLoss, _issue_lovasz))
 
 
 def adam_state_to_torch(m, v, t, shapes, lr, betas, eps):
@@ -214,17 +220,20 @@ class TrainStep:
     boundary: a `boundary.BoundaryLoss`, tag `bd`: L_B = mean(sigmoid(logit) * phi) with phi the signed distance map of the call's
     target (wtpse_signed_distance, then ONE wtpse_boundary_loss; the cup call on the ROI-masked logits, as its region loss).
     overlap: an `overlap.OverlapLoss`, tag `ov`: the soft Dice / Tversky / focal Tversky loss per image of the call's logits against its
-    target (ONE wtpse_overlap_loss; the cup call inside the ROI mask; wtpse_hip/overlap.py)."""
+    target (ONE wtpse_overlap_loss; the cup call inside the ROI mask; wtpse_hip/overlap.py).
+    lovasz: a `lovasz.LovaszLoss`, tag `lv`: the Lovász hinge loss per image of the call's logits against its target (ONE
+    wtpse_lovasz_loss: a segmented stable sort of every plane on the device; the cup call over the pixels of the ROI mask only;
+    wtpse_hip/lovasz.py)."""
 
     def __init__(self, model_od, shape_od, model_oc, shape_oc, hparams, lr=5e-4, betas=(0.9, 0.99), dp=None, graph=False, log=None,
-                 freeze_bn=False, average=None, boundary=None, overlap=None):
+                 freeze_bn=False, average=None, boundary=None, overlap=None, lovasz=None):
         self.hp = hparams
         self.freeze_bn = bool(freeze_bn)
         if self.freeze_bn and dp is not None:
             raise ValueError("freeze_bn=True is not supported together with data-parallel training (dp=)")
         if average is not None and dp is not None:
             raise ValueError("average= is not supported together with data-parallel training (dp=)")
-        given = dict(boundary=boundary, overlap=overlap)
+        given = dict(boundary=boundary, overlap=overlap, lovasz=lovasz)
         self.terms = []                 # the terms that are on, in TERMS' order
         for key, tag, _, issue in TERMS:
             if given[key] is not None:
@@ -346,12 +355,12 @@ class TrainStep:
         return {tag + "_" + call: v for tag, v in r.items()}
 
     @staticmethod
-    def log_names(hparams, boundary=False, overlap=False):
+    def log_names(hparams, boundary=False, overlap=False, lovasz=False):
         """The loss names in the order a LossLog for this step holds them: the keys of step()'s result, call by call (A-D).
-        boundary, overlap: with the term's `bd_*` / `ov_*`; the terms that are on follow the other names of their call (A / C) in TERMS'
+        boundary, overlap, lovasz: with the term's `bd_*` / `ov_*` / `lv_*`; the terms that are on follow the other names of their call (A / C) in TERMS'
         order, so that the call's one wtpse_loss_log launch covers them."""
         full = bool(hparams['whitening'])
-        given = dict(boundary=boundary, overlap=overlap)
+        given = dict(boundary=boundary, overlap=overlap, lovasz=lovasz)
         tags = (["seg", "ins", "dom"] if full else ["seg"]) + [tag for key, tag, _, _ in TERMS if given[key]]
         shape = {"od": ["kd_od", "ins_shape_od", "ins_ij_od", "ins_ii_od", "dom_shape_od"], "oc": ["kd_oc", "ins_shape_oc", "dom_shape_oc"]}
         names = []
@@ -461,11 +470,13 @@ class TrainStep:
         """The weight as last set (the host value; None when the term is off)."""
         return self._term(key, "weight")
 
-    # the two terms under their public names: the schedule object, the device weight, the weight's setter and getter
+    # the terms under their public names: the schedule object, the device weight, the weight's setter and getter
     boundary = property(lambda self: self._term("boundary", "schedule"))
     overlap = property(lambda self: self._term("overlap", "schedule"))
     bd_alpha = property(lambda self: self._term("boundary", "dev"))
     ov_w = property(lambda self: self._term("overlap", "dev"))
+    lovasz = property(lambda self: self._term("lovasz", "schedule"))
+    lv_w = property(lambda self: self._term("lovasz", "dev"))
 
     def set_boundary_weight(self, a):
         self.set_term_weight("boundary", a)
@@ -478,6 +489,12 @@ class TrainStep:
 
     def get_overlap_weight(self):
         return self.get_term_weight("overlap")
+
+    def set_lovasz_weight(self, w):
+        self.set_term_weight("lovasz", w)
+
+    def get_lovasz_weight(self):
+        return self.get_term_weight("lovasz")
 
     def state_dict(self):
         """What a run needs beside the networks' own state_dict()s to continue where it stopped: per network the optimiser state

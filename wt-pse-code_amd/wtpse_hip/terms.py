@@ -1,5 +1,5 @@
 """Extra terms of the objective of calls A and C (step.py): what every term shares.  `WeightSchedule` is the base of a term's
-schedule class (boundary.BoundaryLoss, overlap.OverlapLoss); `LossTerm` is one term of a TrainStep that is switched on.  Which terms
+schedule class (boundary.BoundaryLoss, overlap.OverlapLoss, lovasz.LovaszLoss); `LossTerm` is one term of a TrainStep that is switched on.  Which terms
 exist, in which order they are issued and named, says the table step.TERMS."""
 import math
 

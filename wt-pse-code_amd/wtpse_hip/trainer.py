@@ -215,16 +215,17 @@ class TrainRun:
     schedule stays readable as the attribute of the keyword's name.
     boundary: a `boundary.BoundaryLoss`; columns bd_od / bd_oc.
     overlap: an `overlap.OverlapLoss` (soft Dice / Tversky); columns ov_od / ov_oc.
+    lovasz: a `lovasz.LovaszLoss` (Lovász hinge); columns lv_od / lv_oc.
     """
 
     swad, swad_every, average = None, 0, None        # averaging is off unless the constructor switches it on
-    boundary = overlap = None                        # so are the terms of step.TERMS
+    boundary = overlap = lovasz = None                      # so are the terms of step.TERMS
 
     def __init__(self, model_od, shape_od, model_oc, shape_oc, hparams, next_batch, iter_per_epoch, max_epoch, lr=(1e-3, 1e-3, 1e-3, 1e-3),
                  stop_epoch=-1, val_batches=None, validator=None, interval_validate=10, lr_schedule=None, out_dir=None, graph="plan",
                  seed=0, checkpoint_every=0, betas=(0.9, 0.99), freeze_bn=False, swad=None, swad_every=0, swad_batches=None, swad_loss=None,
-                 boundary=None, overlap=None):
-        terms = dict(boundary=boundary, overlap=overlap)
+                 boundary=None, overlap=None, lovasz=None):
+        terms = dict(boundary=boundary, overlap=overlap, lovasz=lovasz)
         for key, _, cls, _ in TERMS:
             if isinstance(terms[key], dict):        # a saved config()'s form ({}: off)
                 terms[key] = cls(**terms[key]) if terms[key] else None
