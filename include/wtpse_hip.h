@@ -613,6 +613,26 @@ int wtpse_amix_workspace(int N, int S, int b);
 int wtpse_amplitude_mix(const unsigned char* img, const int* partner, const float* lam, const float* twiddle,
                         unsigned char* out_u8, float* out_f32, float* work, int N, int S, int b, void* stream);
 
+/* ---- image-quality augmentation: focus, contrast, brightness, noise (csrc/quality.hip) -----------------------------------
+ * The optional stage between amplitude mixing (or the augmentations, or the crop) and wtpse_input_finish;
+ * input_pipeline.quality_host is its specification in integers, and the device equals it byte for byte.  img [N][S][S][3] uint8,
+ * 1 <= S <= 512, N <= 65535.  params [N][13] int32 per sample: a (focus, Q8: -256 the blurred picture, 0 untouched, > 0 unsharp
+ * masking; -256 <= a <= 512), c (contrast, Q8, 0 <= c <= 512), beta (brightness shift, Q8 grey levels, |beta| <= 16320), k (noise
+ * scale, 0 <= k <= 181000; 0: no noise), w[0..8] (Gaussian taps, Q12: w[j] >= 0, w[0] + 2 (w[1] + .. + w[8]) = 4096).  Per
+ * pixel and channel, x the input byte, `>>` the arithmetic shift:
+ *   H = sum_j w[|j|] X[y][clamp(x + j)], B = sum_j w[|j|] H[clamp(y + j)][x] (j = -8 .. 8, unsigned 32 bits), b8 = (B + 32768) >> 16,
+ *   x8 = x << 8, s = x8 + ((a (x8 - b8) + 128) >> 8), m8 = (256 sums[n] + n/2) / n with n = 3 S S (64 bits, once per sample),
+ *   t = m8 + ((c (s - m8) + 128) >> 8) + beta, u = t + ((k g + 2048) >> 12) when k > 0, out = clip((u + 128) >> 8, 0, 255);
+ *   g = b0 + b1 + b2 + b3 - 510 of word ch of the Philox4x32-10 block with key `seed` and counter (pos[n] + y S + x, 0, 1): the 1
+ *   keeps these blocks apart from those of wtpse_uniform_f64 and wtpse_randn for any seed.
+ * A sample with a = 0 skips both blur passes; one with a = 0, c = 256, beta = 0, k = 0 is copied.  Integers only: the same bytes
+ * on every run.  out != img; img is not written.  The entry points do not check the ranges of params (ops.image_quality does):
+ * outside them the arithmetic wraps, inside them nothing leaves 32 bits. */
+/* sums [N] uint32 = the sum of the 3 S S bytes of every sample (a memset and one launch; integer adds in any order). */
+int wtpse_quality_sums(const unsigned char* img, unsigned* sums, int N, int S, void* stream);
+int wtpse_quality_apply(const unsigned char* img, const int* params, const unsigned* sums, const unsigned long long* pos,
+                        unsigned long long seed, unsigned char* out, int N, int S, void* stream);
+
 /* ---- validation back half (csrc/postprocess.hip) --------------------------------------------------- */
 /* utils.postprocessing (utils.py:267-329) bit for bit: logit [B][h][w] fp32 -> out [B][h][w] uint8 = the largest 8-connected
  * component of sigmoid(logit) > threshold (ties: the first in raster order), holes (background not 4-connected to the border)

@@ -1475,3 +1475,32 @@ def amplitude_mix(img, partner, lam, b, want_float=False):
     outf = torch.empty(img.shape, dtype=torch.float32, device=dev) if want_float else None
     lib().call("wtpse_amplitude_mix", ptr(img), ptr(dpartner), ptr(dlam), ptr(tw), ptr(out), ptr(outf), ptr(work), N, S, b, stream_ptr())
     return (out, outf) if want_float else out
+
+
+# ----------------------------------------------------------------------------------------------- image quality
+def image_quality(img, params, seed, pos, want_pos=False):
+    """[N,S,S,3] uint8 on the device, params [N,13] integers on the host (a, c, beta, k, w[0..8] per sample:
+    input_pipeline.draw_quality), the noise stream `seed` from position `pos` on -> the batch after focus, contrast, brightness and
+    noise (csrc/quality.hip; input_pipeline.quality_host is the specification, byte for byte); with want_pos also the stream
+    position behind the batch (S * S positions per sample with k > 0).  The input is not written."""
+    from .input_pipeline import QUALITY_MAX_SIZE, check_quality_params, quality_positions
+    import numpy as np
+    _chk_u8(img, "img", 4)
+    N, S = int(img.shape[0]), int(img.shape[1])
+    if img.shape[2] != S or img.shape[3] != 3 or not 1 <= N <= 65535 or not 1 <= S <= QUALITY_MAX_SIZE:
+        raise ValueError("image_quality: img must be [N,S,S,3] with 1 <= N <= 65535 and 1 <= S <= %d (got %s)"
+                         % (QUALITY_MAX_SIZE, tuple(img.shape)))
+    seed, pos = int(seed), int(pos)
+    if not 0 <= seed < 1 << 64 or not 0 <= pos < 1 << 62:
+        raise ValueError("image_quality: seed must lie in 0 .. 2^64 - 1 and pos in 0 .. 2^62 - 1 (got %r, %r)" % (seed, pos))
+    params = check_quality_params(params, N)
+    table, next_pos = quality_positions(params, S, pos)
+    dev = img.device
+    # every table stays referenced until the launches are queued: a temporary's block would be handed to the next allocation
+    dparams = torch.from_numpy(params.astype(np.int32)).to(dev, non_blocking=True)
+    dpos = torch.from_numpy(table.view(np.int64)).to(dev, non_blocking=True)
+    sums = torch.empty(N, dtype=torch.int32, device=dev)
+    out = torch.empty_like(img)
+    lib().call("wtpse_quality_sums", ptr(img), ptr(sums), N, S, stream_ptr())
+    lib().call("wtpse_quality_apply", ptr(img), ptr(dparams), ptr(sums), ptr(dpos), seed, ptr(out), N, S, stream_ptr())
+    return (out, next_pos) if want_pos else out

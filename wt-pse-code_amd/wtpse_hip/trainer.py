@@ -92,12 +92,22 @@ class FundusBatches:
     is added).  A batch is assembled domain-major, so every sample has partners from the other domains next to it; the stage's
     draws (`draw_mix`) come from the numpy generator AFTER all of the batch's other draws: every stream is what it is without the
     stage up to that point.  The stage keeps no state of its own — the generator, which TrainRun's checkpoints carry, is all of it.
-    It needs at least two source domains and a side that is a power of two from 32 to 512 (ValueError here)."""
+    It needs at least two source domains and a side that is a power of two from 32 to 512 (ValueError here).
 
-    def __init__(self, datasets, batch_size, device, size=256, augment=None, pipe=None, style=None):
-        from .input_pipeline import DeviceInputPipeline, _check_mix_size
+    quality: an `input_pipeline.ImageQuality` switches the image-quality stage on (None: off — not one launch, allocation or draw is
+    added): blur or sharpening, contrast, brightness and noise on the uint8 batch, after the other two stages.  Its draws
+    (`draw_quality`) come from the numpy generator AFTER all of the batch's other draws, amplitude mixing included: every stream is
+    what it is without the stage up to that point.  Its noise comes from the device Philox stream `set_seed` sets (blocks of their
+    own) at a running position, which is feed state: `state()` carries it as "quality_pos" when the stage is on, and a state saved
+    without the field loads with position 0."""
+
+    def __init__(self, datasets, batch_size, device, size=256, augment=None, pipe=None, style=None, quality=None):
+        from .input_pipeline import QUALITY_MAX_SIZE, DeviceInputPipeline, _check_mix_size
         self.augment = augment
         self.style = style
+        self.quality = quality
+        if quality is not None and not 1 <= int(size) <= QUALITY_MAX_SIZE:
+            raise ValueError("the image-quality stage takes samples of side 1 .. %d, got %r" % (QUALITY_MAX_SIZE, size))
         self.datasets = list(datasets)
         if style is not None:
             if len(self.datasets) < 2:
@@ -124,9 +134,9 @@ class FundusBatches:
         if self.augment is None:
             images, masks = multi_batch([self.datasets[i] for i in self.order], self.per_domain, np_rng)
             draws = [draw(py_rng, self.size) for _ in images]
-            if self.style is None:
+            if self.style is None and self.quality is None:
                 return self.pipe(images, masks, draws)
-            return self.pipe(images, masks, draws, mix_draws=self._mix_draws(np_rng))
+            return self.pipe(images, masks, draws, **self._stage_draws(np_rng, len(images)))
         images, masks, draws, aug_draws = [], [], [], []
         for i in self.order:
             for _ in range(self.per_domain):
@@ -135,9 +145,19 @@ class FundusBatches:
                 masks += mask
                 draws.append(draw(py_rng, self.size))
                 aug_draws.append(draw_augment(py_rng, np_rng, self.size, self.augment))
-        if self.style is None:
+        if self.style is None and self.quality is None:
             return self.pipe(images, masks, draws, aug_draws)
-        return self.pipe(images, masks, draws, aug_draws, mix_draws=self._mix_draws(np_rng))
+        return self.pipe(images, masks, draws, aug_draws, **self._stage_draws(np_rng, len(images)))
+
+    def _stage_draws(self, np_rng, n):
+        """The draws of the stages behind the augmentations, in the stages' order: amplitude mixing, then image quality."""
+        from .input_pipeline import draw_quality
+        kw = {}
+        if self.style is not None:
+            kw["mix_draws"] = self._mix_draws(np_rng)
+        if self.quality is not None:
+            kw["quality_draws"] = draw_quality(np_rng, n, self.quality)
+        return kw
 
     def _mix_draws(self, np_rng):
         from .input_pipeline import draw_mix
@@ -145,13 +165,17 @@ class FundusBatches:
         return partner, lam, self.style.band(self.size)
 
     def set_seed(self, seed):
-        """The seed of the elastic transform's noise stream (TrainRun calls this with the run seed)."""
+        """The seed of the device noise stream — the elastic transform's fields and the image-quality stage's noise (TrainRun calls
+        this with the run seed)."""
         self.pipe.noise_seed = int(seed)
 
     def state(self):
-        if self.augment is None:
-            return {"order": list(self.order)}
-        return {"order": list(self.order), "noise_pos": int(self.pipe.noise_pos)}
+        state = {"order": list(self.order)}
+        if self.augment is not None:
+            state["noise_pos"] = int(self.pipe.noise_pos)
+        if self.quality is not None:
+            state["quality_pos"] = int(self.pipe.quality_pos)
+        return state
 
     def load_state(self, state):
         order = [int(i) for i in state["order"]]
@@ -159,6 +183,7 @@ class FundusBatches:
             raise ValueError("the saved domain order %s is not a permutation of this feed's %d datasets" % (order, len(self.datasets)))
         self.order = order
         self.pipe.noise_pos = int(state.get("noise_pos", 0))
+        self.pipe.quality_pos = int(state.get("quality_pos", 0))
 
 
 def _py_state_to_lists(state):
