@@ -633,6 +633,34 @@ int wtpse_quality_sums(const unsigned char* img, unsigned* sums, int N, int S, v
 int wtpse_quality_apply(const unsigned char* img, const int* params, const unsigned* sums, const unsigned long long* pos,
                         unsigned long long seed, unsigned char* out, int N, int S, void* stream);
 
+/* ---- CLAHE preprocessing: tile histograms, clipped LUTs, bilinear blend (csrc/clahe.hip) ----------------------------------
+ * Contrast-limited adaptive histogram equalisation of img [N][H][W][3] uint8 in front of the normalisation (wtpse_input_finish /
+ * wtpse_image_finish); input_pipeline.clahe_host is its specification in integers, and the device equals it byte for byte.
+ * 1 <= H, W <= 4096, 1 <= N <= 65535, 1 <= ty <= min(16, H), 1 <= tx <= min(16, W), 0 <= floor <= 255, planes = 1 ("luma": the plane
+ * Y = (77 R + 150 G + 29 B + 128) >> 8) or 3 ("rgb": the channels), 256 <= clip_q8 <= 65536 (256 times the clip limit).
+ *   field : max(R, G, B) >= floor; a pixel outside it is neither counted nor changed.
+ *   tiles : boundaries b_k = (k L) / t (floor) along each axis, k = 0 .. t.
+ *   LUT of a tile and plane, h[256] its histogram over field pixels, n = sum h: the identity when n = 0; else limit = max(1,
+ *     (clip_q8 n) >> 16) (64 bits), excess = sum max(h - limit, 0), h = min(h, limit) + excess / 256, r = excess % 256, and with
+ *     step = 256 / r the bins 0, step, .., (r - 1) step get one more; c = the inclusive prefix sum; lut[v] = min((255 c[v] + n / 2) / n, 255).
+ *   pixel : rows[y] = k0y | wy << 8, cols[x] = k0x | wx << 8 (input_pipeline.clahe_axis_table: the lower tile and the Q8 weight, 0 ..
+ *     256, of the next; cols holds W rounded up to a multiple of 4 entries and is 16-byte aligned), the upper tiles min(k0 + 1,
+ *     t - 1); a, b, c, d = the LUT values of tiles (k0y, k0x), (k0y, k0x + 1), (k0y + 1, k0x), (k0y + 1, k0x + 1) at the plane's value:
+ *     v' = ((256 - wy) ((256 - wx) a + wx b) + wy ((256 - wx) c + wx d) + 32768) >> 16.
+ *     planes = 3: channel c becomes its own v'; planes = 1: every channel becomes clip(channel + (Y' - Y), 0, 255).
+ * Integers only: the same bytes on every run, whatever the order of the histogram's atomic adds. */
+/* hist [N][planes][ty tx][256] uint32 (a memset and one launch; tiles of more than 4096 pixels are split over workgroups). */
+int wtpse_clahe_hist(const unsigned char* img, unsigned* hist, int N, int H, int W, int ty, int tx, int floor, int planes,
+                     void* stream);
+/* hist [count][256] uint32 -> lut [count][256] uint8, count = N planes ty tx; both 16-byte aligned. */
+int wtpse_clahe_lut(const unsigned* hist, unsigned char* lut, int count, int clip_q8, void* stream);
+/* bands [ty + 1]: the first row y whose k0y is k (k0y does not decrease with y and takes every value), bands[ty] = H — a workgroup
+ * stages the LUTs of tile rows k and min(k + 1, ty - 1) in LDS and works on rows of band k only; rows, cols and bands as
+ * input_pipeline.clahe_device_tables builds them (their contents are not checked here).  lut is 4-byte aligned.  out != img; img is
+ * not written. */
+int wtpse_clahe_apply(const unsigned char* img, const unsigned char* lut, const int* rows, const int* cols, const int* bands,
+                      unsigned char* out, int N, int H, int W, int ty, int tx, int floor, int planes, void* stream);
+
 /* ---- validation back half (csrc/postprocess.hip) --------------------------------------------------- */
 /* utils.postprocessing (utils.py:267-329) bit for bit: logit [B][h][w] fp32 -> out [B][h][w] uint8 = the largest 8-connected
  * component of sigmoid(logit) > threshold (ties: the first in raster order), holes (background not 4-connected to the border)

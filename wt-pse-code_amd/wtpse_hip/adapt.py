@@ -25,9 +25,11 @@ host specification (`target_host`, `blend_host`, `coeffs_host`, `divergence_host
 `batch` and `stream` predictions depend on the images that share the call (and, for `stream`, on those before it); a `site` checkpoint
 is an ordinary checkpoint, its predictions depend on the image alone.
 
-    python -m wtpse_hip.adapt --images DIR --checkpoint CK --out OUT [--prior 16] [--batch-size 9]
+    python -m wtpse_hip.adapt --images DIR --checkpoint CK --out OUT [--prior 16] [--batch-size 9] [--clahe checkpoint]
 
-    OUT/adapted_checkpoint.pth.tar   loads wherever checkpoint_<epoch>.pth.tar does (test_run.load_checkpoint); extra entry "site"
+    OUT/adapted_checkpoint.pth.tar   loads wherever checkpoint_<epoch>.pth.tar does (test_run.load_checkpoint); extra entry "site",
+                                     and "clahe" — the CLAHE preprocessing the statistics were fitted under — when CK has one
+                                     (--clahe checkpoint, the default) or --clahe names one
     OUT/shift.csv                    SHIFT_COLUMNS, one row per BatchNorm module of the four networks: KL(N_target || N_source) per
                                      channel, its mean and maximum (images = 0: the layer does not run at prediction time, kept as is)
     OUT/shift.json                   prior, images, source, the mean divergence per network and overall: "how far is this site"
@@ -225,10 +227,11 @@ def _checkpoint_keys():
     return CHECKPOINT_KEYS
 
 
-def site_checkpoint(state_dicts, updates, site):
+def site_checkpoint(state_dicts, updates, site, clahe=None):
     """state_dicts: the four networks' state_dicts in CHECKPOINT_KEYS order; updates: {key: {BatchNorm module name: (mean_b, var_b)}}
     -> the four-key checkpoint dict with every tensor CLONED, `<name>.running_mean / .running_var` replaced by the float32 roundings
-    of the updates, plus "site" = `site`.  The inputs are not modified."""
+    of the updates, plus "site" = `site` and, when `clahe` (a `Clahe.record()`) is not None, "clahe" = a copy of it.  The inputs are
+    not modified."""
     out = {}
     for key, sd in zip(_checkpoint_keys(), state_dicts):
         new = {k: v.detach().clone() for k, v in sd.items()}
@@ -241,6 +244,8 @@ def site_checkpoint(state_dicts, updates, site):
                 new[buf] = val.to(old.device)
         out[key] = new
     out["site"] = site
+    if clahe is not None:
+        out["clahe"] = dict(clahe)
     return out
 
 
@@ -280,9 +285,12 @@ def read_shift(out_dir):
 
 class SiteStatistics:
     """fit(folder or batches) -> the adapted checkpoint dict of the module docstring; `self.state` keeps the pass's BlendState (its
-    slots hold every visited layer's pooled sums and last moments), `self.site` the "site" entry."""
+    slots hold every visited layer's pooled sums and last moments), `self.site` the "site" entry.
+    clahe: the `input_pipeline.Clahe` the source checkpoint was trained under (None: none): the folder's images pass through it on
+    their way in, and the adapted checkpoint carries its record as "clahe" like its source."""
 
-    def __init__(self, model, model_shape, model_oc, model_shape_oc, prior=DEFAULT_PRIOR, batch_size=9, size=256):
+    def __init__(self, model, model_shape, model_oc, model_shape_oc, prior=DEFAULT_PRIOR, batch_size=9, size=256, clahe=None):
+        self.clahe = clahe
         if int(batch_size) < 1:
             raise ValueError("batch_size must be positive")
         self.nets = [model, model_shape, model_oc, model_shape_oc]
@@ -297,7 +305,7 @@ class SiteStatistics:
             yield from source
             return
         device = next(self.nets[0].parameters()).device
-        front = Segmenter(None, None, None, None, out_dir=None, size=self.size).front       # the loader `segment` and `locate` use
+        front = Segmenter(None, None, None, None, out_dir=None, size=self.size, clahe=self.clahe).front   # `segment`'s and `locate`'s loader
         for first in range(0, len(source), self.batch_size):
             yield front([source.load(i) for i in range(first, min(first + self.batch_size, len(source)))], device)
 
@@ -330,7 +338,8 @@ class SiteStatistics:
             layers[key][name] = dict(images=int(n), divergence=[float(d) for d in div])
         self.site = dict(prior=self.prior, images=images, source=source_name, layers=layers)
         torch.cuda.synchronize()
-        return site_checkpoint([n.state_dict() for n in self.nets], updates, self.site)
+        return site_checkpoint([n.state_dict() for n in self.nets], updates, self.site,
+                               None if self.clahe is None else self.clahe.record())
 
 
 # ---- command line -----------------------------------------------------------------------------------------------------------------
@@ -342,6 +351,8 @@ def parser():
     ap.add_argument("--out", required=True)
     ap.add_argument("--prior", type=float, default=DEFAULT_PRIOR, help="N0: how many target images the source statistics are worth")
     ap.add_argument("--batch-size", type=int, default=9)
+    from .programs import add_clahe_argument
+    add_clahe_argument(ap)
     return ap
 
 
@@ -353,7 +364,7 @@ def add_adapt_arguments(ap):
 
 
 def main(argv=None):
-    from .programs import load_networks, require_gpu
+    from .programs import load_networks, require_gpu, resolve_clahe
     from .segment import EXTENSIONS, ImageFolder
     ap = parser()
     args = ap.parse_args(argv)
@@ -363,11 +374,11 @@ def main(argv=None):
     folder = ImageFolder(args.images)
     if len(folder) < 1:
         raise SystemExit("no image (%s) under %s" % (" ".join(EXTENSIONS), args.images))
-    nets, _ = load_networks(args.checkpoint)
-    fit = SiteStatistics(*nets, prior=args.prior, batch_size=args.batch_size)
+    nets, _, record = load_networks(args.checkpoint, want_clahe=True)
+    fit = SiteStatistics(*nets, prior=args.prior, batch_size=args.batch_size, clahe=resolve_clahe(ap, args.clahe, record))
     ckpt = fit.fit(folder, source_name=os.path.basename(args.checkpoint))
     os.makedirs(args.out, exist_ok=True)
-    torch.save({k: ({n: v.cpu() for n, v in d.items()} if k != "site" else d) for k, d in ckpt.items()},
+    torch.save({k: ({n: v.cpu() for n, v in d.items()} if k in _checkpoint_keys() else d) for k, d in ckpt.items()},
                os.path.join(args.out, "adapted_checkpoint.pth.tar"))
     summary = write_shift(args.out, fit.site)
     print(json.dumps(summary, sort_keys=True))

@@ -235,7 +235,7 @@ class Locator:
     [B,1,S,S]` is the disc network (model.predict(model_shape, image)[0]); the caller holds the networks in eval mode."""
 
     def __init__(self, model, model_shape, candidates=3, refine=1, disc_scale=0.13, roi_scale=0.4, roi_side=None, cell="auto",
-                 fov_threshold=24, min_area=0.01, max_area=0.5, batch_size=9, size=256):
+                 fov_threshold=24, min_area=0.01, max_area=0.5, batch_size=9, size=256, clahe=None):
         if int(candidates) < 1 or int(refine) < 0 or int(batch_size) < 1:
             raise ValueError("candidates and batch_size must be positive and refine must not be negative")
         if cell != "auto" and not 2 <= int(cell) <= 256:
@@ -248,7 +248,9 @@ class Locator:
         self.count, self.refine, self.disc_scale, self.roi_scale = int(candidates), int(refine), float(disc_scale), float(roi_scale)
         self.roi_side, self.cell, self.t = (None if roi_side is None else int(roi_side)), (cell if cell == "auto" else int(cell)), int(fov_threshold)
         self.min_area, self.max_area, self.batch_size, self.size = float(min_area), float(max_area), int(batch_size), int(size)
-        self._front = Segmenter(None, None, None, None, out_dir=None, size=size)
+        # (clahe: the candidate crops the disc network verifies are preprocessed as the final crops are; the search for candidates
+        # on the full photograph is not)
+        self._front = Segmenter(None, None, None, None, out_dir=None, size=size, clahe=clahe)
         self.seconds = None                                 # {"cells", "verify", "refine"} when timing is on (tools/bench_locate.py)
 
     def stage1(self, image):
@@ -368,7 +370,8 @@ class WholeImageSegmenter:
     def __init__(self, model, model_shape, model_oc, model_shape_oc, out_dir, full=True, chunk=4, **kw):
         loc = {k: kw.pop(k) for k in self.LOCATOR_KEYS if k in kw}
         self.segmenter = Segmenter(model, model_shape, model_oc, model_shape_oc, out_dir=out_dir, **kw)
-        self.locator = Locator(model, model_shape, batch_size=self.segmenter.batch_size, size=self.segmenter.size, **loc)
+        self.locator = Locator(model, model_shape, batch_size=self.segmenter.batch_size, size=self.segmenter.size,
+                               clahe=self.segmenter.clahe, **loc)
         self.out_dir, self.full, self.chunk, self.roi_rows = out_dir, bool(full), max(1, int(chunk)), []
 
     def _locate_all(self, folder, device):
@@ -458,7 +461,7 @@ def parser():
 
 def main(argv=None):
     from . import segment
-    from .programs import load_networks, require_gpu
+    from .programs import load_networks, require_gpu, resolve_clahe
     ap = parser()
     args = ap.parse_args(argv)
     kw = segment.segmenter_arguments(ap, args)
@@ -471,7 +474,10 @@ def main(argv=None):
     folder = ImageFolder(args.images)
     if len(folder) < 1:
         raise SystemExit("no image (%s) under %s" % (" ".join(segment.EXTENSIONS), args.images))
-    nets, _ = load_networks(args.checkpoint)
+    nets, _, record = load_networks(args.checkpoint, want_clahe=True)
+    clahe = resolve_clahe(ap, args.clahe, record)
+    if clahe is not None:                   # (off: the keywords are what they were)
+        kw["clahe"] = clahe
     try:
         run = WholeImageSegmenter(*nets, out_dir=args.out, full=not args.no_full, candidates=args.candidates, refine=args.refine,
                                   disc_scale=args.disc_scale, roi_scale=args.roi_scale, roi_side=args.roi_side, cell=args.cell,

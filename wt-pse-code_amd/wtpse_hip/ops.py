@@ -1504,3 +1504,43 @@ def image_quality(img, params, seed, pos, want_pos=False):
     lib().call("wtpse_quality_sums", ptr(img), ptr(sums), N, S, stream_ptr())
     lib().call("wtpse_quality_apply", ptr(img), ptr(dparams), ptr(sums), ptr(dpos), seed, ptr(out), N, S, stream_ptr())
     return (out, next_pos) if want_pos else out
+
+
+# ----------------------------------------------------------------------------------------------- CLAHE preprocessing
+_CLAHE_TABLES = {}
+
+
+def clahe_tables(H, W, clahe, device):
+    """The stage's two axis tables on `device` (input_pipeline.clahe_device_tables), kept per (H, W, tiles, device)."""
+    from .input_pipeline import clahe_device_tables
+    key = (int(H), int(W), clahe.tiles, str(device))
+    t = _CLAHE_TABLES.get(key)
+    if t is None:
+        if len(_CLAHE_TABLES) >= 64:
+            _CLAHE_TABLES.clear()
+        t = _CLAHE_TABLES[key] = tuple(torch.from_numpy(a).to(device) for a in clahe_device_tables(H, W, clahe))
+    return t
+
+
+def clahe(img, clahe, want_luts=False):
+    """[N,H,W,3] uint8 on the device and an input_pipeline.Clahe -> the equalised batch, a new tensor (csrc/clahe.hip: tile
+    histograms, clipped LUTs, bilinear blend; input_pipeline.clahe_host is the specification, byte for byte); with want_luts also
+    the tile LUTs [N,P,ty,tx,256] uint8.  The input is not written.  No draws: the same bytes on every call."""
+    from .input_pipeline import CLAHE_MAX_SIDE, Clahe
+    _chk_u8(img, "img", 4)
+    if not isinstance(clahe, Clahe):
+        raise ValueError("clahe: the parameters must be an input_pipeline.Clahe (got %r)" % (clahe,))
+    N, H, W, C = (int(s) for s in img.shape)
+    if C != 3 or not 1 <= N <= 65535 or not (1 <= H <= CLAHE_MAX_SIDE and 1 <= W <= CLAHE_MAX_SIDE):
+        raise ValueError("clahe: img must be [N,H,W,3] with 1 <= N <= 65535 and 1 <= H, W <= %d (got %s)" % (CLAHE_MAX_SIDE, tuple(img.shape)))
+    clahe.check_size(H, W)
+    (ty, tx), P, dev = clahe.tiles, clahe.planes, img.device
+    rows, cols, bands = clahe_tables(H, W, clahe, dev)
+    hist = torch.empty((N, P, ty, tx, 256), dtype=torch.int32, device=dev)
+    luts = torch.empty((N, P, ty, tx, 256), dtype=torch.uint8, device=dev)
+    out = torch.empty_like(img)
+    st = stream_ptr()
+    lib().call("wtpse_clahe_hist", ptr(img), ptr(hist), N, H, W, ty, tx, clahe.floor, P, st)
+    lib().call("wtpse_clahe_lut", ptr(hist), ptr(luts), N * P * ty * tx, clahe.clip_q8, st)
+    lib().call("wtpse_clahe_apply", ptr(img), ptr(luts), ptr(rows), ptr(cols), ptr(bands), ptr(out), N, H, W, ty, tx, clahe.floor, P, st)
+    return (out, luts) if want_luts else out

@@ -44,6 +44,11 @@ over the V views' deterministic predictions with --samples 0, over the V K sampl
 summary.json is the number of maps merged; sample v K + k is sample k of view v).  summary.json gains views, the code list.  The
 image at folder index i draws from position 2 V K S^2 i of the stream; the cost is V passes of both U-Nets.
 
+With --clahe (Segmenter(clahe=Clahe(...)); `checkpoint`, the default, applies what the checkpoint records as "clahe" and changes
+nothing for a checkpoint without the entry; `off`; or CLIP[:TY,TX[:FLOOR[:MODE]]]) the resized crops pass through the CLAHE
+preprocessing (csrc/clahe.hip; the project's own integer definition, not byte-equal to OpenCV; effect on held-out Dice / HD95
+unmeasured) before the normalisation: a checkpoint trained under the stage needs it, one trained without must not get it.
+
 With --adapt batch|stream (Segmenter(adapt=..., prior=N0); none, the default, changes nothing) the eval-mode BatchNorm layers run on the
 images' own statistics blended with the checkpoint's (adapt.py): per network batch, or pooled over the run in folder order.  The
 predictions then depend on the images that share the batch (and, for stream, on those before it); --adapt stream refuses --views,
@@ -205,10 +210,19 @@ class BackResult:
 class Segmenter:
     """run(folder) segments every image of an ImageFolder (or of what ImageFolder takes) in batches of `batch_size` consecutive
     images and writes the files of the module docstring; -> the summary, `self.rows` keeps the table.  Eval mode for the duration, the
-    previous modes restored.  front / back are the two halves around validate.predict_pair."""
+    previous modes restored.  front / back are the two halves around validate.predict_pair.
+    clahe: an `input_pipeline.Clahe` puts the CLAHE preprocessing into `front`, after the resize and before the normalisation (None,
+    the default: nothing changes) — for a checkpoint trained under the same Clahe (its "clahe" entry).  Overlays show the network
+    input, hence the equalised picture."""
 
     def __init__(self, model, model_shape, model_oc, model_shape_oc, out_dir, batch_size=9, overlay=True, size=256, samples=0, seed=0,
-                 scale=1.0, morphometry=False, sectors=24, eye=None, views=None, adapt=None, prior=A.DEFAULT_PRIOR):
+                 scale=1.0, morphometry=False, sectors=24, eye=None, views=None, adapt=None, prior=A.DEFAULT_PRIOR, clahe=None):
+        if clahe is not None:
+            from .input_pipeline import Clahe
+            if not isinstance(clahe, Clahe):
+                raise ValueError("clahe must be an input_pipeline.Clahe or None, got %r" % (clahe,))
+            clahe.check_size(int(size), int(size))
+        self.clahe = clahe
         self.morphometry, self.sectors, self.eye = bool(morphometry), M.check_sectors(sectors), M.check_eye(eye)
         self.morph_rows, self.morph_sample_rows = [], []
         if int(batch_size) < 1:
@@ -249,7 +263,7 @@ class Segmenter:
 
     def front(self, images, device="cuda"):
         """images: decoded [h,w,3] uint8 arrays of any sizes -> [B,3,S,S] fp32 on the device, in their order: FundusTree's LANCZOS
-        resize, then FundusTestBatches.host_sample's normalisation, bit for bit.  An image may also be a [h,w,3] uint8 tensor that is
+        resize, then (with clahe) ops.clahe, then FundusTestBatches.host_sample's normalisation, bit for bit.  An image may also be a [h,w,3] uint8 tensor that is
         already on the device (locate.py's crops): it takes the same path without visiting the host."""
         S, dev = self.size, torch.device(device)
         if dev.type != "cuda":
@@ -276,7 +290,10 @@ class Segmenter:
                 small = t
             else:
                 small[torch.tensor(idx, device=dev)] = t
-        return ops.image_finish(small.contiguous())
+        small = small.contiguous()
+        if self.clahe is not None:
+            small = ops.clahe(small, self.clahe)
+        return ops.image_finish(small)
 
     def back(self, image, logits_od, logits_oc, sizes, spread=None):
         """image [B,3,S,S] (the network input) and the two logit maps [B,1,S,S] on the device, sizes = [(h, w)] per image ->
@@ -461,6 +478,8 @@ def add_arguments(ap, images_help=None):
     ap.add_argument("--views", default="none", help="test-time views to merge: none, id, hflip, flips, d4 or a comma list of codes 0..7 "
                                                     "(0 first): uncertainty/ and uncertainty.csv over the views")
     A.add_adapt_arguments(ap)
+    from .programs import add_clahe_argument
+    add_clahe_argument(ap)
 
 
 def segmenter_arguments(ap, args):
@@ -482,7 +501,7 @@ def segmenter_arguments(ap, args):
 
 def main(argv=None):
     import argparse
-    from .programs import load_networks, require_gpu
+    from .programs import load_networks, require_gpu, resolve_clahe
     ap = argparse.ArgumentParser(prog="python -m wtpse_hip.segment", description=__doc__.split("\n\n")[0])
     add_arguments(ap)
     args = ap.parse_args(argv)
@@ -491,7 +510,10 @@ def main(argv=None):
     folder = ImageFolder(args.images)
     if len(folder) < 1:
         raise SystemExit("no image (%s) under %s" % (" ".join(EXTENSIONS), args.images))
-    nets, _ = load_networks(args.checkpoint)
+    nets, _, record = load_networks(args.checkpoint, want_clahe=True)
+    clahe = resolve_clahe(ap, args.clahe, record)
+    if clahe is not None:                   # (off: the keywords are what they were)
+        kw["clahe"] = clahe
     summary = Segmenter(*nets, out_dir=args.out, **kw).run(folder)
     torch.cuda.synchronize()
     print(json.dumps(summary, sort_keys=True))

@@ -99,13 +99,23 @@ class FundusBatches:
     (`draw_quality`) come from the numpy generator AFTER all of the batch's other draws, amplitude mixing included: every stream is
     what it is without the stage up to that point.  Its noise comes from the device Philox stream `set_seed` sets (blocks of their
     own) at a running position, which is feed state: `state()` carries it as "quality_pos" when the stage is on, and a state saved
-    without the field loads with position 0."""
+    without the field loads with position 0.
 
-    def __init__(self, datasets, batch_size, device, size=256, augment=None, pipe=None, style=None, quality=None):
-        from .input_pipeline import QUALITY_MAX_SIZE, DeviceInputPipeline, _check_mix_size
+    clahe: an `input_pipeline.Clahe` switches the CLAHE preprocessing on (None: off — not one launch or allocation is added): the
+    uint8 batch is equalised after every other stage and immediately before the normalisation.  It draws nothing and adds no feed
+    state; it is a preprocessing step, so whatever reads the run's checkpoints must apply the same one: TrainRun writes
+    `clahe.record()` into every checkpoint as "clahe" (`clahe_record()` is what it asks the feed for)."""
+
+    def __init__(self, datasets, batch_size, device, size=256, augment=None, pipe=None, style=None, quality=None, clahe=None):
+        from .input_pipeline import QUALITY_MAX_SIZE, Clahe, DeviceInputPipeline, _check_mix_size
         self.augment = augment
         self.style = style
         self.quality = quality
+        if clahe is not None:
+            if not isinstance(clahe, Clahe):
+                raise ValueError("clahe must be an input_pipeline.Clahe or None, got %r" % (clahe,))
+            clahe.check_size(int(size), int(size))
+        self.clahe = clahe
         if quality is not None and not 1 <= int(size) <= QUALITY_MAX_SIZE:
             raise ValueError("the image-quality stage takes samples of side 1 .. %d, got %r" % (QUALITY_MAX_SIZE, size))
         self.datasets = list(datasets)
@@ -134,7 +144,7 @@ class FundusBatches:
         if self.augment is None:
             images, masks = multi_batch([self.datasets[i] for i in self.order], self.per_domain, np_rng)
             draws = [draw(py_rng, self.size) for _ in images]
-            if self.style is None and self.quality is None:
+            if self.style is None and self.quality is None and self.clahe is None:
                 return self.pipe(images, masks, draws)
             return self.pipe(images, masks, draws, **self._stage_draws(np_rng, len(images)))
         images, masks, draws, aug_draws = [], [], [], []
@@ -145,19 +155,26 @@ class FundusBatches:
                 masks += mask
                 draws.append(draw(py_rng, self.size))
                 aug_draws.append(draw_augment(py_rng, np_rng, self.size, self.augment))
-        if self.style is None and self.quality is None:
+        if self.style is None and self.quality is None and self.clahe is None:
             return self.pipe(images, masks, draws, aug_draws)
         return self.pipe(images, masks, draws, aug_draws, **self._stage_draws(np_rng, len(images)))
 
     def _stage_draws(self, np_rng, n):
-        """The draws of the stages behind the augmentations, in the stages' order: amplitude mixing, then image quality."""
+        """The draws of the stages behind the augmentations, in the stages' order: amplitude mixing, then image quality; CLAHE,
+        the last stage, draws nothing and rides along."""
         from .input_pipeline import draw_quality
         kw = {}
         if self.style is not None:
             kw["mix_draws"] = self._mix_draws(np_rng)
         if self.quality is not None:
             kw["quality_draws"] = draw_quality(np_rng, n, self.quality)
+        if self.clahe is not None:
+            kw["clahe"] = self.clahe
         return kw
+
+    def clahe_record(self):
+        """The feed's preprocessing as a checkpoint carries it: `Clahe.record()`, or None without the stage."""
+        return None if self.clahe is None else self.clahe.record()
 
     def _mix_draws(self, np_rng):
         from .input_pipeline import draw_mix
@@ -184,6 +201,16 @@ class FundusBatches:
         self.order = order
         self.pipe.noise_pos = int(state.get("noise_pos", 0))
         self.pipe.quality_pos = int(state.get("quality_pos", 0))
+
+
+def _clahe_record_of(feed):
+    """A feed, or a bound method of one (`ClaheTestBatches(...).triples`) -> (it can tell, its `clahe_record()`).  A plain
+    test_run.FundusTestBatches can tell too: it applies none."""
+    from .test_run import FundusTestBatches
+    owner = getattr(feed, "__self__", feed)
+    if owner is not None and hasattr(owner, "clahe_record"):
+        return True, owner.clahe_record()
+    return isinstance(owner, FundusTestBatches), None
 
 
 def _py_state_to_lists(state):
@@ -241,6 +268,11 @@ class TrainRun:
     boundary: a `boundary.BoundaryLoss`; columns bd_od / bd_oc.
     overlap: an `overlap.OverlapLoss` (soft Dice / Tversky); columns ov_od / ov_oc.
     lovasz: a `lovasz.LovaszLoss` (Lovász hinge); columns lv_od / lv_oc.
+    CLAHE preprocessing: a feed that has `clahe_record()` (`FundusBatches(clahe=...)`) is asked for it once; when it returns a record,
+    every checkpoint the run writes — run_checkpoint, swad_checkpoint and, through `validator.clahe`, the best-Dice checkpoint —
+    carries it as "clahe" (`self.clahe_record`; absent otherwise: the files are what they were).  A `val_batches` whose owner has
+    `clahe_record()` too (`labelled_split.ClaheTestBatches(...).triples`), or is a plain `FundusTestBatches`, which applies none, must
+    agree with the feed: ValueError otherwise.
     """
 
     swad, swad_every, average = None, 0, None        # averaging is off unless the constructor switches it on
@@ -276,6 +308,13 @@ class TrainRun:
         self.py_rng, self.np_rng = random.Random(self.seed), np.random.RandomState(self.seed)
         if hasattr(next_batch, "set_seed"):            # a feed with a device noise stream of its own (FundusBatches with augment=)
             next_batch.set_seed(self.seed)
+        seen, self.clahe_record = _clahe_record_of(next_batch)
+        val_seen, val_record = _clahe_record_of(val_batches)
+        if seen and val_seen and val_record != self.clahe_record:
+            raise ValueError("the training feed and val_batches disagree about the CLAHE preprocessing (%r against %r): the networks "
+                             "would be validated on other pictures than they are trained on" % (self.clahe_record, val_record))
+        if self.clahe_record is not None and validator is not None:
+            validator.clahe = dict(self.clahe_record)
         device = next(model_od.parameters()).device
         self.log = LossLog(device, TrainStep.log_names(hparams, **{key: s is not None for key, s in terms.items()}))
         self.swad, self.swad_every, self.swad_batches, self.swad_loss = swad, int(swad_every) if swad is not None else 0, swad_batches, swad_loss
@@ -433,6 +472,8 @@ class TrainRun:
             d = {key: {name: v.detach().clone() for name, v in n.state_dict().items()}
                  for key, n in zip(CKPT_KEYS, self.nets) if n is not None}
             d["swad"] = info
+            if self.clahe_record is not None:
+                d["clahe"] = dict(self.clahe_record)
         finally:
             for n, sv in zip(nets, saved):
                 object.__setattr__(n, "bn_momentum", sv["momentum"])
@@ -537,6 +578,8 @@ class TrainRun:
                  feed=self.next_batch.state() if hasattr(self.next_batch, "state") else {})
         if self.swad is not None:
             d["swad_state"] = {"average": self.average.state(), "valley": self.swad.state()}
+        if self.clahe_record is not None:
+            d["clahe"] = dict(self.clahe_record)
         return d
 
     def save(self, path):
@@ -565,6 +608,9 @@ class TrainRun:
         """The non-network part of a checkpoint, in place (also into a run whose step is already recorded).  Lines of
         out_dir/train_log.csv for epochs the checkpoint has not seen (a run killed after an epoch's line and before its checkpoint)
         are dropped: the resumed run writes them again."""
+        if d.get("clahe") != self.clahe_record:
+            raise ValueError("the checkpoint was written under the CLAHE preprocessing %r and this run's feed has %r: continue with "
+                             "the same FundusBatches(clahe=...)" % (d.get("clahe"), self.clahe_record))
         self.train_step.load_state_dict(d["train_step"])
         self.epoch, self.iteration = int(d["epoch"]), int(d["iteration"])
         self._set_term_weights()            # the schedules' values for the epoch that runs next (train_epoch() sets them again)

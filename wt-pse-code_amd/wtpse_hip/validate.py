@@ -365,7 +365,11 @@ def best_checkpoint(model, model_shape, model_oc, model_shape_oc):
 class Validator:
     """The per-epoch bookkeeping of Trainer.validate (Trainer.py:258-311): the validation objective ('OD' -> disc Dice, 'OC' -> cup
     Dice, anything else their mean), best_mean_dice / best_epoch, and on a new best the four-state_dict checkpoint (returned; saved
-    with torch.save when `out_dir` is given, as checkpoint_<best_epoch>.pth.tar, with the score line appended to score.txt)."""
+    with torch.save when `out_dir` is given, as checkpoint_<best_epoch>.pth.tar, with the score line appended to score.txt).
+    clahe: the `Clahe.record()` of the preprocessing the networks are trained under (TrainRun sets it from its feed); when it is not
+    None the checkpoint carries it as a fifth entry "clahe", which the reference's filtered load ignores."""
+
+    clahe = None
 
     def __init__(self, objective="OD_OC", out_dir=None, metrics="host"):
         _check_metrics(metrics)
@@ -386,6 +390,8 @@ class Validator:
             return 0, 0, 0, 0, 0, 0, 0
         self.best_epoch, self.best_mean_dice = epoch + 1, mean_dice
         self.checkpoint = best_checkpoint(model, model_shape, model_oc, model_shape_oc)
+        if self.clahe is not None:
+            self.checkpoint["clahe"] = dict(self.clahe)
         if self.out_dir is not None:
             import os
             with open(os.path.join(self.out_dir, "score.txt"), "a") as f:
