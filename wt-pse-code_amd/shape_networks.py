@@ -76,8 +76,9 @@ class ShapeVariationalDist_x(E.HipNet, E.UNetBody):
         """Reference shape_networks.py:483-500.  `inputs` = W[-1] = relu(z2), materialised by the caller."""
         self.ensure_ready(repack=True)
         x = self._as_input(inputs)
-        if getattr(inputs, "wt_amax", None) is not None and x.data_ptr() == inputs.data_ptr():
-            x.wt_amax = inputs.wt_amax          # (the caller's W[-1] from DeepWTP.forward carries the amax table of its data)
+        tab = ops.amax_attached(inputs)
+        if tab is not None and x.data_ptr() == inputs.data_ptr():
+            ops.amax_attach(x, tab)             # (the caller's W[-1] from DeepWTP.forward carries the amax table of its data)
         with ops.fwd_scope(x.device):
             mu, fmap = self._student_mu(E.Act(x), self.training, None, want_fmap=True)
         if not training:

@@ -473,14 +473,14 @@ class Act:
 
     def __init__(self, t, pro=None, relu=False, amax=None):
         self.t, self.pro, self.relu = t, pro, bool(relu)
-        self.amax = amax if amax is not None else (getattr(t, "wt_amax", None) if pro is None else None)
+        self.amax = amax if amax is not None else (ops.amax_attached(t) if pro is None else None)
 
     def dense(self):
         if self.pro is None and not self.relu:
             return self.t
         z = ops.affine_act(self.t, self.pro, self.relu)
         if self.amax is not None:
-            z.wt_amax = self.amax
+            ops.amax_attach(z, self.amax)
         return z
 
 
@@ -605,7 +605,7 @@ def _dgrad(layer, dy, split=None, mask_ref=None, below0=None, below1=None):
             tail += (root.gbias(below.conv),)
         d0, d1, stats, coef = ops.dgrad_bnb(dy, wptr, layout, layer.cin, layer.k, below.y, below.ss, below.mean, below.relu, split,
                                             below1 is not None and below0 is None, tail,
-                                            _gamax(dy) if layout == 1 else getattr(dy, "wt_amax", None) if layout == 2 else None)
+                                            _gamax(dy) if layout == 1 else ops.amax_attached(dy) if layout == 2 else None)
         if below0 is not None:
             return PreBN(d0, stats, coef), d1
         return d0, PreBN(d1, stats, coef)
@@ -696,7 +696,7 @@ def _wgrad_kernel(layer, dy, a0, a1, with_bias):
             ops.wgrad_r_supported(layer.cin, layer.cout, 3, c0 if a1 is not None else 16, a0.t.shape[3]) and (not with_bias or small)):
         # (the 16 x 16-channel blocks are HBM-bound: an extra pass over dY to find its scale costs more than x2h gains there — they
         # take the table their dY's producer attached, or run in x3)
-        return "r", (getattr(dy, "wt_amax", None) if small else _gamax(dy), act_amax(a0), act_amax(a1))
+        return "r", (ops.amax_attached(dy) if small else _gamax(dy), act_amax(a0), act_amax(a1))
     if X3 and X3_WGRAD and not with_bias and ops.wgrad_x3_supported(layer.cin, layer.cout, layer.k, c0 if a1 is not None else 8):
         return "x3", (None, None, None)
     return "fp32", (None, None, None)
@@ -784,7 +784,7 @@ def convbn_fwd(conv, bn, a0, a1, relu, training, want_tape=True):
     else:
         stats_wanted = training or blend is not None        # (under blend the conv leaves its partials as in train mode, and no amax)
         y, stats = _conv(conv, a0, a1, False, stats_wanted, want_amax=not stats_wanted)
-        ss, mean, invstd, tab = _bn_coeffs(root, bn, y, stats, training, tab, getattr(y, "wt_amax", None), want_tape, blend)
+        ss, mean, invstd, tab = _bn_coeffs(root, bn, y, stats, training, tab, ops.amax_attached(y), want_tape, blend)
     z = Act(y, ss, relu, tab)
     if not want_tape:
         return z, None
@@ -888,7 +888,7 @@ def upbn_fwd(conv, bn, a0, training, want_tape=True):
     z, _ = _conv(conv, a0, None, False, False, want_amax=not stats_wanted)      # low resolution, pre-BatchNorm
     # (bilinear interpolation is a convex combination: the upsampled map is bounded by the amax of the low-resolution one)
     y, stats = ops.upsample2x_fwd_stats(z) if stats_wanted else (ops.upsample2x_fwd(z), None)
-    ss, mean, invstd, tab = _bn_coeffs(root, bn, y, stats, training, None, getattr(z, "wt_amax", None), want_tape, blend)
+    ss, mean, invstd, tab = _bn_coeffs(root, bn, y, stats, training, None, ops.amax_attached(z), want_tape, blend)
     out = Act(y, ss, True, tab)
     if not want_tape:
         return out, None

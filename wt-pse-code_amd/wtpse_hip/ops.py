@@ -71,7 +71,7 @@ def _conv_launch(name, layout, in_amax, in0, in1, wpacked_ptr, bias, cout, ksize
     lib().call(name, ptr(in0), C0, ptr(in1), C1, wpacked_ptr, ptr(bias), ptr(pro0), ptr(pro1), int(pro_relu), ptr(out0),
                ptr(out1), csplit, ptr(stats), B, H, W, cout, ksize, int(relu_out), ptr(mask_ref), *in_amax, ptr(out_amax), stream_ptr())
     if out_amax is not None:
-        out0.wt_amax = out_amax
+        amax_attach(out0, out_amax)
     return out0, out1, stats
 
 
@@ -95,7 +95,7 @@ def conv_fwd_gram(in0, wpacked_ptr, bias, pro0=None, pro_relu=0, relu_out=False,
     L.call("wtpse_conv_fwd_gram", ptr(in0), C0, wpacked_ptr, ptr(bias), ptr(pro0), int(pro_relu), ptr(out), ptr(partial), B, H, W,
            16, int(relu_out), ptr(out_amax), stream_ptr())
     if out_amax is not None:
-        out.wt_amax = out_amax
+        amax_attach(out, out_amax)
     return out, (partial, nblk // B)
 
 
@@ -124,9 +124,9 @@ def conv16_x3(in0, wx16_ptr, bias, cout, pro0=None, pro_relu=0, relu_out=False, 
         assert mask_ref.shape == out.shape
     L.call("wtpse_conv16_x3", ptr(in0), C0, wx16_ptr, ptr(bias), ptr(pro0), int(pro_relu), ptr(out), ptr(stats), ptr(gram),
            ptr(mask_ref), ptr(bn_ss), ptr(bn_mean), int(bool(bn_relu)), B, H, W, cout, int(relu_out), int(bool(grad_in)),
-           ptr(getattr(in0, "wt_amax", None)) if grad_in else ptr(in_amax), ptr(out_amax), stream_ptr())
+           ptr(amax_attached(in0)) if grad_in else ptr(in_amax), ptr(out_amax), stream_ptr())
     if out_amax is not None:
-        out.wt_amax = out_amax
+        amax_attach(out, out_amax)
     return out, stats, ((gram, nblk // B) if want_gram else None)
 
 
@@ -239,15 +239,41 @@ def act_bound(ss, raw_amax):
     return tab
 
 
+def _version(t):
+    try:
+        return t._version
+    except RuntimeError:            # a tensor made under torch.inference_mode() tracks no version: the table stays with the object
+        return -1
+
+
+def amax_attach(t, tab):
+    """Attach the amax table `tab` to the tensor t, for the contents t has (or is about to be given by the launch that fills tab):
+    the table is valid for as long as t is not written again.  In-place writes through torch move `t._version`, which is kept next
+    to the table; the library's own in-place launches (raw pointers: no version) say so with _amax_stale."""
+    t.wt_amax = tab
+    if tab is not None:
+        t.wt_amax_version = _version(t)
+
+
+def amax_attached(t):
+    """The amax table attached to t if it still describes t's contents, else None: a caller who wrote into t in place since
+    (x.copy_(batch), dz.mul_(s)) gets a fresh look at the data instead of the scale of the contents before."""
+    tab = getattr(t, "wt_amax", None)
+    if tab is not None and getattr(t, "wt_amax_version", None) != _version(t):
+        t.wt_amax = tab = None
+    return tab
+
+
 def amax_of(t):
     """The amax table (int32 tensor [AMAX_WORDS]) of the tensor t as stored: the scale source of an operand of the x2h kernels.
     Producers that fill it as they write t (bn_bwd_*, upsample2x_bwd*; the convolutions' epilogues for un-normalised forward maps) attach
-    it to their result as `t.wt_amax`; anything else pays one extra pass here (and keeps the table on the tensor for its other consumers)."""
-    tab = getattr(t, "wt_amax", None)
+    it to their result (amax_attach); anything else pays one extra pass here (and keeps the table on the tensor for its other
+    consumers, until the tensor is written again: amax_attached)."""
+    tab = amax_attached(t)
     if tab is None:
         tab = torch.empty(AMAX_WORDS, dtype=torch.int32, device=t.device)
         lib().call("wtpse_amax", ptr(t), t.numel(), ptr(tab), stream_ptr())
-        t.wt_amax = tab
+        amax_attach(t, tab)
     return tab
 
 
@@ -510,7 +536,7 @@ def affine_act(y, ss, relu):
 def _dy_like(t):
     """The dy of a BatchNorm backward: shaped like t, with the amax table its x2h consumers read (filled by the launch)."""
     dy = torch.empty_like(t)
-    dy.wt_amax = _amax_table(t.device)
+    amax_attach(dy, _amax_table(t.device))
     return dy
 
 
@@ -720,7 +746,7 @@ def upsample2x_bwd(dout):
     _chk(dout, "dout")
     B, C, Ho, Wo = dout.shape
     dx = torch.empty((B, C, Ho // 2, Wo // 2), dtype=torch.float32, device=dout.device)
-    dx.wt_amax = _amax_table(dout.device)
+    amax_attach(dx, _amax_table(dout.device))
     lib().call("wtpse_upsample2x_bwd", ptr(dout), ptr(dx), 0, B, C, Ho // 2, Wo // 2, ptr(dx.wt_amax), stream_ptr())
     return dx
 
@@ -731,7 +757,7 @@ def upsample2x_bwd_bn(g, bn_y, coef):
     B, C, Ho, Wo = g.shape
     assert bn_y.shape == g.shape and coef.shape == (C, 3) and Wo % 8 == 0, (g.shape, bn_y.shape, coef.shape)
     dx = torch.empty((B, C, Ho // 2, Wo // 2), dtype=torch.float32, device=g.device)
-    dx.wt_amax = _amax_table(g.device)
+    amax_attach(dx, _amax_table(g.device))
     lib().call("wtpse_upsample2x_bwd_bn", ptr(g), ptr(bn_y), ptr(coef), ptr(dx), B, C, Ho // 2, Wo // 2, ptr(dx.wt_amax), stream_ptr())
     return dx
 
@@ -768,6 +794,7 @@ def axpy(dst, src, alpha=1.0):
 
 
 def zero_(t):
+    _amax_stale(t)
     lib().call("wtpse_zero", ptr(t), t.numel() * t.element_size(), stream_ptr())
     return t
 
@@ -807,6 +834,7 @@ def head_bwd(dy, x, pro, relu, h1, h2, w1, w2, w3, dparams, accumulate=False, b1
     L = lib()
     ns = 1024 + 32 + 256 + 8 + 9 * nc
     assert dparams.numel() == ns and dparams.is_contiguous()
+    _amax_stale(dparams)
     slab = workspace("head_slab", L.query("wtpse_head_slabs", B, H * W) * ns, x.device)
     dx = torch.empty_like(x)
     L.call("wtpse_head_bwd", ptr(dy), ptr(x), ptr(pro), int(bool(relu)), ptr(h1), ptr(h2), ptr(w1), ptr(b1), ptr(w2), ptr(w3), nc,
@@ -860,6 +888,7 @@ def reparam_student(mu, logvar, eps, flag):
 
 
 def nan_scrub_(x, flag):
+    _amax_stale(x)
     lib().call("wtpse_nan_scrub", ptr(x), x.numel(), flag.data_ptr(), stream_ptr())
     return x
 
@@ -915,6 +944,8 @@ def shape_samples_mask_(ref, mean, std, votes, logits=None):
     K = 1 if logits is None else logits.shape[1]
     if not (ref.numel() == mean.numel() == std.numel() == votes.numel() and votes.dtype == torch.uint8 and votes.is_contiguous()):
         raise ValueError("shape_samples_mask_: ref, mean, std and votes (uint8) must be [B,1,H,W] of one size")
+    for t in (mean, std, logits):
+        _amax_stale(t)
     lib().call("wtpse_shape_samples_mask", ptr(ref), ptr(mean), ptr(std), ptr(votes), ptr(logits), K, B, H * W, stream_ptr())
 
 
@@ -1088,6 +1119,7 @@ def roi(image, logit):
 
 def adam_step(p, g, m, v, lr, beta1, beta2, eps, step, step_dev=None):
     """Step number t = step + *step_dev (step_dev: device int32 count of completed steps, or None)."""
+    _amax_stale(p)
     lib().call("wtpse_adam", ptr(p), ptr(g), ptr(m), ptr(v), p.numel(), float(lr), float(beta1), float(beta2), float(eps),
                int(step), ptr(step_dev), stream_ptr())
 
@@ -1095,6 +1127,7 @@ def adam_step(p, g, m, v, lr, beta1, beta2, eps, step, step_dev=None):
 def adam_step_dev(p, g, m, v, lr_dev, beta1, beta2, eps, step, step_dev=None, hold=None):
     """adam_step with the learning rate in device memory (lr_dev: one fp32) and an optional hold flag (device int32: non-zero =
     the launch changes nothing)."""
+    _amax_stale(p)
     lib().call("wtpse_adam_dev", ptr(p), ptr(g), ptr(m), ptr(v), p.numel(), ptr(lr_dev), float(beta1), float(beta2), float(eps),
                int(step), ptr(step_dev), ptr(hold), stream_ptr())
 
@@ -1138,6 +1171,7 @@ def avg_merge(acc, seg, n_acc, n_seg):
     _chk(acc, "acc"); _chk(seg, "seg")
     if acc.numel() != seg.numel():
         raise ValueError("avg_merge: %d elements against %d" % (acc.numel(), seg.numel()))
+    _amax_stale(acc)
     lib().call("wtpse_avg_merge", ptr(acc), ptr(seg), acc.numel(), int(n_acc), int(n_seg), stream_ptr())
     return acc
 
