@@ -421,6 +421,14 @@ int wtpse_adam(float* p, const float* g, float* m, float* v, long long n, double
  * their bits (the NaN flag of wtpse_loss_log: a poisoned loss is not applied to the weights). */
 int wtpse_adam_dev(float* p, const float* g, float* m, float* v, long long n, const float* lr_dev, double beta1, double beta2,
                    double eps, int step, const int* step_dev, const int* hold, void* stream);
+/* wtpse_adam_dev over an index list: p and g are a network's flat buffers, idx a device int32 [n_idx] of DISTINCT element
+ * positions in them (0 <= idx[k] < the buffers' length: the caller's duty, nothing is checked on the device), m and v COMPACT,
+ * [n_idx]: element k of them belongs to p[idx[k]].  One thread per index; the arithmetic is wtpse_adam_dev's, statement for
+ * statement, so p[idx[k]], m[k], v[k] come out bit-identical to a dense wtpse_adam_dev on the same operands.  Elements of p
+ * outside idx are never written; *hold != 0: nothing is.  (Test-time entropy minimisation steps the BatchNorm affines alone:
+ * wtpse_hip/tent.py.) */
+int wtpse_adam_index(float* p, const float* g, float* m, float* v, const int* idx, int n_idx, const float* lr_dev, double beta1,
+                     double beta2, double eps, int step, const int* step_dev, const int* hold, void* stream);
 /* Device-side loss log (Trainer.py:788-800, 828-832, 874-885, 917-919): one single-wave launch per update() call of a step.
  * s0..s5: device fp32 scalars (trailing ones may be NULL); for every non-NULL sj: acc[j] += (double)*sj — the reference's
  * `running += loss.item()`, so a double accumulator fed in iteration order holds its running sums bit for bit.
@@ -473,6 +481,23 @@ int wtpse_boundary_loss(const float* x, const float* mask, const float* phi, con
 int wtpse_overlap_loss_ws(int B, int hw);
 int wtpse_overlap_loss(const float* x, const float* mask, const float* t, const float* w_dev, int B, int hw, float fp, float fn,
                        float focal, float smooth, void* ws, float* plane_loss, float* loss, float* dx, void* stream);
+
+/* ---- prediction entropy per image and its gradient (csrc/entropy.hip; specification: wtpse_hip/tent.py) ----
+ * x, mask (NULL: m = 1), dx: [B][hw] fp32, one plane per image.  Per pixel z = x m, e = exp(-|z|) (fp64):
+ *     h(z) = log1p(e) + |z| e / (1 + e)   (the binary entropy of sigmoid(z), in nats),   h'(z) = -z e / (1 + e)^2;
+ * per plane M_b = sum m, H_b = (sum m h) / M_b (H_b = 0 where M_b = 0), c_b = [M_b > 0 and H_b < margin] (a NaN plane fails the
+ * test), w_b = exp(margin - H_b) when reweight != 0 and margin is finite, else 1 (a constant: no gradient through it).
+ *     *loss = (1 / B) sum_b c_b w_b H_b   — the mean over ALL B planes, folded in plane order in fp64, rounded once;
+ *     dx_i  = (c_b w_b / (B M_b)) m_i^2 h'(z_i)   — WRITTEN (not added), fp64 rounded once; every element of dx is written and an
+ *             unselected plane's are +0.0.  dx may be NULL (value only).
+ * planes[b] = H_b (fp32 [B]) and selected[b] = c_b (int32 [B]); either may be NULL.  margin > 0 in nats, +inf allowed (plain TENT;
+ * EATA's filter for two classes: 0.4 ln 2).  ws: wtpse_entropy_loss_ws(B, hw) BYTES, 8-byte aligned (-1: refused shape; 1 <= B <
+ * 65536, 1 <= hw <= 2^30, B hw < 2^31).  Three launches: fp64 partial sums per workgroup (the number of workgroups per plane
+ * depends on hw alone), the per-plane fold + gradient, the fold over the planes.  Fixed order of additions, no atomics: results do
+ * not depend on scheduling, nor on a plane's place in the batch, its neighbours or its alignment. */
+int wtpse_entropy_loss_ws(int B, int hw);
+int wtpse_entropy_loss(const float* x, const float* mask, int B, int hw, double margin, int reweight, void* ws, float* planes,
+                       int* selected, float* loss, float* dx, void* stream);
 
 /* ---- Lovász hinge loss per image: a segmented stable sort on the device (csrc/lovasz.hip; specification: wtpse_hip/lovasz.py) ----
  * x, t, mask (NULL: every pixel kept), dx: [B][hw] fp32, one plane per image.  A pixel is kept iff mask == NULL or m_i != 0 (an

@@ -178,6 +178,68 @@ class WT_PSE(E.HipNet, E.UNetBody):
             out, _ = E._conv(self.outc[0], self._outc_input(fuse, z))
             return out, pre
 
+    def _forward_predict(self, learn_x_network, inputs_all, want_tape):
+        """predict() with a tape for `_backward_predict` -> ((logits, pre), tape or None): the same launches in the same order, so
+        (logits, pre) are predict()'s bit for bit with or without the tape.  The student's latent z is a constant of the tape:
+        `learn_x_network` runs without one, exactly as in predict().  In train mode the BatchNorm layers run on the batch's statistics
+        (and advance their running buffers as any train-mode forward does), in eval mode on the running ones; a `bn_blend` state
+        together with a tape is refused (nn._blend_state)."""
+        self.ensure_ready(repack=True)
+        if self.two_step:
+            inputs, wt_in = self._as_input(inputs_all[0]), self._as_input(inputs_all[1])
+        else:
+            inputs = wt_in = self._as_input(inputs_all)
+        training = self.training
+        t = E.Tape() if want_tape else None
+        with ops.fwd_scope(inputs.device):           # (its tables are kept alive by the activations on the tape)
+            emb = self._embedding(inputs, training, t)
+            if not self.hparams['shape_prior']:
+                out, _ = E._conv(self.outc[0], emb)
+                if want_tape:
+                    t.shape_prior, t.emb = False, emb
+                return (out, None), t
+            learn_x_network.ensure_ready(repack=True)
+            w = E.deepwt_fwd(learn_x_network.wt_model, wt_in, want_tape=False)
+            z = learn_x_network._student_mu(E.Act(w.z2, None, True), learn_x_network.training, None)
+            coef = float(self.hparams['shape_attention_coeffient'])
+            att, pre, _, fuse = ops.attn_fuse_fwd(z, self.attention_layer.layer1.weight.data_ptr(), emb, coef, want_tape, True, False)
+            fuse_in = self._outc_input(fuse, z)
+            out, _ = E._conv(self.outc[0], fuse_in)
+            if want_tape:
+                t.shape_prior, t.emb, t.z, t.att, t.fuse, t.coef = True, emb, z, att, fuse_in, coef
+            return (out, pre), t
+
+    def _backward_predict(self, t, d_out, affine_only=False):
+        """Backward of `_forward_predict`: d_out is the gradient wrt the logits; the parameter gradients of the segmentation network
+        land in the flat gradient buffer (nothing flows into the student: z is a constant, the cat_shape slice of the outc data
+        gradient is dropped).  affine_only: no weight-gradient launch is issued and no side stream forked — the conv-weight ranges
+        of the gradient buffer are not written; the launches whose tails write dgamma / dbeta (and a frozen-mode conv-bias gradient)
+        are the same, and the fused head backward and the attention backward keep writing their own (unread) parameter gradients."""
+        object.__setattr__(self, "_affine_only", bool(affine_only))
+        try:
+            self.begin_backward()
+            d_out = d_out.contiguous()
+            outc = self.outc[0]
+            if not t.shape_prior:
+                E._wgrad(outc, d_out, t.emb)
+                demb, _ = E._dgrad(outc, d_out)
+            else:
+                E._wgrad(outc, d_out, t.fuse)
+                dfuse, _ = E._dgrad(outc, d_out)
+                if self.cat_shape:          # the last channel is the gradient wrt the student's z: not propagated
+                    dfuse = dfuse[:, :self.feature_dim].contiguous()
+                al = self.attention_layer.layer1
+                d_wb = self.gview(al.weight)
+                self.gview(al.bias)
+                demb, _ = ops.attn_fuse_bwd(dfuse, t.z, t.emb, t.att, al.weight.data_ptr(), t.coef, d_wb.data_ptr(), False)
+            dfeat = E.head_bwd(self.mu, t.mu, demb, (0, 2))
+            self.grads_ready(self.mu, self.attention_layer)
+            dx1 = E.unet_bwd(self, t.unet, dfeat, decoder_done=lambda: self.grads_ready(self.up1, self.up4), below_x1=t.inc.c3)
+            E.convd_bwd(self.inc, t.inc, dx1, need_dx=False)
+            self.end_backward()
+        finally:
+            object.__setattr__(self, "_affine_only", False)
+
     def predict_samples(self, learn_x_network, inputs_all, n_samples, seed=0, offset=0, scale=1.0, noise=None, want_logits=False,
                         image_stride=None):
         """predict() plus n_samples draws of the student's latent, z_k = mu + scale * exp(logvar / 2) * eps_k (the teacher's

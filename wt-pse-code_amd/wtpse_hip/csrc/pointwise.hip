@@ -696,6 +696,48 @@ __global__ __launch_bounds__(256) void adam_k(float* __restrict__ p, const float
   p[i] -= (lr / bc1) * (mi / denom);
 }
 
+// The same step over an index list (wtpse_adam_index): p and g are a network's flat buffers, idx[k] the position of element k in
+// them, m and v COMPACT ([n_idx]).  One thread per index; the prologue and the element-wise expressions are adam_k's, statement
+// for statement, so the two kernels leave the same bits on the same operands.  Elements of p outside idx are never touched.
+__global__ __launch_bounds__(256) void adam_index_k(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                    float* __restrict__ v, const int* __restrict__ idx, int n, float b1, float b2,
+                                                    float eps, float bc1, float bc2_sqrt, int step, const int* __restrict__ step_dev,
+                                                    double b1d, double b2d, const float* __restrict__ lr_dev,
+                                                    const int* __restrict__ hold) {
+  float lr;
+  {
+    __shared__ float bc[3];
+    __shared__ int held;
+    if (threadIdx.x == 0) {
+      if (step_dev) {
+        const double t = (double)(step + *step_dev);
+        bc[0] = (float)(1.0 - pow(b1d, t));
+        bc[1] = (float)sqrt(1.0 - pow(b2d, t));
+      } else {
+        bc[0] = bc1;
+        bc[1] = bc2_sqrt;
+      }
+      bc[2] = *lr_dev;
+      held = hold ? *hold : 0;
+    }
+    __syncthreads();
+    if (held) return;
+    bc1 = bc[0];
+    bc2_sqrt = bc[1];
+    lr = bc[2];
+  }
+  int k = (int)blockIdx.x * 256 + (int)threadIdx.x;
+  if (k >= n) return;
+  const int i = idx[k];
+  float gi = g[i];
+  float mi = b1 * m[k] + (1.f - b1) * gi;
+  float vi = b2 * v[k] + (1.f - b2) * gi * gi;
+  m[k] = mi;
+  v[k] = vi;
+  float denom = sqrtf(vi) / bc2_sqrt + eps;
+  p[i] -= (lr / bc1) * (mi / denom);
+}
+
 // ------------------------------------------------------------------------------------------------ loss log (Trainer.py:788-800, 874-885)
 // One wave: lane j < 6 folds scalar j into its running sum (the reference's `running_x += loss.item()`: an fp32 value widened to
 // double, added to a double); lane 0 evaluates the reference's NaN test on the first k scalars (0..6), summed left to right in
@@ -1032,6 +1074,16 @@ extern "C" int wtpse_adam_dev(float* p, const float* g, float* m, float* v, long
   float bc2s = (float)sqrt(1.0 - pow(beta2, (double)step));
   hipLaunchKernelGGL(adam_k, GRID1(n), dim3(256), 0, ST, p, g, m, v, n, 0.f, (float)beta1, (float)beta2, (float)eps, bc1, bc2s,
                      step, step_dev, beta1, beta2, lr_dev, hold);
+  return wtpse_status();
+}
+extern "C" int wtpse_adam_index(float* p, const float* g, float* m, float* v, const int* idx, int n_idx, const float* lr_dev,
+                                double beta1, double beta2, double eps, int step, const int* step_dev, const int* hold,
+                                void* stream) {
+  WTPSE_REQUIRE(p && g && m && v && idx && lr_dev && n_idx > 0 && step >= 1);
+  float bc1 = (float)(1.0 - pow(beta1, (double)step));
+  float bc2s = (float)sqrt(1.0 - pow(beta2, (double)step));
+  hipLaunchKernelGGL(adam_index_k, GRID1(n_idx), dim3(256), 0, ST, p, g, m, v, idx, n_idx, (float)beta1, (float)beta2, (float)eps,
+                     bc1, bc2s, step, step_dev, beta1, beta2, lr_dev, hold);
   return wtpse_status();
 }
 extern "C" int wtpse_loss_log(const float* s0, const float* s1, const float* s2, const float* s3, const float* s4, const float* s5,

@@ -183,10 +183,13 @@ class HipNet(nn.Module):
         # for its k-th refitting pass (the cumulative mean of torch.optim.swa_utils.update_bn) and puts it back.
         # bn_blend: None, or an adapt.BlendState — every EVAL-mode BatchNorm of this tree then runs on this call's statistics, pooled
         # and blended with the running ones (adapt.py; _blend_state below).  Eager only; train mode ignores it.
+        # _affine_only: a backward of this tree issues no weight-gradient launch (_wgrad / _wgrad_side return at once): only the
+        # BatchNorm affines' gradients (and what rides in the same launches) are wanted — WT_PSE._backward_predict(affine_only=True),
+        # test-time entropy minimisation (tent.py).  Off everywhere else.
         for name, value in dict(_flat=None, _gflat=None, _gwork=None, _packed=None, _x3=None, _xdesc=None, _x16desc=None, _desc=None,
                                 _packed_version=-1, _touched=[], _noise_queue=[], _noise_seed=0x5eed, _noise_ctr=None, _dp=None,
                                 _flag=None, _packed_valid=False, _attach_grads=True, _defer_allreduce=False, _join=[],
-                                _frozen_bias={}, _frozen_pass=False, bn_momentum=0.1, bn_blend=None).items():
+                                _frozen_bias={}, _frozen_pass=False, bn_momentum=0.1, bn_blend=None, _affine_only=False).items():
             object.__setattr__(self, name, value)
         self._convs = [m for m in self.modules() if isinstance(m, ConvP)]
         for m in self.modules():
@@ -663,6 +666,8 @@ def _wgrad_side(layer, dy, a0, a1=None):
     """_wgrad(..., with_bias=False) on the side stream.  dy must not be written again by the caller (it is a fresh
     BatchNorm-backward result in both callers)."""
     root = layer._root
+    if root._affine_only:
+        return
     if not WGRAD_SIDE_STREAM:
         return _wgrad(layer, dy, a0, a1, with_bias=False)
     a0 = as_act(a0)
@@ -716,6 +721,8 @@ def _wgrad_launch(kernel, tables, layer, dy, a0, a1, with_bias):
 
 
 def _wgrad(layer, dy, a0, a1=None, with_bias=True):
+    if layer._root._affine_only:      # (no launch, no fork: the conv-weight ranges of the gradient buffer are not written)
+        return
     a0 = as_act(a0)
     a1 = as_act(a1) if a1 is not None else None
     kernel, tables = _wgrad_kernel(layer, dy, a0, a1, with_bias)

@@ -1132,6 +1132,49 @@ def adam_step_dev(p, g, m, v, lr_dev, beta1, beta2, eps, step, step_dev=None, ho
                int(step), ptr(step_dev), ptr(hold), stream_ptr())
 
 
+def adam_index(p, g, m, v, idx, lr_dev, beta1, beta2, eps, step, step_dev=None, hold=None):
+    """adam_step_dev on the elements p[idx] of a flat buffer alone (idx: device int32 [n] of distinct positions, checked by whoever
+    built it), with COMPACT moments m, v [n]: bitwise adam_step_dev on those elements, everything else of p untouched."""
+    _chk(p, "p"); _chk(g, "g"); _chk(m, "m"); _chk(v, "v")
+    if not (idx.is_cuda and idx.dtype == torch.int32 and idx.is_contiguous() and idx.dim() == 1 and idx.numel() > 0):
+        raise ValueError("adam_index: idx must be a non-empty contiguous int32 vector in device memory")
+    n = idx.numel()
+    if p.numel() != g.numel() or m.numel() != n or v.numel() != n:
+        raise ValueError("adam_index: p and g must have one length, m and v that of idx (got %d, %d, %d, %d for %d indices)"
+                         % (p.numel(), g.numel(), m.numel(), v.numel(), n))
+    _amax_stale(p)
+    lib().call("wtpse_adam_index", ptr(p), ptr(g), ptr(m), ptr(v), ptr(idx), n, ptr(lr_dev), float(beta1), float(beta2), float(eps),
+               int(step), ptr(step_dev), ptr(hold), stream_ptr())
+
+
+def entropy_loss(x, mask=None, margin=float("inf"), reweight=False, want_planes=False, want_grad=True):
+    """The entropy objective of x [B, ..., H, W], one plane per image: tent.tent_loss_host on x * mask (mask None: the disc form)
+    -> (loss, dx): the 0-dim device fp32 loss and its gradient wrt x, WRITTEN into a fresh tensor (every element; an unselected
+    plane's are +0.0); want_planes: -> (loss, dx, planes [B] fp32, selected [B] int32).  want_grad=False: dx is None, nothing but
+    the value is computed.  margin in nats (inf: every plane with a non-empty mask is selected), reweight: EATA's exp(margin - H_b)."""
+    _chk(x, "x"); _chk(mask, "mask")
+    if x.dim() < 2 or x.numel() == 0:
+        raise ValueError("entropy_loss: logits [B, ..., H, W], got shape %s" % (tuple(x.shape),))
+    n, B = x.numel(), int(x.shape[0])
+    if mask is not None and mask.numel() != n:
+        raise ValueError("entropy_loss: mask has %d elements, x has %d" % (mask.numel(), n))
+    margin = float(margin)
+    if not margin > 0.0:
+        raise ValueError("entropy_loss: margin must be positive (nats; inf: no filter), got %r" % (margin,))
+    L = lib()
+    nbytes = L.query("wtpse_entropy_loss_ws", B, n // B)
+    if nbytes <= 0:
+        raise ValueError("entropy_loss: unsupported size %s" % (tuple(x.shape),))
+    loss = torch.empty((), dtype=torch.float32, device=x.device)
+    dx = torch.empty_like(x) if want_grad else None
+    planes = torch.empty((B,), dtype=torch.float32, device=x.device) if want_planes else None
+    selected = torch.empty((B,), dtype=torch.int32, device=x.device) if want_planes else None
+    ws = workspace("entropy_loss", (nbytes + 3) // 4, x.device)
+    L.call("wtpse_entropy_loss", ptr(x), ptr(mask), B, n // B, margin, int(bool(reweight)), ptr(ws), ptr(planes), ptr(selected),
+           ptr(loss), ptr(dx), stream_ptr())
+    return (loss, dx, planes, selected) if want_planes else (loss, dx)
+
+
 def loss_log_code(k):
     """wtpse_loss_log's check_n for "NaN-test the first k scalars" (the table of include/wtpse_hip.h)."""
     if not 0 <= k <= 6:
