@@ -638,6 +638,44 @@ int wtpse_amix_workspace(int N, int S, int b);
 int wtpse_amplitude_mix(const unsigned char* img, const int* partner, const float* lam, const float* twiddle,
                         unsigned char* out_u8, float* out_f32, float* work, int N, int S, int b, void* stream);
 
+/* ---- random appearance networks: GIN + IPA in fixed point (csrc/appearance.hip) -------------------------------------------
+ * The optional stage between amplitude mixing (or the augmentations, or the crop) and the image-quality stage;
+ * input_pipeline.appearance_host is its specification in integers, and the device equals it byte for byte.  The definition is this
+ * project's own, after Ouyang et al. 2022 (GIN / IPA) and Xu et al. 2021 (RandConv): it is NOT byte-equal to anyone's float code.
+ * img [N][S][S][3] uint8, 1 <= S <= 512, N <= 65535.  params [N][389] int32 per sample: flags (bit 0: selected, else the sample is
+ * copied; bit 1: blend, two nets), alpha_0, alpha_1 (0 .. 256), then per net j = 0, 1 its 193 values: k[4] (1 or 3 per layer), the
+ * weights W_l[co][ci][3][3] of layers l = 0 .. 3 one after the other (channels 3 -> 2 -> 2 -> 2 -> 3: 54 + 36 + 36 + 54 values, Q12,
+ * |W| <= 16384; with k = 1 only the centre tap [1][1] is used, the others are ignored), the biases (2 + 2 + 2 + 3 values, Q8 grey
+ * levels, |bias| <= 2^19).  `>>` is the arithmetic shift, CL = 2^19 - 1, x an input byte:
+ *   m8  = (256 sums[n] + cnt/2) / cnt, cnt = 3 S S (the image-quality stage's pivot);  c0 = (x << 8) - m8, 0 outside the picture
+ *   layer: v = ((sum_{ci,dy,dx} W[co][ci][dy][dx] h[ci][y + dy - 1][x + dx - 1] + 2048) >> 12) + bias[co] (64-bit sum; h = 0 outside
+ *          the picture at EVERY layer); layers 0 .. 2: v < 0 -> (3 v + 128) >> 8; every layer: h' = clip(v, -CL, CL);  y_j = layer 3
+ *   z_j = (alpha_j c0 + (256 - alpha_j) y_j + 128) >> 8
+ *   E_in = sum ((c0 + 8) >> 4)^2, E_j = sum ((z_j + 8) >> 4)^2 over the sample: exact 64-bit integers below 2^53
+ *   R_j = min(rint(sqrt((double)E_in / (double)E_j) * 4096), 2^20) — one fp64 division, square root and multiplication, each correctly
+ *         rounded: the only floating-point operations of the stage;  E_j = 0: R_j = 4096 and z_j := c0
+ *   g_j = clip((R_j z_j + 2048) >> 12, -CL, CL) (64-bit product)
+ *   b   : without the blend flag 256 (net 0 alone; net 1 is not evaluated).  With it, from the control values field [N][G][G] (0 .. 256,
+ *         G = ceil(S / spacing) + 3) through axis [S][5] = (first control index i, four cubic B-spline weights in Q12, >= 0, summing to
+ *         4096; input_pipeline.appearance_axis_table), the same table for rows and columns:
+ *         hx_r = (sum_c wx[c] P[iy + r][ix + c] + 8) >> 4 (r = 0 .. 3),  b = (sum_r wy[r] hx_r + 2^19) >> 20  (0 .. 256)
+ *   out = clip((m8 + ((b g_0 + (256 - b) g_1 + 128) >> 8) + 128) >> 8, 0, 255)
+ * alpha_0 = 256 without the blend flag returns the input.  No atomics on floats: the same bytes on every run.  out != img; img is not
+ * written.  The entry points do not check the ranges of params, field and axis (ops.appearance_nets does): outside them the
+ * arithmetic wraps (every index into field is clamped into the grid), inside them nothing leaves the stated widths — 32 bits
+ * everywhere but the layers' sums, the energies and R_j z_j.  The spacing is at least 4: a tile of 32 x 64 pixels touches at most
+ * 12 x 20 control values. */
+/* 4-byte words of workspace a call needs: 7 N (energies and byte sums) rounded up to 4, plus 6 N S S (z_0 and z_1 as int32); -1 for
+ * a shape the stage refuses or a size beyond 2^31 - 1 words.  Host only. */
+int wtpse_appearance_workspace(int N, int S);
+/* pass 1: the byte sums (wtpse_quality_sums into the workspace), then per tile the nets in LDS -> z_j and the energies.  work:
+ * 16-byte aligned, wtpse_appearance_workspace(N, S) words.  A memset and two launches. */
+int wtpse_appearance_nets(const unsigned char* img, const int* params, void* work, int N, int S, void* stream);
+/* pass 2: R_j, the scaling, the field, the blend, the mean and the clip; samples that are not selected are copied.  work as pass 1
+ * left it; 4 <= G <= 131.  One launch. */
+int wtpse_appearance_finish(const unsigned char* img, const int* params, const int* field, const int* axis, const void* work,
+                            unsigned char* out, int N, int S, int G, void* stream);
+
 /* ---- image-quality augmentation: focus, contrast, brightness, noise (csrc/quality.hip) -----------------------------------
  * The optional stage between amplitude mixing (or the augmentations, or the crop) and wtpse_input_finish;
  * input_pipeline.quality_host is its specification in integers, and the device equals it byte for byte.  img [N][S][S][3] uint8,

@@ -1554,6 +1554,52 @@ def amplitude_mix(img, partner, lam, b, want_float=False):
     return (out, outf) if want_float else out
 
 
+# ----------------------------------------------------------------------------------------------- random appearance networks
+_APPEARANCE_TABLES = {}
+
+
+def appearance_axis(S, spacing, device):
+    """The stage's axis table [S,5] int32 on `device` (input_pipeline.appearance_axis_table), kept per (S, spacing, device)."""
+    from .input_pipeline import appearance_axis_table
+    import numpy as np
+    key = (int(S), int(spacing), str(device))
+    t = _APPEARANCE_TABLES.get(key)
+    if t is None:
+        if len(_APPEARANCE_TABLES) >= 64:
+            _APPEARANCE_TABLES.clear()
+        t = _APPEARANCE_TABLES[key] = torch.from_numpy(appearance_axis_table(S, spacing).astype(np.int32)).to(device)
+    return t
+
+
+def appearance_nets(img, params, field, spacing):
+    """[N,S,S,3] uint8 on the device, (params [N,389], field [N,G,G]) integers on the host (input_pipeline.draw_appearance) and the
+    field's spacing -> the batch after the random appearance networks, a new tensor (csrc/appearance.hip: the nets tile by tile in
+    LDS, then scaling and blend; input_pipeline.appearance_host is the specification, byte for byte).  The input is not written."""
+    from .input_pipeline import APPEARANCE_MAX_SIZE, appearance_grid, check_appearance_params
+    import numpy as np
+    _chk_u8(img, "img", 4)
+    N, S = int(img.shape[0]), int(img.shape[1])
+    if img.shape[2] != S or img.shape[3] != 3 or not 1 <= N <= 65535 or not 1 <= S <= APPEARANCE_MAX_SIZE:
+        raise ValueError("appearance_nets: img must be [N,S,S,3] with 1 <= N <= 65535 and 1 <= S <= %d (got %s)"
+                         % (APPEARANCE_MAX_SIZE, tuple(img.shape)))
+    params, field = check_appearance_params(params, field, N, S, spacing)
+    words = lib().query("wtpse_appearance_workspace", N, S)
+    if words < 0:
+        raise ValueError("appearance_nets: a [%d,%d,%d,3] batch needs more workspace than one call can take" % (N, S, S))
+    dev = img.device
+    axis = appearance_axis(S, spacing, dev)
+    work = workspace("appearance", words, dev)
+    # every table stays referenced until the launches are queued: a temporary's block would be handed to the next allocation
+    # (C order whatever the caller's strides: a broadcast field keeps its stride order through astype)
+    dparams = torch.from_numpy(np.ascontiguousarray(params, dtype=np.int32)).to(dev, non_blocking=True)
+    dfield = torch.from_numpy(np.ascontiguousarray(field, dtype=np.int32)).to(dev, non_blocking=True)
+    out = torch.empty_like(img)
+    lib().call("wtpse_appearance_nets", ptr(img), ptr(dparams), ptr(work), N, S, stream_ptr())
+    lib().call("wtpse_appearance_finish", ptr(img), ptr(dparams), ptr(dfield), ptr(axis), ptr(work), ptr(out), N, S,
+               appearance_grid(S, spacing), stream_ptr())
+    return out
+
+
 # ----------------------------------------------------------------------------------------------- image quality
 def image_quality(img, params, seed, pos, want_pos=False):
     """[N,S,S,3] uint8 on the device, params [N,13] integers on the host (a, c, beta, k, w[0..8] per sample:
