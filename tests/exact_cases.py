@@ -161,15 +161,53 @@ def wgrad_x3_supported(Cin, Cout, k, C0):
     return k == 3 and Cin >= 32 and Cout >= 32 and Cin % 32 == 0 and Cout % 32 == 0 and C0 % 8 == 0
 
 
-def wgrad_x3_geometry(B, H, W, Cin, Cout):
-    """wgrad_x3_geometry (conv_x3.hip) with the default 16-wide tiles (the 32-wide form needs a once-per-process switch)."""
+def wgrad_x3_geometry(B, H, W, Cin, Cout, tw32=False):
+    """wgrad_x3_geometry (conv_x3.hip): 16-wide tiles by default; tw32: the 32-wide tiles a process started under
+    WTPSE_X3_WGRAD_TW32=1 takes on maps wider than 16 (conv_wgrad_x3_k<3, 5, Q>; read once per process)."""
     q = Cin % 64 == 0 and Cout % 64 == 0
-    return dict(tiling(B, H, W, True, 64 if q else 128), Q=q, blk=64 if q else 32)
+    return dict(tiling(B, H, W, not (tw32 and W > 16), 64 if q else 128), Q=q, blk=64 if q else 32)
 
 
-def wgrad_x3_ksplit(B, H, W, Cin, Cout):
-    g = wgrad_x3_geometry(B, H, W, Cin, Cout)
+def wgrad_x3_ksplit(B, H, W, Cin, Cout, tw32=False):
+    g = wgrad_x3_geometry(B, H, W, Cin, Cout, tw32)
     return max(1, min(512 // ((Cout // g["blk"]) * (Cin // g["blk"])), g["tiles"]))
+
+
+def x3_mt2(B, H, W, CoutP, mt=0):
+    """x3_mt2 (conv_x3.hip): 64-channel blocks where they give 512 workgroups; mt: the once-per-process override WTPSE_X3_MT (1 | 2)."""
+    mt2 = CoutP % 64 == 0 and tiling(B, H, W, W <= 16, 256)["tiles"] * (CoutP // 64) >= 512
+    if mt == 1:
+        mt2 = False
+    if mt == 2 and CoutP % 64 == 0:
+        mt2 = True
+    return mt2
+
+
+def x3_half(B, H, W, CoutP, k, mt2, x3r=1, half_min=256):
+    """x3_half: 64-channel blocks on 128-pixel tiles (3x3, conv_x3r_k allowed); half_min: WTPSE_X3_HALF_MIN (0: WTPSE_X3_HALF=0)."""
+    if k != 3 or half_min == 0 or x3r == 0 or CoutP % 64 != 0 or mt2:
+        return False
+    return tiling(B, H, W, W <= 16, 128)["tiles"] * (CoutP // 64) >= half_min
+
+
+def x3_small_tiles(B, H, W, CoutP, mt2, small_wide=0):
+    """x3_small_tiles: 32-channel blocks on 128-pixel tiles — few workgroups on a 16-wide map, or wtpse_x3_small_wide(1) at W % 32 == 0."""
+    if mt2:
+        return False
+    if W > 16:
+        return bool(small_wide) and W % 32 == 0
+    return tiling(B, H, W, True, 256)["tiles"] * (CoutP // 32) < 512
+
+
+def x3_tiling(B, H, W, Cout, k, small_wide=0, x3r=1, mt=0, half_min=256):
+    """x3_tiling (conv_x3.hip), the switches as parameters: wtpse_x3_small_wide, wtpse_x3r_enable and the once-per-process
+    WTPSE_X3_MT / WTPSE_X3_HALF_MIN.  -> the tiling plus mt (32-channel blocks per workgroup), px, half, small."""
+    CoutP = (Cout + 31) & ~31
+    mt2 = x3_mt2(B, H, W, CoutP, mt)
+    half = x3_half(B, H, W, CoutP, k, mt2, x3r, half_min)
+    small = (not half) and x3_small_tiles(B, H, W, CoutP, mt2, small_wide)
+    px = 128 if (half or small) else 256
+    return dict(tiling(B, H, W, W <= 16, px), mt=2 if (mt2 or half) else 1, px=px, half=int(half), small=int(small))
 
 
 def wgrad_r_supported(Cin, Cout, k, C0, W):
@@ -288,6 +326,15 @@ WGX3_CASES = {
     "concat":    ((2, 32, 32, 64, 5, 9), {"Q": True, "tiles": 4}, (V(1), V(2), V(3, acc=True))),
 }
 
+# conv_wgrad_x3_k<3, 5, Q>: reached only by a process started under WTPSE_X3_WGRAD_TW32=1 (tests/switch_worker.py, job tw32); each case
+# changes its tile count between the 16- and the 32-wide tiles.  name -> (shape, expected subset of wgrad_x3_geometry(tw32=True),
+# tiles on the default 16-wide tiles, variants)
+WGX3_TW32_CASES = {
+    "tw32_q0":  ((2, 32, 0, 32, 5, 40), {"Q": False, "TW": 32, "TH": 4, "tiles_x": 2, "tiles_y": 2, "tiles": 8}, 6, _X3W_V),
+    "tw32_q1":  ((2, 64, 0, 64, 3, 72), {"Q": True, "TW": 32, "TH": 2, "tiles_x": 3, "tiles_y": 2, "tiles": 12}, 10, _X3W_V),
+    "tw32_cat": ((2, 32, 32, 64, 5, 72), {"Q": True, "TW": 32, "tiles": 18}, 20, (V(1), V(2), V(3, acc=True))),
+}
+
 _BLK_V = (V(3), V(None), V(3, bn=True), V(3, amax="dy"), V(None, amax="dyx"))
 _SEG_V = (V(3),)
 # name -> (shape, expected subset of wgrad_r_plan(), variants, classes)
@@ -331,7 +378,7 @@ FOLD4_SLABS = {1: "blk11", 3: "bias_21u", 7: "fold7", 12: "rseg3_24", 32: "fold3
 
 
 def wgrad_cases(fam):
-    return {"fp32": WG32_CASES, "ksplit": WG32_KSPLIT, "x3": WGX3_CASES, "r": WGR_CASES}[fam]
+    return {"fp32": WG32_CASES, "ksplit": WG32_KSPLIT, "x3": WGX3_CASES, "x3tw32": WGX3_TW32_CASES, "r": WGR_CASES}[fam]
 
 
 def wgrad_case(fam, name):
@@ -343,6 +390,8 @@ def wgrad_case(fam, name):
         return c[0], c[1], c[3], "IT"
     if fam == "x3":
         return c[0], 3, c[2], "IT"
+    if fam == "x3tw32":
+        return c[0], 3, c[3], "IT"
     return c[0], 3, c[2], c[3]
 
 
@@ -482,13 +531,32 @@ def _existing_tables():
             "x3half": list(TX.X3_HALF_CASES), "bnb": list(bnb)}
 
 
-TABLES = _existing_tables()
+# 32-channel blocks on 32 x 4 tiles: conv_x3_k<KS, 1, 5, EPI, 1, TERMS> and (wtpse_x3r_enable(2), 3x3) conv_x3r_k<1, 1, 1, 5, ...>,
+# reached only under wtpse_x3_small_wide(1) at W % 32 == 0.  (B, C0, C1, Cout, H, W, k)
+X3_SMALL_WIDE_CASES = [
+    (2, 16, 0, 32, 6, 32, 3),      # one chunk, one tile column, the last tile row 2 of 4 rows
+    (2, 16, 16, 32, 9, 64, 3),     # concat, two tile columns, the last tile row a single row
+    (2, 40, 0, 96, 8, 32, 3),      # ragged chunk (40 -> 48), three output-channel blocks
+    (3, 64, 0, 64, 5, 32, 3),      # 64 outputs that stay on 32-channel blocks (neither mt2 nor half: 6 tiles), grid.y = 2, four chunks
+    (2, 64, 0, 32, 5, 32, 1),      # 1x1, multi-chunk
+    (2, 3, 0, 8, 4, 96, 3),        # 3-channel input, Cout <= 16 on a 32-row tile, three tile columns, exactly one full tile row
+    (1, 32, 0, 32, 1, 32, 3),      # image lower than a tile
+]
+# 64-channel blocks on a 1x1 layer (conv_x3_k<1, 2, ...>), default path: 512 tiles x one block, the step's own instantiation
+# (up2.conv2 at B = 32).  A table of its own: the tolerance tests iterate X3_CASES.
+X3_K1_MT2_CASES = [(32, 16, 0, 64, 64, 64, 1)]
+# the EPI 2 cases (of the bnb table) that take the 32 x 4 tiles under wtpse_x3_small_wide(1)
+BNB_SMALL_WIDE = ((2, 32, 0, False, 32, 16, 32, 3, False, True), (2, 32, 0, False, 32, 6, 32, 3, True, True),
+                  (2, 32, 32, True, 64, 6, 64, 3, True, True))
+MIN_DENSITY_SMALL_WIDE = 0.125  # every call of X3_SMALL_WIDE_CASES with a sparse operand keeps it at least this dense
+
+TABLES = dict(_existing_tables(), x3sw=X3_SMALL_WIDE_CASES, x3k1=X3_K1_MT2_CASES)
 BIG_BATCH = 16          # from this batch size on the density of B is looked for on two images first (the bound does not grow with the batch)
 
 
 def conv_shape(table, case):
     """-> (B, C0, C1, Cout, H, W, k) of a case of one of the existing tables."""
-    if table in ("conv", "x3"):
+    if table in ("conv", "x3", "x3sw", "x3k1"):
         return tuple(case)
     if table == "x16":
         B, Ci, Co, H, W = case

@@ -1,6 +1,8 @@
 """The split-bf16 ("x3") convolution — fp32 operands as three bf16 terms, six bf16 MFMAs per product, fp32 accumulation
 (csrc/conv_x3.hip) — against stock PyTorch fp32/fp64 convolutions on the host, at the SAME tolerance as the fp32-MFMA kernel
 (tests/test_kernels_gpu.py::test_conv_forward), and against the fp64 result with the fp32-MFMA kernel as the yardstick."""
+import contextlib
+
 import pytest
 import torch
 import torch.nn.functional as F
@@ -231,6 +233,8 @@ def test_conv_wgrad_r(case):
     (2, 32, 32, True, 64, 12, 36, 3, True, True),      # ConvU.conv3: gradient of a concat, the BatchNorm'd tensor is the second half
     (2, 16, 16, False, 16, 20, 20, 1, True, False),    # teacher fusion (1x1): the first half
     (2, 128, 0, False, 64, 8, 8, 1, True, True),       # ConvU.conv2 (1x1) on the x3 path
+    (2, 32, 0, False, 32, 6, 32, 3, True, True),       # x3, W % 32 == 0 with ragged rows: 32 x 4 tiles under wtpse_x3_small_wide(1)
+    (2, 32, 32, True, 64, 6, 64, 3, True, True),       # ... split output, 64 outputs that stay on 32-channel blocks
 ])
 def test_dgrad_bnb(case):
     """Data gradient with the BatchNorm-backward reductions in its epilogue + wtpse_bn_bwd_from_stats, against autograd (fp64)
@@ -414,7 +418,9 @@ def test_conv16_x3_bnb(case):
     (0, 3, 3, 0, 16, 24, 40, 3),        # fp32 16-channel path
     (0, 4, 8, 0, 40, 16, 32, 1),        # fp32 ragged channels
     (2, 20, 16, 0, 16, 64, 64, 3),      # 16-channel x3 fragments, 320 tiles -> 5 groups
-    (1, 33, 16, 0, 32, 128, 128, 3),    # 2112 workgroups: beyond WTPSE_TAIL_MAX_WGS the call runs the stand-alone finalize itself
+    (1, 33, 16, 0, 32, 128, 128, 3),    # 2112 workgroups -> 33 ticket groups folded in place: the 8-way unrolled second fold plus a remainder
+                                        # (launches beyond WTPSE_TAIL_MAX_WGS = 8192 workgroups: test_tail_after_launch below)
+    (1, 3, 16, 0, 32, 10, 32, 3),       # W % 32 == 0, ragged rows: the 32 x 4 tiles under wtpse_x3_small_wide(1) (test_tails_on_small_wide_tiles)
 ])
 def test_conv_fwd_bnf(case):
     """A convolution that finishes its own BatchNorm statistics (last-arriver tickets) against conv + wtpse_bn_finalize: same output
@@ -817,3 +823,218 @@ def test_x2h_zero_and_nonfinite_gradients():
     d, _, _ = o.conv_fwd_x3(n, None, packed.data_ptr() + 2 * xd, None, Ci, 3, in_amax=o.amax_of(n))
     # (non-finite, not necessarily NaN: a data gradient's epilogue clamps with v_max_f32, which turns a NaN into its -inf bound — loud either way)
     assert not bool(torch.isfinite(d[1, :, 2:5, 3:6]).any()) and bool(torch.isfinite(d[0]).all())
+
+
+# ---------------------------------------------------------------- wtpse_x3_small_wide(1): 32-channel blocks on 32 x 4 tiles of the wide maps
+@contextlib.contextmanager
+def small_wide(on):
+    """wtpse_x3_small_wide is process-global and part of wtpse_tuning_state(): set for the block, the previous value restored."""
+    L = ops().lib()
+    was = L.query("wtpse_x3_small_wide", int(on))
+    try:
+        yield
+    finally:
+        L.query("wtpse_x3_small_wide", was)
+
+
+@pytest.mark.parametrize("case", [(2, 16, 16, 32, 24, 64), (3, 16, 0, 32, 40, 96)])
+def test_small_wide_tiling_equals_default_tiles(case):
+    """The 32 x 4 tiles of wtpse_x3_small_wide(1) against the 32 x 8 tiles the same launches take by default, conv_x3_k and
+    conv_x3r_k alike: every accumulator sees the same products in the same order — outputs and masked gradients BITWISE equal; the
+    statistics partials come in twice the rows, their column sums agree to fp32 summation order."""
+    o, run = _x3_case_runner(case)
+    B, C0, C1, Co, H, W = case
+    L = o.lib()
+    n_old = L.query("wtpse_conv_x3_stats_blocks", B, H, W, Co, 3)
+    for x3r in (1, 2):
+        try:
+            L.query("wtpse_x3r_enable", x3r)
+            old = run()
+            with small_wide(1):
+                n_new = L.query("wtpse_conv_x3_stats_blocks", B, H, W, Co, 3)
+                new = run()
+        finally:
+            L.query("wtpse_x3r_enable", 1)
+        assert n_new == 2 * n_old, "the case must take the 128-pixel tiling (%d vs %d rows)" % (n_new, n_old)
+        assert any(a_.shape != b_.shape for a_, b_ in zip(new, old)), "the statistics partials must come in more rows"
+        _assert_same_outputs(new, old)
+    assert L.query("wtpse_x3_small_wide", -1) == 0
+
+
+def test_tails_on_small_wide_tiles():
+    """The in-launch BatchNorm tails on the 32 x 4 tiles: the forward finalize (test_conv_fwd_bnf) and the backward coefficients
+    (test_dgrad_bnb's tail run) under wtpse_x3_small_wide(1) — tickets and partial2 then come from wtpse_bnb_tail_tickets(nblk, ...)
+    with the doubled nblk; the assertions are those tests' own, "tickets left at zero" included."""
+    L = ops().lib()
+    fwd, bwd = (1, 3, 16, 0, 32, 10, 32, 3), (2, 32, 0, False, 32, 6, 32, 3, True, True)
+    with small_wide(1):
+        # rows of partials, hence nblk of the ticket queries: 3 tile rows of 4 instead of 2 of 8; 2 instead of 1
+        assert (L.query("wtpse_conv_x3_stats_blocks", 3, 10, 32, 32, 3), L.query("wtpse_conv_stats_blocks", 3, 10, 32)) == (9, 6)
+        assert (L.query("wtpse_conv_x3_stats_blocks", 2, 6, 32, 32, 3), L.query("wtpse_conv_stats_blocks", 2, 6, 32)) == (4, 2)
+        test_conv_fwd_bnf(fwd)
+        test_dgrad_bnb(bwd)
+    assert L.query("wtpse_x3_small_wide", -1) == 0
+
+
+# ---------------------------------------------------------------- tail_after_launch: the tails of launches beyond WTPSE_TAIL_MAX_WGS
+POISON = 0x40000000          # a ticket word no count reaches: a launch that folds in place never sees "I am last" behind it
+
+
+def _devrnd(*shape, seed, scale=1.0):
+    return torch.randn(*shape, device=DEV, generator=torch.Generator(device=DEV).manual_seed(seed)) * scale
+
+
+def _sentinel(*shape):
+    from dispatch_cases import NAN_BITS
+    return torch.full(shape, NAN_BITS, dtype=torch.int32, device=DEV).view(torch.float32)
+
+
+def _is_sentinel(t):
+    from dispatch_cases import NAN_BITS
+    return bool((t.view(torch.int32) == NAN_BITS).all())
+
+
+def _tail_buffers(nblk, cout):
+    L = ops().lib()
+    tickets = torch.full(((L.query("wtpse_bnb_tail_tickets", nblk, cout) + 63) & ~63,), POISON, dtype=torch.int32, device=DEV)
+    partial2 = torch.empty(L.query("wtpse_bnb_tail_partial2", nblk, cout), dtype=torch.float64, device=DEV)
+    return tickets, partial2
+
+
+def _same(what, got, want, failures):
+    if not torch.equal(got, want):
+        bad = ~(got == want)
+        failures.append("%s: %d of %d elements differ, first at flat index %d" % (what, int(bad.sum()), bad.numel(),
+                                                                                 int(bad.reshape(-1).to(torch.uint8).argmax())))
+
+
+def tail_forward(layout, case, after):
+    """wtpse_conv_fwd_bnf through the C ABI with POISONED tickets and sentinel outputs.  after = True (the launch exceeds
+    WTPSE_TAIL_MAX_WGS: the call nulls the ticket pointers it passes to the kernel and runs the stand-alone finalize itself): the
+    ticket words unchanged, scale / shift, mean, invstd and the running statistics BITWISE those of wtpse_bn_finalize on the call's own
+    stats, num_batches == 1.  after = False (the launch folds in place, and behind the poison nobody is ever last): the tail outputs
+    still the sentinel, the running statistics untouched.  Either way the output and stats of the plain entry point.  -> failures."""
+    o = ops()
+    L, ptr, st = o.lib(), o.ptr, o.stream_ptr()
+    B, C0, C1, Co, H, W, k = case
+    assert C1 == 0
+    x0 = _devrnd(B, C0, H, W, seed=81)
+    w = rnd(Co, C0, k, k, seed=82, scale=0.2)
+    bias = rnd(Co, seed=83).to(DEV)
+    pro0 = torch.stack([rnd(C0, seed=84) * 0.5 + 1.0, rnd(C0, seed=85)], 1).contiguous().to(DEV)
+    gamma, beta = (rnd(Co, seed=86) * 0.2 + 1).to(DEV), (rnd(Co, seed=87) * 0.2).to(DEV)
+    rm0, rv0 = rnd(Co, seed=88).to(DEV), (rnd(Co, seed=89).abs() + 0.5).to(DEV)
+    if layout == 1:
+        packed, xf, _ = pack_x3(w)
+        wptr = packed.data_ptr() + 2 * xf
+        y_ref, _, stats_ref = o.conv_fwd_x3(x0, None, wptr, bias, Co, k, pro0, 1, want_stats=True)
+    elif layout == 2:
+        packed, xf, _ = pack_x16(w)
+        wptr = packed.data_ptr() + 2 * xf
+        y_ref, stats_ref, _ = o.conv16_x3(x0, wptr, bias, Co, pro0, 1, want_stats=True)
+    else:
+        packed, wf, _ = pack(w)
+        wptr = packed.data_ptr() + 4 * wf
+        y_ref, _, stats_ref = o.conv_fwd(x0, None, wptr, bias, Co, k, pro0, 1, want_stats=True)
+    nblk = stats_ref.shape[0]
+    tickets, partial2 = _tail_buffers(nblk, Co)
+    y, stats = _sentinel(B, Co, H, W), _sentinel(nblk, Co, 2)
+    ss, mean, invstd = _sentinel(Co, 2), _sentinel(Co), _sentinel(Co)
+    rm, rv, nbt = rm0.clone(), rv0.clone(), torch.zeros(1, dtype=torch.int64, device=DEV)
+    L.call("wtpse_conv_fwd_bnf", ptr(x0), C0, 0, 0, wptr, layout, ptr(bias), ptr(pro0), 0, 1, ptr(y), ptr(stats), ptr(gamma), ptr(beta),
+           ptr(rm), ptr(rv), ptr(nbt), 0.1, 1e-5, ptr(ss), ptr(mean), ptr(invstd), ptr(partial2), ptr(tickets), B, H, W, Co, k, 0, 0, 0, st)
+    torch.cuda.synchronize()
+    what = "conv_fwd_bnf layout %d %s" % (layout, case)
+    failures = []
+    _same(what + ": output", y, y_ref, failures)
+    _same(what + ": stats", stats, stats_ref, failures)
+    del y, y_ref
+    if not after:
+        assert all(_is_sentinel(t) for t in (ss, mean, invstd)), what + ": a launch that folds in place must not get past poisoned tickets"
+        assert torch.equal(rm, rm0) and torch.equal(rv, rv0) and int(nbt) == 0, what
+        assert not bool((tickets == POISON).all()), what + ": a launch that folds in place takes its tickets"
+        return failures
+    assert bool((tickets == POISON).all()), what + ": a launch beyond the threshold must not touch its tickets"
+    rm2, rv2, nbt2 = rm0.clone(), rv0.clone(), torch.zeros(1, dtype=torch.int64, device=DEV)
+    ss2, mean2, invstd2 = o.bn_finalize(stats, B * H * W, gamma, beta, rm2, rv2, nbt2)
+    for name, a_, b_ in (("scale_shift", ss, ss2), ("save_mean", mean, mean2), ("save_invstd", invstd, invstd2),
+                         ("running_mean", rm, rm2), ("running_var", rv, rv2)):
+        _same(what + ": " + name, a_, b_, failures)
+    assert int(nbt) == 1 and int(nbt2) == 1, what
+    return failures
+
+
+def tail_backward(layout, case, frozen, after=True):
+    """wtpse_dgrad_bnb_coef / _frozen the same way: coef, dgamma, dbeta (and dbias) BITWISE those of wtpse_bn_bwd_finalize_coef / _frozen
+    on the call's own stats, the masked gradient and stats those of the plain entry point, the poisoned tickets unchanged."""
+    o = ops()
+    L, ptr, st = o.lib(), o.ptr, o.stream_ptr()
+    B, Cn, C1, Ct, H, W, k = case                  # the launch: Cn channels of dY in, Ct channels out, all of them BatchNorm'd
+    assert C1 == 0 and layout in (0, 1)
+    du = _devrnd(B, Cn, H, W, seed=91)
+    w = rnd(Cn, Ct, k, k, seed=92, scale=0.2)
+    yd = _devrnd(B, Ct, H, W, seed=93)
+    bn_ss = torch.stack([rnd(Ct, seed=94) * 0.3 + 1.0, rnd(Ct, seed=95) * 0.2], 1).contiguous().to(DEV)
+    bn_mean = (rnd(Ct, seed=96) * 0.1).to(DEV)
+    gamma, invstd = (rnd(Ct, seed=97) * 0.2 + 1).to(DEV), (rnd(Ct, seed=98).abs() + 0.5).to(DEV)
+    if layout == 1:
+        packed, _, off = pack_x3(w)
+        wptr = packed.data_ptr() + 2 * off
+    else:
+        packed, _, off = pack(w)
+        wptr = packed.data_ptr() + 4 * off
+    g_ref, _, stats_ref, _ = o.dgrad_bnb(du, wptr, layout, Ct, k, yd, bn_ss, bn_mean, True)
+    nblk = stats_ref.shape[0]
+    tickets, partial2 = _tail_buffers(nblk, Ct)
+    g, stats = _sentinel(B, Ct, H, W), _sentinel(nblk, Ct, 2)
+    coef, dg, dbt, dbias = _sentinel(Ct, 3), _sentinel(Ct), _sentinel(Ct), _sentinel(Ct)
+    args = [ptr(du), Cn, wptr, layout, ptr(g), 0, Ct, ptr(yd), ptr(bn_ss), ptr(bn_mean), 1, 0, Ct, ptr(stats), ptr(gamma), ptr(invstd),
+            ptr(coef), ptr(dg), ptr(dbt)] + ([ptr(dbias)] if frozen else [])
+    L.call("wtpse_dgrad_bnb_coef_frozen" if frozen else "wtpse_dgrad_bnb_coef", *args, 0, ptr(partial2), ptr(tickets), B, H, W, Ct, k, 0, st)
+    torch.cuda.synchronize()
+    what = "dgrad_bnb_coef%s layout %d %s" % ("_frozen" if frozen else "", layout, case)
+    failures = []
+    _same(what + ": masked gradient", g, g_ref, failures)
+    _same(what + ": stats", stats, stats_ref, failures)
+    del g, g_ref
+    assert after
+    assert bool((tickets == POISON).all()), what + ": a launch beyond the threshold must not touch its tickets"
+    coef2, dg2, dbt2, dbias2 = _sentinel(Ct, 3), _sentinel(Ct), _sentinel(Ct), _sentinel(Ct)
+    if frozen:
+        L.call("wtpse_bn_bwd_finalize_coef_frozen", ptr(stats), nblk, Ct, ptr(gamma), ptr(invstd), ptr(coef2), ptr(dg2), ptr(dbt2), ptr(dbias2), 0, st)
+    else:
+        L.call("wtpse_bn_bwd_finalize_coef", ptr(stats), nblk, Ct, B * H * W, ptr(gamma), ptr(bn_mean), ptr(invstd), ptr(coef2), ptr(dg2),
+               ptr(dbt2), 0, st)
+    torch.cuda.synchronize()
+    for name, a_, b_ in (("coef", coef, coef2), ("dgamma", dg, dg2), ("dbeta", dbt, dbt2)) + ((("dbias", dbias, dbias2),) if frozen else ()):
+        assert not _is_sentinel(b_) and bool(torch.isfinite(b_).all()), what + ": " + name
+        _same(what + ": " + name, a_, b_, failures)
+    return failures
+
+
+# the smallest launches of more than 8192 workgroups (8448 tiles), 1x1 where the layout has one: layout, (B, C0, C1, Cout, H, W, k)
+TAIL_AFTER_CASES = [(0, (3, 3, 0, 5, 704, 1024, 1)), (1, (3, 16, 0, 32, 704, 1024, 1)), (2, (3, 16, 0, 16, 704, 1024, 3))]
+
+
+@pytest.mark.parametrize("layout,case", TAIL_AFTER_CASES)
+def test_tail_after_launch(layout, case):
+    """Every convolution with a BatchNorm tail above WTPSE_TAIL_MAX_WGS (8192 workgroups: any 16- or 32-channel layer at 512 x 512
+    from B = 9) runs the stand-alone fold behind its launch (tail_after_launch, internal.h): the forward finalize on all three
+    launchers, the backward coefficients and their frozen form on layouts 0 and 1.  No tolerance: the same kernel on the same
+    partials as the two-step route."""
+    B, C0, C1, Co, H, W, k = case
+    n = ops()._stats_blocks(layout, B, H, W, Co, k)
+    assert n == 8448, n
+    failures = tail_forward(layout, case, after=True)
+    if layout != 2:
+        failures += tail_backward(layout, case, frozen=False)
+        failures += tail_backward(layout, case, frozen=True)
+    assert not failures, "\n  ".join(failures)
+
+
+def test_tail_folds_in_place_at_the_threshold():
+    """Exactly 8192 workgroups still fold in place: behind poisoned tickets the tail outputs stay the sentinel."""
+    case = (2, 3, 0, 5, 1024, 1024, 1)
+    assert ops()._stats_blocks(0, 2, 1024, 1024) == 8192
+    failures = tail_forward(0, case, after=False)
+    assert not failures, "\n  ".join(failures)

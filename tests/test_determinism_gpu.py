@@ -153,7 +153,7 @@ def test_plan_refuses_to_replay_under_other_switches():
     before = [n.flat_params().clone() for n in nets]
     L = ops.lib()
     state = L.query("wtpse_tuning_state")
-    for name, other in (("wtpse_x3r_enable", 0), ("wtpse_x3_terms", 3 if ops.x3_terms() != 3 else 2)):
+    for name, other in (("wtpse_x3r_enable", 0), ("wtpse_x3_terms", 3 if ops.x3_terms() != 3 else 2), ("wtpse_x3_small_wide", 1)):
         was = L.query(name, other)
         try:
             assert L.query("wtpse_tuning_state") != state

@@ -65,6 +65,75 @@ def test_x3_wgrad_cases_take_the_named_branch(L):
         assert int(E.wgrad_x3_supported(cin, cout, k, c0)) == L.query("wtpse_wgrad_x3_supported", cin, cout, k, c0), (cin, cout, k, c0)
 
 
+def test_tw32_wgrad_cases_change_their_tile_count():
+    """WGX3_TW32_CASES (run by the tw32 job of tests/switch_worker.py): listed under conv_wgrad_x3_k<3, 5, Q> for both Q, with two and
+    three tile columns, ragged last columns and rows — and each with another tile count, hence another default split count, than on the
+    16-wide tiles: that is what lets a process prove the switch in force.  (The library's side of it needs a process started under
+    the switch: test_switch_paths_cpu.py.)"""
+    for name, (shape, expect, tiles16, _) in E.WGX3_TW32_CASES.items():
+        B, C0, C1, Co, H, W = shape
+        assert E.wgrad_x3_supported(C0 + C1, Co, 3, C0 if C1 else 8), name
+        g = E.wgrad_x3_geometry(B, H, W, C0 + C1, Co, tw32=True)
+        for key, val in expect.items():
+            assert g[key] == val, (name, key, g)
+        assert W % 32 != 0 and (H % g["TH"] != 0 or name == "tw32_cat"), name            # ragged last tile column (and row)
+        assert E.wgrad_x3_geometry(B, H, W, C0 + C1, Co)["tiles"] == tiles16 != g["tiles"], name
+        assert E.wgrad_x3_ksplit(B, H, W, C0 + C1, Co, tw32=True) == g["tiles"] and E.wgrad_x3_ksplit(B, H, W, C0 + C1, Co) == tiles16, name
+    geo = [E.wgrad_x3_geometry(s[0], s[4], s[5], s[1] + s[2], s[3], tw32=True) for s, _, _, _ in E.WGX3_TW32_CASES.values()]
+    assert {g["Q"] for g in geo} == {False, True}
+    assert any(v.pro == 3 and v.acc for v in E.WGX3_TW32_CASES["tw32_cat"][3]) and E.WGX3_TW32_CASES["tw32_cat"][0][2]
+    # 16-wide maps keep the 16-wide tiles under the switch
+    assert E.wgrad_x3_geometry(2, 8, 16, 32, 32, tw32=True) == E.wgrad_x3_geometry(2, 8, 16, 32, 32)
+
+
+X3_TABLES = ("x3", "x3r", "x3half", "x3sw", "x3k1")
+
+
+def test_x3_tiling_restated(L):
+    """x3_tiling of exact_cases against wtpse_conv_x3_stats_blocks for every case of every x3 table (and the layout-1 bnb cases) under
+    the default switches, wtpse_x3_small_wide(1) and wtpse_x3r_enable(0) — the setters work on the host —; and every new case in the
+    branch it is listed under."""
+    shapes = [E.conv_shape(t, c) for t in X3_TABLES for c in E.TABLES[t]]
+    shapes += [(c[0], c[1] + c[2], 0, c[1] + c[2], c[5], c[6], c[7]) for c in E.TABLES["bnb"] if c[9]]
+    assert L.query("wtpse_x3_small_wide", -1) == 0 and L.query("wtpse_x3r_enable", -1) == 1
+    try:
+        for sw, x3r in ((0, 1), (1, 1), (0, 0), (1, 0), (1, 2)):
+            L.query("wtpse_x3_small_wide", sw)
+            L.query("wtpse_x3r_enable", x3r)
+            for B, C0, C1, Co, H, W, k in shapes:
+                for cout in (Co, C0 + C1):               # forward and data-gradient direction
+                    t = E.x3_tiling(B, H, W, cout, k, small_wide=sw, x3r=x3r)
+                    assert t["tiles"] == L.query("wtpse_conv_x3_stats_blocks", B, H, W, cout, k), ((B, C0, C1, Co, H, W, k), cout, sw, x3r, t)
+    finally:
+        L.query("wtpse_x3_small_wide", 0)
+        L.query("wtpse_x3r_enable", 1)
+    # the new cases in the branches they are listed under
+    for case in E.X3_SMALL_WIDE_CASES:
+        B, C0, C1, Co, H, W, k = case
+        for cout in (Co, C0 + C1):
+            for x3r in (1, 2):
+                t = E.x3_tiling(B, H, W, cout, k, small_wide=1, x3r=x3r)
+                assert (t["small"], t["half"], t["mt"], t["TW"], t["TH"]) == (1, 0, 1, 32, 4), (case, cout, t)
+            off = E.x3_tiling(B, H, W, cout, k)
+            assert (off["small"], off["half"], off["mt"], off["TH"]) == (0, 0, 1, 8), (case, cout, off)
+    sw = [E.x3_tiling(c[0], c[4], c[5], c[3], c[6], small_wide=1) for c in E.X3_SMALL_WIDE_CASES]
+    assert {t["tiles_x"] for t in sw} == {1, 2, 3}
+    last_rows = {c[4] - (t["tiles_y"] - 1) * 4 for c, t in zip(E.X3_SMALL_WIDE_CASES, sw)}
+    assert last_rows == {1, 2, 4}                         # ragged last tile rows of one and two rows, full ones, an image lower than a tile
+    assert {c[6] for c in E.X3_SMALL_WIDE_CASES} == {1, 3} and any(c[2] for c in E.X3_SMALL_WIDE_CASES)
+    assert any(c[3] == 64 for c in E.X3_SMALL_WIDE_CASES) and any(c[3] > 64 for c in E.X3_SMALL_WIDE_CASES) and any(c[3] <= 16 for c in E.X3_SMALL_WIDE_CASES)
+    for case in E.BNB_SMALL_WIDE:
+        B, Cl, Co, bn_second, Cn, H, W, k, relu, x3 = case
+        assert case in E.TABLES["bnb"] and x3, case
+        t = E.x3_tiling(B, H, W, Cl + Co, k, small_wide=1)
+        assert (t["small"], t["mt"], t["TW"], t["TH"]) == (1, 1, 32, 4), (case, t)
+    for B, C0, C1, Co, H, W, k in E.X3_K1_MT2_CASES:
+        t = E.x3_tiling(B, H, W, Co, k)
+        assert k == 1 and (t["mt"], t["half"], t["small"], t["tiles"]) == (2, 0, 0, 512), t
+    # no 1x1 case of the older tables reaches the 64-channel blocks
+    assert not any(E.x3_tiling(c[0], c[4], c[5], c[3], c[6])["mt"] == 2 for c in E.TABLES["x3"] if c[6] == 1)
+
+
 def test_r_wgrad_cases_take_the_named_branch(L):
     plans = {}
     for name, (shape, expect, variants, _) in E.WGR_CASES.items():
@@ -188,6 +257,17 @@ def test_x3_wgrad_cases_are_exact_and_have_teeth():
     _wgrad_checks("x3")
 
 
+def test_tw32_wgrad_cases_are_exact_and_have_teeth():
+    _wgrad_checks("x3tw32")
+    for name in E.WGX3_TW32_CASES:
+        shape, k, variants, classes = E.wgrad_case("x3tw32", name)
+        for cls in ("TX", "TD"):
+            for v in variants:
+                # (the concat sums 720 pixels x 64 channels per weight — twice the pixels of the other two — and takes the next density)
+                assert E.wgrad_problem("x3tw32", name, cls, v)["d"] >= (0.125 if name == "tw32_cat" else 0.25), (name, cls, E.vid(v))
+    E.clear_caches()
+
+
 def test_r_wgrad_cases_are_exact_and_have_teeth():
     _wgrad_checks("r")
 
@@ -209,6 +289,7 @@ def test_forward_and_dgrad_cases_are_exact_and_have_teeth(table):
                     left_out.add((idx, cls, variant))
                     continue
                 assert p["d"] is not None and (cls == "I" or p["d"] >= E.MIN_DENSITY_EXISTING), what
+                assert table != "x3sw" or p["d"] >= E.MIN_DENSITY_SMALL_WIDE, what
                 assert float(p["absout"].max()) / p["unit"] < E.BOUND and E.fp32_exact(p["out"]), what
                 if variant in ("bias", "stats") and cls == "I":
                     # (the rows of partials are compared through their fp64 sum: each row exact, the total need not fit fp32)

@@ -10,7 +10,7 @@ import torch
 
 import exact_cases as E
 from test_kernels_gpu import ops, pack, DEV
-from test_conv_x3_gpu import pack_x3, pack_x16
+from test_conv_x3_gpu import pack_x3, pack_x16, small_wide
 
 pytestmark = pytest.mark.gpu
 
@@ -90,7 +90,7 @@ def run_wgrad(fam, p, v, ksplit=None):
     ptr, st = o.ptr, o.stream_ptr()
     if fam in ("fp32", "ksplit"):
         ns = ksplit or L.query("wtpse_wgrad_ksplit", B, H, W, Cin, Co)
-    elif fam == "x3":
+    elif fam in ("x3", "x3tw32"):
         ns = L.query("wtpse_wgrad_x3_ksplit", B, H, W, Cin, Co)
     else:
         ns = L.query("wtpse_wgrad_r_slabs", B, H, W, Cin, Co)
@@ -105,7 +105,7 @@ def run_wgrad(fam, p, v, ksplit=None):
     if fam in ("fp32", "ksplit"):
         L.call("wtpse_conv_wgrad", ptr(dy), ptr(x0), C0, ptr(x1), C1, ptr(pro0), ptr(pro1), pro_relu, ptr(slab), ptr(dbs), ns, ptr(dw),
                ptr(db), int(v.acc), B, H, W, Co, k, st)
-    elif fam == "x3":
+    elif fam in ("x3", "x3tw32"):
         L.call("wtpse_conv_wgrad_x3", ptr(dy), ptr(x0), C0, ptr(x1), C1, ptr(pro0), ptr(pro1), pro_relu, ptr(slab), ns, ptr(dw), int(v.acc),
                B, H, W, Co, k, st)
     else:
@@ -119,6 +119,10 @@ def run_wgrad(fam, p, v, ksplit=None):
 
 def check_wgrad(fam, name, modes_of, ksplit=None):
     """Every class, variant and mode of one case; the failures of all calls in one message."""
+    finish(wgrad_failures(fam, name, modes_of, ksplit))
+
+
+def wgrad_failures(fam, name, modes_of, ksplit=None):
     shape, k, variants, classes = E.wgrad_case(fam, name)
     failures = []
     for cls in E.wgrad_classes(classes):
@@ -137,7 +141,7 @@ def check_wgrad(fam, name, modes_of, ksplit=None):
                     f = differs(db, p["db"], what + ": dbias (cout)")
                     if f:
                         failures.append(f)
-    finish(failures)
+    return failures
 
 
 def all_modes(cls):
@@ -274,6 +278,60 @@ def test_conv_x3(table, idx, cls):
                         compare_conv(p, out, stats, None, "conv_fwd_x3 %s %s class %s %s mode %d x3r %d%s"
                                      % (table, case, cls, variant, mode, setting, " amax" if with_table else ""), failures)
     finish(failures)
+
+
+def x3_failures(table, idx, cls, x3r_settings, sw_settings=(0,)):
+    """Every variant of one case of an x3 table in one class through wtpse_conv_fwd_x3: every mode the class is exact in, with an amax
+    table where the entry point takes one, under every wtpse_x3r_enable setting of x3r_settings and wtpse_x3_small_wide setting of
+    sw_settings.  -> the first_difference messages."""
+    case = E.TABLES[table][idx]
+    failures = []
+    for variant in E.conv_variants(table, case):
+        if cls not in E.conv_classes(variant):
+            continue
+        p = E.conv_problem(table, idx, cls, variant)
+        assert p["d"] is not None, (table, case, cls, variant)
+        for mode in all_modes(cls):
+            with x3_terms(mode):
+                packed, xf, xd = pack_x3(p["w"].float())
+                for with_table in table_runs("x3", variant, mode):
+                    tabs = amax_tables(p) if with_table else (None, None)
+                    for sw in sw_settings:
+                        for setting in x3r_settings:
+                            with x3r_enable(setting), small_wide(sw):
+                                out, stats, _ = conv_call("wtpse_conv_fwd_x3", 1, p, packed.data_ptr() + 2 * (xd if p["back"] else xf), tabs)
+                            compare_conv(p, out, stats, None, "conv_fwd_x3 %s %s class %s %s mode %d x3r %d small_wide %d%s"
+                                         % (table, case, cls, variant, mode, setting, sw, " amax" if with_table else ""), failures)
+    return failures
+
+
+@pytest.mark.parametrize("idx,cls", [(i, c) for i in range(len(E.X3_SMALL_WIDE_CASES)) for c in E.CONV_CLASSES])
+def test_conv_x3_small_wide(idx, cls):
+    """X3_SMALL_WIDE_CASES: the 32-channel blocks on 32 x 4 tiles that only wtpse_x3_small_wide(1) reaches — conv_x3_k<KS, 1, 5, EPI, 1,
+    TERMS> (wtpse_x3r_enable 1) and, for the 3x3 cases, conv_x3r_k<1, 1, 1, 5, ...> (2) — and the same calls with the switch off, so
+    that a failure tells the tiling from the case."""
+    B, C0, C1, Co, H, W, k = E.X3_SMALL_WIDE_CASES[idx]
+    finish(x3_failures("x3sw", idx, cls, (1, 2) if k == 3 else (1,), (1, 0)))
+    assert ops().lib().query("wtpse_x3_small_wide", -1) == 0
+
+
+@pytest.mark.parametrize("idx,cls", [(i, c) for i in range(len(E.X3_K1_MT2_CASES)) for c in E.CONV_CLASSES])
+def test_conv_x3_k1_mt2(idx, cls):
+    """X3_K1_MT2_CASES: the 64-channel blocks on a 1x1 layer, conv_x3_k<1, 2, ...> — what up2.conv2 runs in the step at B = 32."""
+    finish(x3_failures("x3k1", idx, cls, (1,)))
+
+
+@pytest.mark.parametrize("case", E.BNB_SMALL_WIDE)
+def test_dgrad_bnb_small_wide(case):
+    """EPI 2 on the 32 x 4 tiles: the bnb cases on wide maps with W % 32 == 0 once more under wtpse_x3_small_wide(1), compared as
+    test_dgrad_bnb compares them (masked gradient, other half, class-I partials through their fp64 sum)."""
+    B, Cl, Co, bn_second, Cn, H, W, k, relu, x3 = case
+    L = ops().lib()
+    with small_wide(1):
+        assert L.query("wtpse_conv_x3_stats_blocks", B, H, W, Cl + Co, k) == E.x3_tiling(B, H, W, Cl + Co, k, small_wide=1)["tiles"]
+        assert E.x3_tiling(B, H, W, Cl + Co, k, small_wide=1)["small"] == 1 and x3
+        test_dgrad_bnb(E.TABLES["bnb"].index(case))
+    assert L.query("wtpse_x3_small_wide", -1) == 0
 
 
 @pytest.mark.parametrize("idx", range(len(E.TABLES["x16"])))

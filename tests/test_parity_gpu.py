@@ -912,14 +912,7 @@ def _rescale_blocks(net, plan):
 RESCALE = {"down2": 1e-3, "up3": 30.0, "down4": 1e4, "up1": 1e-5, "prior_dist.down3": 1e-4, "prior_dist.up2": 3e3, "inc": 64.0}
 
 
-@pytest.mark.parametrize("H", [64, 256])
-def test_update_predict_rescaled_blocks_vs_oracle(H):
-    """Round 6 (VERDICT r05 #2): activations far from O(1) at the plain 1e-4 bar.  Whole blocks are rescaled function-preservingly
-    (_rescale_blocks: gamma, beta x f, the consumer's weights / f, f from 1e-5 to 1e4), so the reference computes the same, equally
-    well-conditioned function — but the tensors between the rescaled layers are up to 1e4 and down to 1e-5 of their usual size.  Round
-    5's fixed 2^2 input scale lost relative precision below 2^-5 and overflowed to NaN above 2^14 there; the data-driven scale (the
-    Samuelson bound behind a train-mode BatchNorm, the stored data's amax behind an eval-mode one) must hold the bar at every f.
-    Train-mode update() and eval-mode predict() against the CPU oracle on the same state dict."""
+def _rescaled_blocks_vs_oracle(H):
     B, pb = 6, 2
     img, od, oc = make_inputs(177, B, H, H)
     eps = make_noise(178, (B, 1, H, H))
@@ -945,6 +938,30 @@ def test_update_predict_rescaled_blocks_vs_oracle(H):
     assert bool(torch.isfinite(pred).all())
     close(pred, ref_pred, atol=TOL, what="predict, rescaled blocks")
     close(att, ref_att, atol=TOL, what="attention, rescaled blocks")
+
+
+@pytest.mark.parametrize("H", [64, 256])
+def test_update_predict_rescaled_blocks_vs_oracle(H):
+    """Round 6 (VERDICT r05 #2): activations far from O(1) at the plain 1e-4 bar.  Whole blocks are rescaled function-preservingly
+    (_rescale_blocks: gamma, beta x f, the consumer's weights / f, f from 1e-5 to 1e4), so the reference computes the same, equally
+    well-conditioned function — but the tensors between the rescaled layers are up to 1e4 and down to 1e-5 of their usual size.  Round
+    5's fixed 2^2 input scale lost relative precision below 2^-5 and overflowed to NaN above 2^14 there; the data-driven scale (the
+    Samuelson bound behind a train-mode BatchNorm, the stored data's amax behind an eval-mode one) must hold the bar at every f.
+    Train-mode update() and eval-mode predict() against the CPU oracle on the same state dict."""
+    _rescaled_blocks_vs_oracle(H)
+
+
+def test_update_predict_rescaled_blocks_small_wide_tiles():
+    """The same at H = 64 under wtpse_x3_small_wide(1), at that test's own tolerances: down1 and up4 then run the 32-channel blocks on
+    32 x 4 tiles — the one place where the Python side's buffer sizing (ops._stats_blocks, the ticket and partial2 queries) is
+    exercised under the switch."""
+    from test_conv_x3_gpu import small_wide
+    from wtpse_hip import ops
+    L = ops.lib()
+    with small_wide(1):
+        assert L.query("wtpse_conv_x3_stats_blocks", 6, 64, 64, 32, 3) == 2 * L.query("wtpse_conv_stats_blocks", 6, 64, 64)
+        _rescaled_blocks_vs_oracle(64)
+    assert L.query("wtpse_x3_small_wide", -1) == 0
 
 
 @pytest.mark.parametrize("H", [64, 256])
