@@ -696,6 +696,33 @@ int wtpse_quality_sums(const unsigned char* img, unsigned* sums, int N, int S, v
 int wtpse_quality_apply(const unsigned char* img, const int* params, const unsigned* sums, const unsigned long long* pos,
                         unsigned long long seed, unsigned char* out, int N, int S, void* stream);
 
+/* ---- JPEG compression augmentation: baseline JPEG's pixel round trip without the bit stream (csrc/jpeg.hip) -----------------
+ * The optional stage between the image-quality stage and CLAHE (or wtpse_input_finish); input_pipeline.jpeg_host is its
+ * specification in integers — libjpeg's "islow" codec, pinned byte for byte to what Pillow writes and reads back
+ * (tests/test_jpeg_cpu.py) — and the device equals it byte for byte.  img [N][S][S][3] uint8, S a multiple of 16 (no partial MCU),
+ * 16 <= S <= 4096, 1 <= N <= 65535.  mode [N] int32: 0 the sample is copied, 1 = 4:4:4, 2 = 4:2:0 (chroma at half resolution both
+ * ways).  tables [N][2][64] int32: the luma and the chroma quantisation table Q of every sample in natural (row-major) order,
+ * 1 <= Q <= 255; recips [N][2][64] int32 = ceil(2^32 / (8 Q)) (input_pipeline.jpeg_reciprocals): the quantiser's division is
+ * mulhi(|c| + (8 Q >> 1), recip), equal to the quotient for every |c| <= 32767 (tests/test_jpeg_cpu.py, exhaustively).  `>>` is the
+ * arithmetic shift, DESCALE(x, n) = (x + (1 << (n - 1))) >> n:
+ *   Y  = (19595 R + 38470 G + 7471 B + 32768) >> 16,  Cb = (-11059 R - 21709 G + 32768 B + 8388608 + 32767) >> 16,
+ *   Cr = (32768 R - 27439 G - 5329 B + 8388608 + 32767) >> 16
+ *   4:2:0: chroma = (the sum of a 2 x 2 cell + 1 in even output columns, 2 in odd ones) >> 2
+ *   per 8 x 8 block of x - 128: libjpeg's jfdctint (CONST_BITS 13, PASS1_BITS 2; rows, then columns; the output carries a factor 8),
+ *   k = sign(c) ((|c| + (8 Q >> 1)) / (8 Q)), c' = k Q, libjpeg's jidctint (columns DESCALE 11, rows DESCALE 18), + 128, clamp 0 .. 255
+ *   4:2:0: libjpeg's h2v2 "fancy" upsampling: cs = 3 near row + far row (the far row: above for even output rows, below for odd,
+ *   the near row itself at the picture's top and bottom), even column (3 cs[x] + cs[x - 1] + 8) >> 4, odd (3 cs[x] + cs[x + 1] + 7) >> 4,
+ *   the picture's first column (4 cs[0] + 8) >> 4, its last (4 cs[last] + 7) >> 4
+ *   R = Y + ((91881 cr + 32768) >> 16), G = Y + ((-22554 cb - 46802 cr + 32768) >> 16), B = Y + ((116130 cb + 32768) >> 16), each
+ *   clamped to 0 .. 255 (cb = Cb - 128, cr = Cr - 128)
+ * Two launches: the first decodes the half-resolution chroma planes of the 4:2:0 samples into chroma [N][2][S/2][S/2] uint8 (nothing
+ * else of a sample ever leaves the chip between the two colour conversions), the second does everything else and, for a 4:2:0
+ * sample, upsamples out of `chroma`.  chroma == NULL: the first launch is skipped — the caller asserts that no sample has mode 2.
+ * Integers only, no atomics: the same bytes on every run.  img, out 16-byte aligned and distinct, chroma 4-byte aligned; img is
+ * not written.  The entry point does not check mode, tables and recips (ops.jpeg_roundtrip does). */
+int wtpse_jpeg_roundtrip(const unsigned char* img, const int* mode, const int* tables, const int* recips, unsigned char* chroma,
+                         unsigned char* out, int N, int S, void* stream);
+
 /* ---- CLAHE preprocessing: tile histograms, clipped LUTs, bilinear blend (csrc/clahe.hip) ----------------------------------
  * Contrast-limited adaptive histogram equalisation of img [N][H][W][3] uint8 in front of the normalisation (wtpse_input_finish /
  * wtpse_image_finish); input_pipeline.clahe_host is its specification in integers, and the device equals it byte for byte.

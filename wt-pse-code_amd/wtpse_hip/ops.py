@@ -1629,6 +1629,38 @@ def image_quality(img, params, seed, pos, want_pos=False):
     return (out, next_pos) if want_pos else out
 
 
+# ----------------------------------------------------------------------------------------------- JPEG compression
+def jpeg_roundtrip(img, mode, tables):
+    """[N,S,S,3] uint8 on the device with S a multiple of 16, (mode [N], tables [N,2,64]) integers on the host
+    (input_pipeline.draw_jpeg: mode 0 off, 1 = 4:4:4, 2 = 4:2:0; luma and chroma quantisation tables in natural order, 1 .. 255) ->
+    the batch after baseline JPEG's round trip of the pixels, a new tensor (csrc/jpeg.hip; input_pipeline.jpeg_host is the
+    specification, byte for byte, and is pinned to Pillow).  A batch whose modes are all 0 launches nothing and returns `img`
+    itself.  The input is not written."""
+    from .input_pipeline import JPEG_MAX_SIZE, _check_jpeg_size, check_jpeg_params, jpeg_is_neutral, jpeg_reciprocals
+    import numpy as np
+    _chk_u8(img, "img", 4)
+    N, S = int(img.shape[0]), int(img.shape[1])
+    if img.shape[2] != S or img.shape[3] != 3 or not 1 <= N <= 65535:
+        raise ValueError("jpeg_roundtrip: img must be [N,S,S,3] with 1 <= N <= 65535 and S a multiple of 16 up to %d (got %s)"
+                         % (JPEG_MAX_SIZE, tuple(img.shape)))
+    _check_jpeg_size(S)
+    mode, tables = check_jpeg_params(mode, tables, N)
+    if jpeg_is_neutral(mode).all():
+        return img
+    if img.data_ptr() % 16:
+        raise ValueError("jpeg_roundtrip: img must be 16-byte aligned (a view at an odd offset: clone it)")
+    dev = img.device
+    tables = np.where((mode != 0)[:, None, None], tables, 1)            # (the tables of a neutral row are not read: any reciprocal)
+    # every table stays referenced until the launches are queued: a temporary's block would be handed to the next allocation
+    dmode = torch.from_numpy(mode.astype(np.int32)).to(dev, non_blocking=True)
+    dtab = torch.from_numpy(tables.astype(np.int32)).to(dev, non_blocking=True)
+    drec = torch.from_numpy(jpeg_reciprocals(tables)).to(dev, non_blocking=True)
+    chroma = torch.empty((N, 2, S // 2, S // 2), dtype=torch.uint8, device=dev) if (mode == 2).any() else None
+    out = torch.empty_like(img)
+    lib().call("wtpse_jpeg_roundtrip", ptr(img), ptr(dmode), ptr(dtab), ptr(drec), ptr(chroma), ptr(out), N, S, stream_ptr())
+    return out
+
+
 # ----------------------------------------------------------------------------------------------- CLAHE preprocessing
 _CLAHE_TABLES = {}
 

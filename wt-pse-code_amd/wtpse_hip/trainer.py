@@ -111,13 +111,25 @@ class FundusBatches:
     clahe: an `input_pipeline.Clahe` switches the CLAHE preprocessing on (None: off — not one launch or allocation is added): the
     uint8 batch is equalised after every other stage and immediately before the normalisation.  It draws nothing and adds no feed
     state; it is a preprocessing step, so whatever reads the run's checkpoints must apply the same one: TrainRun writes
-    `clahe.record()` into every checkpoint as "clahe" (`clahe_record()` is what it asks the feed for)."""
+    `clahe.record()` into every checkpoint as "clahe" (`clahe_record()` is what it asks the feed for).
+
+    jpeg: an `input_pipeline.JpegCompression` switches the JPEG compression stage on (None: off — not one launch, allocation or draw
+    is added): every selected sample goes through baseline JPEG's round trip of the pixels at a drawn quality, 4:2:0 or 4:4:4, after
+    the image-quality stage and before CLAHE.  Its draws (`draw_jpeg`) come from the numpy generator AFTER all of the batch's other
+    draws, the appearance networks' included.  The stage reads no device random stream: the generator, which TrainRun's checkpoints
+    carry, is all of its state, and `state()` has no entry for it.  The side must be a multiple of 16 (ValueError here).  It is a
+    training augmentation only; its effect on the Dice / HD95 of a held-out domain has not been measured."""
 
     def __init__(self, datasets, batch_size, device, size=256, augment=None, pipe=None, style=None, quality=None, clahe=None,
-                 appearance=None):
-        from .input_pipeline import (QUALITY_MAX_SIZE, AppearanceNets, Clahe, DeviceInputPipeline, _check_appearance_size,
-                                     _check_mix_size)
+                 appearance=None, jpeg=None):
+        from .input_pipeline import (QUALITY_MAX_SIZE, AppearanceNets, Clahe, DeviceInputPipeline, JpegCompression,
+                                     _check_appearance_size, _check_jpeg_size, _check_mix_size)
         self.augment = augment
+        if jpeg is not None:
+            if not isinstance(jpeg, JpegCompression):
+                raise ValueError("jpeg must be an input_pipeline.JpegCompression or None, got %r" % (jpeg,))
+            _check_jpeg_size(int(size))
+        self.jpeg = jpeg
         self.style = style
         self.quality = quality
         if appearance is not None:
@@ -158,7 +170,7 @@ class FundusBatches:
         if self.augment is None:
             images, masks = multi_batch([self.datasets[i] for i in self.order], self.per_domain, np_rng)
             draws = [draw(py_rng, self.size) for _ in images]
-            if self.style is None and self.quality is None and self.clahe is None and self.appearance is None:
+            if self.style is None and self.quality is None and self.clahe is None and self.appearance is None and self.jpeg is None:
                 return self.pipe(images, masks, draws)
             return self.pipe(images, masks, draws, **self._stage_draws(np_rng, len(images)))
         images, masks, draws, aug_draws = [], [], [], []
@@ -169,15 +181,15 @@ class FundusBatches:
                 masks += mask
                 draws.append(draw(py_rng, self.size))
                 aug_draws.append(draw_augment(py_rng, np_rng, self.size, self.augment))
-        if self.style is None and self.quality is None and self.clahe is None and self.appearance is None:
+        if self.style is None and self.quality is None and self.clahe is None and self.appearance is None and self.jpeg is None:
             return self.pipe(images, masks, draws, aug_draws)
         return self.pipe(images, masks, draws, aug_draws, **self._stage_draws(np_rng, len(images)))
 
     def _stage_draws(self, np_rng, n):
         """The draws of the stages behind the augmentations: amplitude mixing, then image quality, then — drawn last, although the
         stage runs in front of image quality — the appearance networks: the stages that were there before it draw what they drew
-        without it.  CLAHE, the last stage, draws nothing and rides along."""
-        from .input_pipeline import draw_appearance, draw_quality
+        without it — and after them, for the same reason, the JPEG stage.  CLAHE, the last stage, draws nothing and rides along."""
+        from .input_pipeline import draw_appearance, draw_jpeg, draw_quality
         kw = {}
         if self.style is not None:
             kw["mix_draws"] = self._mix_draws(np_rng)
@@ -187,6 +199,8 @@ class FundusBatches:
             kw["clahe"] = self.clahe
         if self.appearance is not None:
             kw["appearance_draws"] = draw_appearance(np_rng, n, self.size, self.appearance) + (self.appearance.spacing,)
+        if self.jpeg is not None:
+            kw["jpeg_draws"] = draw_jpeg(np_rng, n, self.jpeg)
         return kw
 
     def clahe_record(self):
