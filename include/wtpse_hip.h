@@ -916,7 +916,9 @@ int wtpse_copy_probe(const float* src, float* dst, long long n, int bytes_per_la
  * HBM-bandwidth micro-benchmark BASELINE.json's wording names and are never called by the training path.
  * Specification (self-defined, parity unpinned): oracle/dwt_cpu.py — separable, orthonormal, periodic extension, lifting,
  * Mallat layout.  x / coef: [planes][H][W] fp32, distinct buffers; wavelet 0 = Haar, 1 = Daubechies 4-tap ("db2");
- * H, W divisible by 2^levels; tmp: 2 * planes * (H/2) * (W/2) floats. */
+ * H, W divisible by 2^levels; tmp: 2 * planes * (H/2) * (W/2) floats.  x, coef and tmp must be 8-byte aligned (the kernels move
+ * float2; anything else is refused before a launch); on square 256 / 512 planes (levels <= 7 / 8) 16-byte alignment of all three
+ * selects the streaming forward path, 8-byte alignment the generic one (tests/dwt_cases.py restates the dispatcher). */
 int wtpse_dwt2_fwd(const float* x, float* coef, float* tmp, int planes, int H, int W, int wavelet, int levels, void* stream);
 int wtpse_dwt2_inv(const float* coef, float* x, float* tmp, int planes, int H, int W, int wavelet, int levels, void* stream);
 

@@ -385,7 +385,6 @@ __global__ __launch_bounds__(256) void dwt2_stream_k(DwtFArgs a) {
 
 template <int WV>
 static void dwt_stream_launch(DwtFArgs a, int planes, bool keep, hipStream_t st) {
-  const int npl = a.w / 128;
   if (keep) {
     const size_t lds = ((size_t)(a.h / 2) * (a.w / 2) + (size_t)(a.h / 4) * (a.w / 4)) * sizeof(float);   // 80 KB at 256 x 256
     static const hipError_t once = hipFuncSetAttribute(reinterpret_cast<const void*>(&dwt2_stream_k<WV, 2, true>),
@@ -393,9 +392,10 @@ static void dwt_stream_launch(DwtFArgs a, int planes, bool keep, hipStream_t st)
     (void)once;
     hipLaunchKernelGGL((dwt2_stream_k<WV, 2, true>), dim3(1, 1, (unsigned)planes), dim3(256), lds, st, a);
   } else {
+    // streaming to memory happens for the first level of a 512-wide plane only (dwt_fwd_fast): 8 pixels per lane.  A 256-wide
+    // plane always keeps its LL band in LDS, so there is no <WV, 2, false> instance: nothing could reach or test it.
     dim3 grid(1, (unsigned)((a.h / 2) / 128), (unsigned)planes);
-    if (npl == 4) hipLaunchKernelGGL((dwt2_stream_k<WV, 4, false>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((dwt2_stream_k<WV, 2, false>), grid, dim3(256), 0, st, a);
+    hipLaunchKernelGGL((dwt2_stream_k<WV, 4, false>), grid, dim3(256), 0, st, a);
   }
 }
 
@@ -432,6 +432,7 @@ extern "C" int wtpse_dwt2_fwd(const float* x, float* coef, float* tmp, int plane
                               void* stream) {
   WTPSE_REQUIRE(x && coef && tmp && planes > 0 && planes <= 65535 && H > 0 && W > 0 && levels >= 1 && levels <= 12);
   WTPSE_REQUIRE((wavelet == 0 || wavelet == 1) && H % (1 << levels) == 0 && W % (1 << levels) == 0 && x != coef);
+  WTPSE_REQUIRE((((uintptr_t)x | (uintptr_t)coef | (uintptr_t)tmp) & 7) == 0);   // the generic kernels load and store float2
   hipStream_t st = (hipStream_t)stream;
   if (dwt_fast_shape(H, W, levels) && (((uintptr_t)x | (uintptr_t)coef | (uintptr_t)tmp) & 15) == 0) {
     if (wavelet == 0) dwt_fwd_fast<0>(x, coef, tmp, planes, H, W, levels, st);
@@ -461,6 +462,7 @@ extern "C" int wtpse_dwt2_inv(const float* coef, float* x, float* tmp, int plane
                               void* stream) {
   WTPSE_REQUIRE(x && coef && tmp && planes > 0 && planes <= 65535 && H > 0 && W > 0 && levels >= 1 && levels <= 12);
   WTPSE_REQUIRE((wavelet == 0 || wavelet == 1) && H % (1 << levels) == 0 && W % (1 << levels) == 0 && x != coef);
+  WTPSE_REQUIRE((((uintptr_t)x | (uintptr_t)coef | (uintptr_t)tmp) & 7) == 0);
   hipStream_t st = (hipStream_t)stream;
   const long long tplane = (long long)(H / 2) * (W / 2);
   float* tbuf[2] = {tmp, tmp + (size_t)planes * tplane};
