@@ -25,23 +25,14 @@ import numpy as np
 import torch
 
 HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [HERE, os.path.join(HERE, "wt-pse-code_amd"), os.path.join(HERE, "tests")]
+sys.path[:0] = [HERE, os.path.join(HERE, "wt-pse-code_amd"), os.path.join(HERE, "tests"), os.path.join(HERE, "tools")]
+
+from stage_bench import alternate, write_profile  # noqa: E402
 
 SHAPES = [("N = 30, 256 x 256, tiles (8, 8), luma", 30, 256, 256, (8, 8), "luma"),
           ("N = 1, 2048 x 2048, tiles (8, 8), luma", 1, 2048, 2048, (8, 8), "luma"),
           ("N = 1, 2048 x 2048, tiles (8, 8), rgb", 1, 2048, 2048, (8, 8), "rgb")]
 COPY = "device copy of the same bytes (`Tensor.copy_`)"
-
-
-def window(fn, inner):
-    """ms per call over `inner` back-to-back calls, between two device events."""
-    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    start.record()
-    for _ in range(inner):
-        fn()
-    end.record()
-    end.synchronize()
-    return start.elapsed_time(end) / inner
 
 
 def variants(N, H, W, tiles, mode):
@@ -107,14 +98,7 @@ def main():
          % (a.inner, a.inner, a.reps), "such windows, the variants of a shape alternating.", ""]
     for title, N, H, W, tiles, mode in SHAPES:
         fns, keep = variants(N, H, W, tiles, mode)
-        for fn in fns.values():                          # warm-up: code objects, allocator
-            for _ in range(5):
-                fn()
-        torch.cuda.synchronize()
-        times = {k: [] for k in fns}
-        for _ in range(a.reps):                          # alternating: other people's work shares the machine
-            for k, fn in fns.items():
-                times[k].append(window(fn, a.inner))
+        times = alternate(fns, a.reps, a.inner)
         copy = med(times[COPY])
         nbytes = N * H * W * 3
         L += ["## %s (%.1f MB read, as much written)" % (title, nbytes / 1e6), "", "| what | us per call | times the copy |", "| --- | --- | --- |"]
@@ -128,15 +112,7 @@ def main():
     for k, t in feed.items():
         L.append("| %s | %.2f (%.2f .. %.2f) |" % (k, 1e3 * med(t), 1e3 * min(t), 1e3 * max(t)))
     L.append("")
-    text = "\n".join(L)
-    marker = "## Reading the numbers"                # written by hand below the tables: a new run keeps it
-    if os.path.isfile(a.out):
-        old = open(a.out).read()
-        if marker in old:
-            text += old[old.index(marker):]
-    with open(a.out, "w") as f:
-        f.write(text)
-    print(text)
+    write_profile(a.out, L)
 
 
 if __name__ == "__main__":

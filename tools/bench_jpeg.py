@@ -22,20 +22,11 @@ import numpy as np
 import torch
 
 HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [HERE, os.path.join(HERE, "wt-pse-code_amd"), os.path.join(HERE, "tests")]
+sys.path[:0] = [HERE, os.path.join(HERE, "wt-pse-code_amd"), os.path.join(HERE, "tests"), os.path.join(HERE, "tools")]
+
+from stage_bench import alternate, write_profile  # noqa: E402
 
 B = 32
-
-
-def window(fn, inner):
-    """ms per call over `inner` back-to-back calls, between two device events."""
-    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    start.record()
-    for _ in range(inner):
-        fn()
-    end.record()
-    end.synchronize()
-    return start.elapsed_time(end) / inner
 
 
 def variants(S):
@@ -88,14 +79,7 @@ def main():
          "median, as a fraction of the copy's.", ""]
     for S in (256, 512):
         fns, keep = variants(S)
-        for fn, _ in fns.values():                    # warm-up: code objects, allocator
-            for _ in range(5):
-                fn()
-        torch.cuda.synchronize()
-        times = {k: [] for k in fns}
-        for _ in range(a.reps):                       # alternating: other people's work shares the machine
-            for k, (fn, _) in fns.items():
-                times[k].append(window(fn, a.inner))
+        times = alternate({k: fn for k, (fn, _) in fns.items()}, a.reps, a.inner)
         copy_key = "device copy of the batch (`Tensor.copy_`)"
         copy_rate = fns[copy_key][1] / med(times[copy_key])
         L += ["## S = %d" % S, "", "| what | us per call | times the copy | MB moved | rate / copy's rate |", "| --- | --- | --- | --- | --- |"]
@@ -106,15 +90,7 @@ def main():
         del fns, keep
     L += ["\"stage\" is `ops.jpeg_roundtrip` as the input pipeline calls it: the parameter checks on the host, three small uploads, the",
           "allocations, one or two launches.  \"launches alone\" has the tables on the device already.", ""]
-    text = "\n".join(L)
-    marker = "## Reading the numbers"                 # written by hand below the tables: a new run keeps it
-    if os.path.isfile(a.out):
-        old = open(a.out).read()
-        if marker in old:
-            text += old[old.index(marker):]
-    with open(a.out, "w") as f:
-        f.write(text)
-    print(text)
+    write_profile(a.out, L)
 
 
 if __name__ == "__main__":

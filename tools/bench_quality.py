@@ -21,20 +21,11 @@ import numpy as np
 import torch
 
 HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [HERE, os.path.join(HERE, "wt-pse-code_amd"), os.path.join(HERE, "tests")]
+sys.path[:0] = [HERE, os.path.join(HERE, "wt-pse-code_amd"), os.path.join(HERE, "tests"), os.path.join(HERE, "tools")]
+
+from stage_bench import alternate, write_profile  # noqa: E402
 
 B, S = 30, 256
-
-
-def window(fn, inner):
-    """ms per call over `inner` back-to-back calls, between two device events."""
-    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    start.record()
-    for _ in range(inner):
-        fn()
-    end.record()
-    end.synchronize()
-    return start.elapsed_time(end) / inner
 
 
 def variants():
@@ -75,14 +66,7 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("this measurement needs the MI355X (no fallback)")
     fns, keep = variants()
-    for fn in fns.values():                          # warm-up: code objects, allocator
-        for _ in range(5):
-            fn()
-    torch.cuda.synchronize()
-    times = {k: [] for k in fns}
-    for _ in range(a.reps):                          # alternating: other people's work shares the machine
-        for k, fn in fns.items():
-            times[k].append(window(fn, a.inner))
+    times = alternate(fns, a.reps, a.inner)
     med = statistics.median
     copy = med(times["device copy of the same bytes (`Tensor.copy_`)"])
     nbytes = B * S * S * 3
@@ -95,15 +79,7 @@ def main():
         L.append("| %s | %.1f (%.1f .. %.1f) | %.1f |" % (k, 1e3 * med(t), 1e3 * min(t), 1e3 * max(t), med(t) / copy))
     L += ["", "\"stage\" is `ops.image_quality` as the input pipeline calls it: the parameter checks on the host, two small uploads, the",
           "memset and the sums launch, the apply launch.  \"launch alone\" has the tables on the device already.", ""]
-    text = "\n".join(L)
-    marker = "## Reading the numbers"                # written by hand below the tables: a new run keeps it
-    if os.path.isfile(a.out):
-        old = open(a.out).read()
-        if marker in old:
-            text += old[old.index(marker):]
-    with open(a.out, "w") as f:
-        f.write(text)
-    print(text)
+    write_profile(a.out, L)
 
 
 if __name__ == "__main__":

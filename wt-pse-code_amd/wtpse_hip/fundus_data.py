@@ -8,7 +8,7 @@
     train phase: __getitem__ ignores its index and draws one with np.random.choice per pool       (:86-99)
 
 Host side and Python as in the reference (PNG decoding is PIL's on both sides); what it hands on are DECODED uint8 arrays, which
-`DeviceInputPipeline` (input_pipeline.py) turns into the fp32 batch on the GPU.  Kept quirks: the Domain-4 centre crop is dead
+`DeviceInputPipeline` (input_pipeline/pipeline.py) turns into the fp32 batch on the GPU.  Kept quirks: the Domain-4 centre crop is dead
 code in the reference (`self.splitid[0] == '4'` compares an int with a str, :180) and is not performed; empty pools are removed the
 reference's way — the first empty one, three times (:58-75) — so `dc` (the domain code) is the index among the pools that are left:
 0 for every single-domain dataset train.py builds; a file with an unknown prefix prints the reference's error line and STOPS the

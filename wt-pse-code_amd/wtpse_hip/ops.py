@@ -1517,6 +1517,19 @@ def paste_u8(canvas, patch, top, left):
     return canvas
 
 
+# ----------------------------------------------------------------------------------------------- input stages
+def _chk_stage_batch(img, who, side_max, square=True):
+    """What every input stage asks of its batch: a contiguous uint8 tensor in device memory, [N,S,S,3] (or [N,H,W,3] with
+    square=False), 1 <= N <= 65535 (a grid dimension), sides 1 .. side_max.  who: the wrapper's name, for the message.
+    -> (N, H, W)."""
+    _chk_u8(img, "img", 4)
+    N, H, W, C = (int(s) for s in img.shape)
+    if C != 3 or (square and H != W) or not 1 <= N <= 65535 or not (1 <= H <= side_max and 1 <= W <= side_max):
+        raise ValueError("%s: img must be [N,%s,3] with 1 <= N <= 65535 and sides in 1 .. %d (got %s)"
+                         % (who, "S,S" if square else "H,W", side_max, tuple(img.shape)))
+    return N, H, W
+
+
 # ----------------------------------------------------------------------------------------------- amplitude mixing
 _TWIDDLES = {}
 
@@ -1525,19 +1538,10 @@ def amplitude_mix(img, partner, lam, b, want_float=False):
     """[N,S,S,3] uint8 on the device, partner [N] int (-1: leave the row alone) and lam [N] float on the host, b = half width of the
     frequency window -> the batch with the amplitude of every row that has a partner moved towards its partner's (csrc/spectrum.hip;
     input_pipeline.amplitude_mix_host is the specification); with want_float also the unrounded fp32 values [N,S,S,3]."""
-    from .input_pipeline import _check_mix_size, twiddle_table
+    from .input_pipeline.amplitude_mix import MIX_SIZES, check_mix_params, twiddle_table
     import numpy as np
-    _chk_u8(img, "img", 4)
-    N, S = int(img.shape[0]), int(img.shape[1])
-    if img.shape[2] != S or img.shape[3] != 3 or not 1 <= N <= 65535:
-        raise ValueError("amplitude_mix: img must be [N,S,S,3] with 1 <= N <= 65535 (got %s)" % (tuple(img.shape),))
-    _check_mix_size(S)
-    b = int(b)
-    partner, lam = np.asarray(partner), np.asarray(lam, np.float64)
-    if partner.shape != (N,) or lam.shape != (N,) or partner.dtype.kind not in "iu" or not np.all(np.isfinite(lam)):
-        raise ValueError("amplitude_mix: partner must be [%d] integers and lam [%d] finite floats" % (N, N))
-    if partner.min() < -1 or partner.max() >= N or not 0 <= b <= S // 2:
-        raise ValueError("amplitude_mix: partner indices must lie in -1 .. %d and b in 0 .. %d (got b = %r)" % (N - 1, S // 2, b))
+    N, S, _ = _chk_stage_batch(img, "amplitude_mix", MIX_SIZES[-1])
+    partner, lam, b = check_mix_params(partner, lam, b, N, S)
     nfloats = lib().query("wtpse_amix_workspace", N, S, b)
     if nfloats < 0:
         raise ValueError("amplitude_mix: a [%d,%d,%d,3] batch with b = %d needs more workspace than one call can take" % (N, S, S, b))
@@ -1560,7 +1564,7 @@ _APPEARANCE_TABLES = {}
 
 def appearance_axis(S, spacing, device):
     """The stage's axis table [S,5] int32 on `device` (input_pipeline.appearance_axis_table), kept per (S, spacing, device)."""
-    from .input_pipeline import appearance_axis_table
+    from .input_pipeline.appearance import appearance_axis_table
     import numpy as np
     key = (int(S), int(spacing), str(device))
     t = _APPEARANCE_TABLES.get(key)
@@ -1575,13 +1579,9 @@ def appearance_nets(img, params, field, spacing):
     """[N,S,S,3] uint8 on the device, (params [N,389], field [N,G,G]) integers on the host (input_pipeline.draw_appearance) and the
     field's spacing -> the batch after the random appearance networks, a new tensor (csrc/appearance.hip: the nets tile by tile in
     LDS, then scaling and blend; input_pipeline.appearance_host is the specification, byte for byte).  The input is not written."""
-    from .input_pipeline import APPEARANCE_MAX_SIZE, appearance_grid, check_appearance_params
+    from .input_pipeline.appearance import APPEARANCE_MAX_SIZE, appearance_grid, check_appearance_params
     import numpy as np
-    _chk_u8(img, "img", 4)
-    N, S = int(img.shape[0]), int(img.shape[1])
-    if img.shape[2] != S or img.shape[3] != 3 or not 1 <= N <= 65535 or not 1 <= S <= APPEARANCE_MAX_SIZE:
-        raise ValueError("appearance_nets: img must be [N,S,S,3] with 1 <= N <= 65535 and 1 <= S <= %d (got %s)"
-                         % (APPEARANCE_MAX_SIZE, tuple(img.shape)))
+    N, S, _ = _chk_stage_batch(img, "appearance_nets", APPEARANCE_MAX_SIZE)
     params, field = check_appearance_params(params, field, N, S, spacing)
     words = lib().query("wtpse_appearance_workspace", N, S)
     if words < 0:
@@ -1606,13 +1606,9 @@ def image_quality(img, params, seed, pos, want_pos=False):
     input_pipeline.draw_quality), the noise stream `seed` from position `pos` on -> the batch after focus, contrast, brightness and
     noise (csrc/quality.hip; input_pipeline.quality_host is the specification, byte for byte); with want_pos also the stream
     position behind the batch (S * S positions per sample with k > 0).  The input is not written."""
-    from .input_pipeline import QUALITY_MAX_SIZE, check_quality_params, quality_positions
+    from .input_pipeline.quality import QUALITY_MAX_SIZE, check_quality_params, quality_positions
     import numpy as np
-    _chk_u8(img, "img", 4)
-    N, S = int(img.shape[0]), int(img.shape[1])
-    if img.shape[2] != S or img.shape[3] != 3 or not 1 <= N <= 65535 or not 1 <= S <= QUALITY_MAX_SIZE:
-        raise ValueError("image_quality: img must be [N,S,S,3] with 1 <= N <= 65535 and 1 <= S <= %d (got %s)"
-                         % (QUALITY_MAX_SIZE, tuple(img.shape)))
+    N, S, _ = _chk_stage_batch(img, "image_quality", QUALITY_MAX_SIZE)
     seed, pos = int(seed), int(pos)
     if not 0 <= seed < 1 << 64 or not 0 <= pos < 1 << 62:
         raise ValueError("image_quality: seed must lie in 0 .. 2^64 - 1 and pos in 0 .. 2^62 - 1 (got %r, %r)" % (seed, pos))
@@ -1636,13 +1632,9 @@ def jpeg_roundtrip(img, mode, tables):
     the batch after baseline JPEG's round trip of the pixels, a new tensor (csrc/jpeg.hip; input_pipeline.jpeg_host is the
     specification, byte for byte, and is pinned to Pillow).  A batch whose modes are all 0 launches nothing and returns `img`
     itself.  The input is not written."""
-    from .input_pipeline import JPEG_MAX_SIZE, _check_jpeg_size, check_jpeg_params, jpeg_is_neutral, jpeg_reciprocals
+    from .input_pipeline.jpeg import JPEG_MAX_SIZE, _check_jpeg_size, check_jpeg_params, jpeg_is_neutral, jpeg_reciprocals
     import numpy as np
-    _chk_u8(img, "img", 4)
-    N, S = int(img.shape[0]), int(img.shape[1])
-    if img.shape[2] != S or img.shape[3] != 3 or not 1 <= N <= 65535:
-        raise ValueError("jpeg_roundtrip: img must be [N,S,S,3] with 1 <= N <= 65535 and S a multiple of 16 up to %d (got %s)"
-                         % (JPEG_MAX_SIZE, tuple(img.shape)))
+    N, S, _ = _chk_stage_batch(img, "jpeg_roundtrip", JPEG_MAX_SIZE)
     _check_jpeg_size(S)
     mode, tables = check_jpeg_params(mode, tables, N)
     if jpeg_is_neutral(mode).all():
@@ -1667,7 +1659,7 @@ _CLAHE_TABLES = {}
 
 def clahe_tables(H, W, clahe, device):
     """The stage's two axis tables on `device` (input_pipeline.clahe_device_tables), kept per (H, W, tiles, device)."""
-    from .input_pipeline import clahe_device_tables
+    from .input_pipeline.clahe import clahe_device_tables
     key = (int(H), int(W), clahe.tiles, str(device))
     t = _CLAHE_TABLES.get(key)
     if t is None:
@@ -1681,14 +1673,9 @@ def clahe(img, clahe, want_luts=False):
     """[N,H,W,3] uint8 on the device and an input_pipeline.Clahe -> the equalised batch, a new tensor (csrc/clahe.hip: tile
     histograms, clipped LUTs, bilinear blend; input_pipeline.clahe_host is the specification, byte for byte); with want_luts also
     the tile LUTs [N,P,ty,tx,256] uint8.  The input is not written.  No draws: the same bytes on every call."""
-    from .input_pipeline import CLAHE_MAX_SIDE, Clahe
-    _chk_u8(img, "img", 4)
-    if not isinstance(clahe, Clahe):
-        raise ValueError("clahe: the parameters must be an input_pipeline.Clahe (got %r)" % (clahe,))
-    N, H, W, C = (int(s) for s in img.shape)
-    if C != 3 or not 1 <= N <= 65535 or not (1 <= H <= CLAHE_MAX_SIDE and 1 <= W <= CLAHE_MAX_SIDE):
-        raise ValueError("clahe: img must be [N,H,W,3] with 1 <= N <= 65535 and 1 <= H, W <= %d (got %s)" % (CLAHE_MAX_SIDE, tuple(img.shape)))
-    clahe.check_size(H, W)
+    from .input_pipeline.clahe import CLAHE_MAX_SIDE, check_clahe
+    N, H, W = _chk_stage_batch(img, "clahe", CLAHE_MAX_SIDE, square=False)
+    check_clahe(clahe, H, W)
     (ty, tx), P, dev = clahe.tiles, clahe.planes, img.device
     rows, cols, bands = clahe_tables(H, W, clahe, dev)
     hist = torch.empty((N, P, ty, tx, 256), dtype=torch.int32, device=dev)

@@ -88,67 +88,38 @@ class FundusBatches:
     running position, which is feed state as well: `state()` carries it as "noise_pos", and a state saved before the field existed
     loads with position 0.
 
-    style: an `input_pipeline.AmplitudeMix` switches the amplitude-mixing stage on (None: off — not one launch, allocation or draw
-    is added).  A batch is assembled domain-major, so every sample has partners from the other domains next to it; the stage's
-    draws (`draw_mix`) come from the numpy generator AFTER all of the batch's other draws: every stream is what it is without the
-    stage up to that point.  The stage keeps no state of its own — the generator, which TrainRun's checkpoints carry, is all of it.
-    It needs at least two source domains and a side that is a power of two from 32 to 512 (ValueError here).
-
-    quality: an `input_pipeline.ImageQuality` switches the image-quality stage on (None: off — not one launch, allocation or draw is
-    added): blur or sharpening, contrast, brightness and noise on the uint8 batch, after the other two stages.  Its draws
-    (`draw_quality`) come from the numpy generator AFTER all of the batch's other draws, amplitude mixing included: every stream is
-    what it is without the stage up to that point.  Its noise comes from the device Philox stream `set_seed` sets (blocks of their
-    own) at a running position, which is feed state: `state()` carries it as "quality_pos" when the stage is on, and a state saved
-    without the field loads with position 0.
-
-    appearance: an `input_pipeline.AppearanceNets` switches the random appearance networks on (None: off — not one launch,
-    allocation or draw is added): every selected sample is remapped by shallow convolutional networks drawn for it alone (GIN / IPA),
-    after amplitude mixing and before the image-quality stage.  Its draws (`draw_appearance`) come from the numpy generator AFTER all
-    of the batch's other draws, the image-quality stage's included.  The stage reads no device random stream: the generator, which
-    TrainRun's checkpoints carry, is all of its state, and `state()` has no entry for it.  Side 1 .. 512 (ValueError here).  Its
-    effect on the Dice / HD95 of a held-out domain has not been measured.
-
-    clahe: an `input_pipeline.Clahe` switches the CLAHE preprocessing on (None: off — not one launch or allocation is added): the
-    uint8 batch is equalised after every other stage and immediately before the normalisation.  It draws nothing and adds no feed
-    state; it is a preprocessing step, so whatever reads the run's checkpoints must apply the same one: TrainRun writes
-    `clahe.record()` into every checkpoint as "clahe" (`clahe_record()` is what it asks the feed for).
-
-    jpeg: an `input_pipeline.JpegCompression` switches the JPEG compression stage on (None: off — not one launch, allocation or draw
-    is added): every selected sample goes through baseline JPEG's round trip of the pixels at a drawn quality, 4:2:0 or 4:4:4, after
-    the image-quality stage and before CLAHE.  Its draws (`draw_jpeg`) come from the numpy generator AFTER all of the batch's other
-    draws, the appearance networks' included.  The stage reads no device random stream: the generator, which TrainRun's checkpoints
-    carry, is all of its state, and `state()` has no entry for it.  The side must be a multiple of 16 (ValueError here).  It is a
-    training augmentation only; its effect on the Dice / HD95 of a held-out domain has not been measured."""
+    style, appearance, quality, jpeg, clahe: one keyword per optional stage behind the augmentations (`input_pipeline.stages`), each
+    taking that stage's config — `AmplitudeMix`, `AppearanceNets`, `ImageQuality`, `JpegCompression`, `Clahe` — or None: the stage
+    is off, and not one launch, allocation or draw is added.  A config of another type or one that does not take the side is a
+    ValueError here.  The stages run in `stages.RUN_ORDER` and draw, from the numpy generator AFTER all of the batch's other draws,
+    in `stages.DRAW_ORDER` — the order in which they were added, so that every stream is what it is without the stages behind it.
+    The generator, which TrainRun's checkpoints carry, is all the state they have, with one exception.  Particular to a stage:
+      * style: a batch is assembled domain-major, so every sample has partners from the other domains next to it; it needs at least
+        two source domains and a side that is a power of two from 32 to 512.
+      * quality: its noise comes from the device Philox stream `set_seed` sets (blocks of their own) at a running position, which is
+        feed state: `state()` carries it as "quality_pos" when the stage is on, and a state saved without the field loads with
+        position 0.
+      * appearance (side 1 .. 512) and jpeg (a side that is a multiple of 16) are training augmentations whose effect on the Dice /
+        HD95 of a held-out domain has not been measured.
+      * clahe draws nothing; it is a preprocessing step, so whatever reads the run's checkpoints must apply the same one: TrainRun
+        writes `clahe.record()` into every checkpoint as "clahe" (`clahe_record()` is what it asks the feed for)."""
 
     def __init__(self, datasets, batch_size, device, size=256, augment=None, pipe=None, style=None, quality=None, clahe=None,
                  appearance=None, jpeg=None):
-        from .input_pipeline import (QUALITY_MAX_SIZE, AppearanceNets, Clahe, DeviceInputPipeline, JpegCompression,
-                                     _check_appearance_size, _check_jpeg_size, _check_mix_size)
+        from .input_pipeline import DeviceInputPipeline
+        from .input_pipeline.stages import RUN_ORDER
         self.augment = augment
-        if jpeg is not None:
-            if not isinstance(jpeg, JpegCompression):
-                raise ValueError("jpeg must be an input_pipeline.JpegCompression or None, got %r" % (jpeg,))
-            _check_jpeg_size(int(size))
-        self.jpeg = jpeg
-        self.style = style
-        self.quality = quality
-        if appearance is not None:
-            if not isinstance(appearance, AppearanceNets):
-                raise ValueError("appearance must be an input_pipeline.AppearanceNets or None, got %r" % (appearance,))
-            _check_appearance_size(int(size), appearance.spacing)
-        self.appearance = appearance
-        if clahe is not None:
-            if not isinstance(clahe, Clahe):
-                raise ValueError("clahe must be an input_pipeline.Clahe or None, got %r" % (clahe,))
-            clahe.check_size(int(size), int(size))
-        self.clahe = clahe
-        if quality is not None and not 1 <= int(size) <= QUALITY_MAX_SIZE:
-            raise ValueError("the image-quality stage takes samples of side 1 .. %d, got %r" % (QUALITY_MAX_SIZE, size))
         self.datasets = list(datasets)
-        if style is not None:
-            if len(self.datasets) < 2:
-                raise ValueError("amplitude mixing needs at least two source domains, got %d" % len(self.datasets))
-            _check_mix_size(int(size))
+        if style is not None and len(self.datasets) < 2:
+            raise ValueError("amplitude mixing needs at least two source domains, got %d" % len(self.datasets))
+        given = {"style": style, "appearance": appearance, "quality": quality, "jpeg": jpeg, "clahe": clahe}
+        for stage in RUN_ORDER:
+            config = given[stage.feed_kw]
+            if config is not None:
+                if not isinstance(config, stage.config):
+                    raise ValueError("%s must be an input_pipeline.%s or None, got %r" % (stage.feed_kw, stage.config.__name__, config))
+                stage.check_size(int(size), config)
+            setattr(self, stage.feed_kw, config)
         self.order = list(range(len(self.datasets)))
         # Trainer.py:1011: per_domain_batch = batch_size // source_domain_num — a batch holds domains * per_domain samples
         # (30 for the reference's batch_size 32 over three source domains)
@@ -170,8 +141,6 @@ class FundusBatches:
         if self.augment is None:
             images, masks = multi_batch([self.datasets[i] for i in self.order], self.per_domain, np_rng)
             draws = [draw(py_rng, self.size) for _ in images]
-            if self.style is None and self.quality is None and self.clahe is None and self.appearance is None and self.jpeg is None:
-                return self.pipe(images, masks, draws)
             return self.pipe(images, masks, draws, **self._stage_draws(np_rng, len(images)))
         images, masks, draws, aug_draws = [], [], [], []
         for i in self.order:
@@ -181,36 +150,16 @@ class FundusBatches:
                 masks += mask
                 draws.append(draw(py_rng, self.size))
                 aug_draws.append(draw_augment(py_rng, np_rng, self.size, self.augment))
-        if self.style is None and self.quality is None and self.clahe is None and self.appearance is None and self.jpeg is None:
-            return self.pipe(images, masks, draws, aug_draws)
         return self.pipe(images, masks, draws, aug_draws, **self._stage_draws(np_rng, len(images)))
 
     def _stage_draws(self, np_rng, n):
-        """The draws of the stages behind the augmentations: amplitude mixing, then image quality, then — drawn last, although the
-        stage runs in front of image quality — the appearance networks: the stages that were there before it draw what they drew
-        without it — and after them, for the same reason, the JPEG stage.  CLAHE, the last stage, draws nothing and rides along."""
-        from .input_pipeline import draw_appearance, draw_jpeg, draw_quality
-        kw = {}
-        if self.style is not None:
-            kw["mix_draws"] = self._mix_draws(np_rng)
-        if self.quality is not None:
-            kw["quality_draws"] = draw_quality(np_rng, n, self.quality)
-        if self.clahe is not None:
-            kw["clahe"] = self.clahe
-        if self.appearance is not None:
-            kw["appearance_draws"] = draw_appearance(np_rng, n, self.size, self.appearance) + (self.appearance.spacing,)
-        if self.jpeg is not None:
-            kw["jpeg_draws"] = draw_jpeg(np_rng, n, self.jpeg)
-        return kw
+        """The pipeline keywords of the stages that are on, drawn in `stages.DRAW_ORDER` (which says why it is not the run order)."""
+        from .input_pipeline.stages import DRAW_ORDER
+        return {stage.pipe_kw: stage.draw(np_rng, n, self) for stage in DRAW_ORDER if getattr(self, stage.feed_kw) is not None}
 
     def clahe_record(self):
         """The feed's preprocessing as a checkpoint carries it: `Clahe.record()`, or None without the stage."""
         return None if self.clahe is None else self.clahe.record()
-
-    def _mix_draws(self, np_rng):
-        from .input_pipeline import draw_mix
-        partner, lam = draw_mix(np_rng, len(self.datasets), self.per_domain, self.style)
-        return partner, lam, self.style.band(self.size)
 
     def set_seed(self, seed):
         """The seed of the device noise stream — the elastic transform's fields and the image-quality stage's noise (TrainRun calls
