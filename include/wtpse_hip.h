@@ -833,6 +833,29 @@ int wtpse_crop_u8(const unsigned char* img, const int* boxes, unsigned char* out
  * 1 <= H, W, h, w <= 65536, |top|, |left| <= 2^24; canvas and patch distinct. */
 int wtpse_paste_u8(unsigned char* canvas, const unsigned char* patch, int H, int W, int C, int h, int w, int top, int left, void* stream);
 
+/* ---- gradability check (csrc/gradability.hip; gradability.record_host is the specification, bit for bit) -------------------------
+ * One exact-integer pass over the full-size pictures.  img [N][H][W][3] uint8 (interleaved RGB, any base alignment) -> rec
+ * [N][WTPSE_GRAD_REC] int64, initialised on the stream first.  Per picture, with
+ *   field    f(p) = max(R, G, B) >= t; a position outside the picture is not in the field (wtpse_locate_cells' definition; t = 0: every
+ *            pixel of the picture)
+ *   luma     Y = (77 R + 150 G + 29 B + 128) >> 8, in 0..255
+ * the record is
+ *   rec[0 .. 255]           the histogram of Y over the field
+ *   rec[256 .. 258]         the sums of R, G, B over the field
+ *   rec[259 .. 261]         the field pixels with R, G, B >= sat, per channel
+ *   rec[262]                the field's area n
+ *   rec[263 .. 266]         top, bottom, left, right of the field's bounding box; (H, -1, W, -1) for an empty field
+ *   rec[267 + 3k .. 269 + 3k]   (n_d, E_d, Q_d) for the k-th dilation d of (1, 2, 4)
+ * For a dilation d a pixel p is interior when p and its four neighbours at distance d along the rows and the columns all lie in the
+ * picture and in the field; over the interior pixels, on the green channel G,
+ *   L = 4 G(p) - G(up) - G(down) - G(left) - G(right),   E_d = sum L^2,   Q_d = sum (G(right) - G(left))^2 + (G(down) - G(up))^2,
+ * and n_d is their number.  L^2 <= 1020^2, so a 65536 x 65536 picture stays below 2^53; the sums are 64-bit.  Integer arithmetic only,
+ * the workgroups' partial records meet in the picture's with 64-bit integer atomics: exact and the same on every run; nothing is
+ * allocated, no host synchronisation.  Nothing outside the 16-byte-aligned hull of img is read.
+ * 1 <= N <= 65535, 1 <= H, W <= 65536, 0 <= t <= 255, 1 <= sat <= 255; rec 8-byte aligned. */
+#define WTPSE_GRAD_REC 276
+int wtpse_gradability_record(const unsigned char* img, long long* rec, int N, int H, int W, int t, int sat, void* stream);
+
 /* ---- calibration against labels (csrc/calibration.hip; calibration.hist_host is the specification, bit for bit) ----------------
  * One pass over a probability map prob, a spread map spread (NULL: every spread is 0) and a label (nonzero = object, as
  * wtpse_seg_metrics takes it; y = 1 for an object pixel, else 0), all [B][h][w] fp32, optionally restricted to the pixels where

@@ -12,6 +12,11 @@ unchanged `segment.Segmenter`.  segment.py starts from crops somebody made; this
     O/full_overlay/<stem>.png   the photograph with the crop's contour overlay at the box (--no-full or --no-overlay: not written)
     O/mask, O/overlay, O/measurements.csv, ... everything segment.py writes for the folder O/crop, in the crop's frame
     O/summary.json           segment's, plus n_located, n_verified, n_not_located
+    O/gradability.csv        with --gradability only (gradability.py): per input image, located or not, the focus, exposure and field
+                             measures of the photograph (photo_*: ops.gradability_record at --fov-threshold in the visit that makes the
+                             cell table, the illumination figures from that table) and of its final crop (roi_*: every pixel in the
+                             field), the flags of the thresholds given — they judge the photograph — and focus_rank; summary.json gains
+                             gradability.  roi.csv and every other file are the same with and without it
 
 1. Cell sums (`ops.locate_cells`, csrc/locate.hip; `cells_host` is the specification, bit for bit): per c x c cell the count n of the
    pixels with max(R,G,B) >= fov_threshold and the sum s of 77 R + 150 G + 29 B over them.  This is the only pass over the full-size
@@ -41,6 +46,7 @@ import os
 import numpy as np
 import torch
 
+from . import gradability as GR
 from . import ops
 from . import tables as T
 from . import validate as V
@@ -235,7 +241,7 @@ class Locator:
     [B,1,S,S]` is the disc network (model.predict(model_shape, image)[0]); the caller holds the networks in eval mode."""
 
     def __init__(self, model, model_shape, candidates=3, refine=1, disc_scale=0.13, roi_scale=0.4, roi_side=None, cell="auto",
-                 fov_threshold=24, min_area=0.01, max_area=0.5, batch_size=9, size=256, clahe=None):
+                 fov_threshold=24, min_area=0.01, max_area=0.5, batch_size=9, size=256, clahe=None, gradability=None):
         if int(candidates) < 1 or int(refine) < 0 or int(batch_size) < 1:
             raise ValueError("candidates and batch_size must be positive and refine must not be negative")
         if cell != "auto" and not 2 <= int(cell) <= 256:
@@ -252,6 +258,9 @@ class Locator:
         # on the full photograph is not)
         self._front = Segmenter(None, None, None, None, out_dir=None, size=size, clahe=clahe)
         self.seconds = None                                 # {"cells", "verify", "refine"} when timing is on (tools/bench_locate.py)
+        # a gradability.Gradability: `locate` also takes the photographs' records (ops.gradability_record at the field threshold) in
+        # the visit that makes the cell tables and leaves their measures, one per picture of the stack, in `photo_measures`
+        self.gradability, self.photo_measures = gradability, None
 
     def stage1(self, image):
         with torch.no_grad():
@@ -298,9 +307,12 @@ class Locator:
         N, H, W, _ = stack.shape
         dev, S = stack.device, self.size
         t0 = self._now()
-        plans = []
-        for cells, c in self.cell_tables(stack):
+        plans, tables = [], self.cell_tables(stack)
+        for cells, c in tables:
             plans.append(None if cells is None else plan(cells, c, self.count, self.disc_scale, self.roi_scale, self.roi_side))
+        if self.gradability is not None:
+            rec = ops.gradability_record(stack, self.t, self.gradability.sat).cpu().numpy()
+            self.photo_measures = [self.gradability.measures(rec[i], cells, c or None) for i, (cells, c) in enumerate(tables)]
         t0 = self._tick("cells", t0)
         rows, crops = [_blank_row(H, W) for _ in range(N)], [None] * N
         live = [i for i in range(N) if plans[i] is not None and plans[i]["candidates"]]
@@ -370,13 +382,20 @@ class WholeImageSegmenter:
     def __init__(self, model, model_shape, model_oc, model_shape_oc, out_dir, full=True, chunk=4, **kw):
         loc = {k: kw.pop(k) for k in self.LOCATOR_KEYS if k in kw}
         self.segmenter = Segmenter(model, model_shape, model_oc, model_shape_oc, out_dir=out_dir, **kw)
+        # gradability (a Segmenter keyword): the segmenter scores the crops, the locator the photographs, and `run` joins the two
+        self.gradability = self.segmenter.gradability
+        self.segmenter.write_gradability = False
+        if self.gradability is not None:
+            loc["gradability"] = self.gradability
         self.locator = Locator(model, model_shape, batch_size=self.segmenter.batch_size, size=self.segmenter.size,
                                clahe=self.segmenter.clahe, **loc)
         self.out_dir, self.full, self.chunk, self.roi_rows = out_dir, bool(full), max(1, int(chunk)), []
+        self.photo_measures, self.grad_rows = [], []
 
     def _locate_all(self, folder, device):
         from PIL import Image
         rows, crops = [None] * len(folder), [None] * len(folder)
+        self.photo_measures = [None] * len(folder)
         os.makedirs(os.path.join(self.out_dir, "crop"), exist_ok=True)
         for first in range(0, len(folder), self.chunk):
             idx = list(range(first, min(first + self.chunk, len(folder))))
@@ -388,6 +407,8 @@ class WholeImageSegmenter:
                 for p, row, crop in zip(pos, got_rows, got_crops):
                     i = idx[p]
                     rows[i], crops[i] = dict(row, index=i + 1, name=folder.names[i]), crop
+                    if self.gradability is not None:
+                        self.photo_measures[i] = self.locator.photo_measures[p]
                     if crop is not None:
                         Image.fromarray(next(host)).save(os.path.join(self.out_dir, "crop", folder.names[i]))
         return rows, crops
@@ -418,6 +439,23 @@ class WholeImageSegmenter:
                     if overlay:
                         Image.fromarray(host_photos[0][j]).save(os.path.join(self.out_dir, "full_overlay", name))
 
+    def _write_gradability(self, rows, found):
+        """gradability.csv: per input picture its photograph-level measures (photo_*) and those of its final crop as the segmenter
+        took them (roi_*; a picture that was not located: an empty record's), the flags — they judge the photograph — and
+        focus_rank by photo_focus_ratio.  -> summary.json's entry."""
+        G = self.gradability
+        blank = G.measures(np.zeros(GR.GRAD_REC, np.int64))
+        roi = dict(zip(found, self.segmenter.grad_rows))
+        table = []
+        for i, r in enumerate(rows):
+            row = {"index": r["index"], "name": r["name"]}
+            row.update({"photo_" + k: self.photo_measures[i][k] for k in GR.MEASURES})
+            row.update({"roi_" + k: roi.get(i, blank)[k] for k in GR.MEASURES})
+            table.append(row)
+        self.grad_rows = GR.finish_rows(table, G, ("photo_", "roi_"))
+        GR.write_csv(self.out_dir, self.grad_rows, ("photo_", "roi_"))
+        return GR.summarise(self.grad_rows, G)
+
     def run(self, folder):
         if not isinstance(folder, ImageFolder):
             folder = ImageFolder(folder)
@@ -433,6 +471,8 @@ class WholeImageSegmenter:
         self.roi_rows = rows
         write_roi_csv(self.out_dir, rows)
         summary = dict(summary, n_located=len(found), n_verified=sum(1 for r in rows if r["verified"] == 1), n_not_located=len(rows) - len(found))
+        if self.gradability is not None:
+            summary = dict(summary, gradability=self._write_gradability(rows, found))
         T.write_json(os.path.join(self.out_dir, "summary.json"), summary, allow_nan=False)
         if self.full and found:
             self._write_full(folder, rows, device)

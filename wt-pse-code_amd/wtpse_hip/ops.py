@@ -1482,6 +1482,28 @@ def locate_cells(img, c, t):
     return out
 
 
+GRAD_REC = 276
+
+
+def gradability_record(img, t=24, sat=250):
+    """[N,H,W,3] (or [H,W,3]) uint8 on the device -> int64 [N, GRAD_REC] (N = 1 for one picture): per picture the luma histogram,
+    channel sums, saturation counts, area and bounding box of its field (max(R,G,B) >= t) and the Laplacian / gradient energies of
+    the green channel at the dilations 1, 2, 4 (csrc/gradability.hip; gradability.record_host bit for bit, gradability.split_record
+    names the parts)."""
+    if isinstance(img, torch.Tensor) and img.dim() == 3:
+        img = img[None]
+    _chk_u8(img, "img", 4)
+    N, H, W, C = img.shape
+    t, sat = int(t), int(sat)
+    if C != 3 or not (1 <= N <= 65535 and 1 <= H <= 65536 and 1 <= W <= 65536):
+        raise ValueError("gradability_record: img must be [N,H,W,3] with 1 <= H, W <= 65536 (got %s)" % (tuple(img.shape),))
+    if not 0 <= t <= 255 or not 1 <= sat <= 255:
+        raise ValueError("gradability_record: the threshold must lie in 0..255 and sat in 1..255 (got %r, %r)" % (t, sat))
+    rec = torch.empty((N, GRAD_REC), dtype=torch.int64, device=img.device)
+    lib().call("wtpse_gradability_record", ptr(img), ptr(rec), N, H, W, t, sat, stream_ptr())
+    return rec
+
+
 def crop_u8(img, boxes, side):
     """One [H,W,C] uint8 picture (C = 1 or 3) and boxes [M,2] int32 = (top, left), both on the device -> [M,side,side,C]: the boxes'
     pixels, 0 beyond the picture's borders (locate.crop_host bit for bit)."""

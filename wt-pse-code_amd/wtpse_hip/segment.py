@@ -4,7 +4,7 @@ cup-to-disc ratios.  The test run (test_run.py) scores a labelled split; this is
 
     python -m wtpse_hip.segment --images DIR --checkpoint C --out O [--batch-size 9] [--no-overlay] [--samples K --seed S --sample-scale X]
                                 [--morphometry [--sectors N] [--eye right|left]] [--views none|id|hflip|flips|d4|<codes>]
-                                [--adapt none|batch|stream [--prior 16]]
+                                [--adapt none|batch|stream [--prior 16]] [--gradability [--min-focus-ratio X ...]]
 
     O/mask/<stem>.png        mode 'L', the image's own size, grey levels 0 (cup) / 128 (disc) / 255 (background): the dataset's
                              label encoding — FundusTree and FundusTestBatches read it as a label
@@ -54,6 +54,17 @@ images' own statistics blended with the checkpoint's (adapt.py): per network bat
 predictions then depend on the images that share the batch (and, for stream, on those before it); --adapt stream refuses --views,
 whose every view would be pooled as one more image.  summary.json gains adapt and prior.  A checkpoint from wtpse_hip.adapt needs no switch.
 
+With --gradability (Segmenter(gradability=Gradability(...)); off, the default, changes nothing and writes none of these) every decoded
+image, at its own size and while `front` has it on the device, also goes through ops.gradability_record (every pixel in the field:
+t = 0) and ops.locate_cells at the cell side gradability.crop_cell(h, w); gradability.py finishes the records:
+
+    O/gradability.csv        gradability.columns(): focus, exposure and field measures per image, then the flags of the thresholds
+                             given (--min-focus, --min-focus-ratio, --max-dark, --max-bright, --max-cv, --min-fov-fill; none by
+                             default, on purpose), then focus_rank, the image's percentile rank by focus_ratio within the run
+    O/summary.json           gains gradability: the thresholds and levels, n_judged, n_gradable
+
+The masks and measurements.csv are the same with and without it.
+
 Front (`Segmenter.front`): the decoded uint8 images go to the GPU as they are; the LANCZOS resize to 256 x 256 — FundusTree's
 Image.resize((S, S), Image.LANCZOS), bit for bit — is two passes of wtpse_resample_u8 with `resample_table(..., "lanczos")`, batched
 over the images of one size, a pass whose axis already has the target length skipped as Pillow skips it; wtpse_image_finish
@@ -75,6 +86,7 @@ import numpy as np
 import torch
 
 from . import adapt as A
+from . import gradability as GR
 from . import morphometry as M
 from . import ops
 from . import tables as T
@@ -216,7 +228,13 @@ class Segmenter:
     input, hence the equalised picture."""
 
     def __init__(self, model, model_shape, model_oc, model_shape_oc, out_dir, batch_size=9, overlay=True, size=256, samples=0, seed=0,
-                 scale=1.0, morphometry=False, sectors=24, eye=None, views=None, adapt=None, prior=A.DEFAULT_PRIOR, clahe=None):
+                 scale=1.0, morphometry=False, sectors=24, eye=None, views=None, adapt=None, prior=A.DEFAULT_PRIOR, clahe=None,
+                 gradability=None):
+        if gradability is not None and not isinstance(gradability, GR.Gradability):
+            raise ValueError("gradability must be a gradability.Gradability or None, got %r" % (gradability,))
+        # (None, the default: nothing changes.  write_gradability: finish() writes gradability.csv — locate.py, which joins these rows
+        # to the photographs', turns it off)
+        self.gradability, self.write_gradability, self.grad_rows, self._grad_pending = gradability, True, [], []
         if clahe is not None:
             from .input_pipeline import Clahe
             if not isinstance(clahe, Clahe):
@@ -282,6 +300,9 @@ class Segmenter:
                 t = torch.stack([images[i] if isinstance(images[i], torch.Tensor) else torch.from_numpy(images[i]).to(dev) for i in idx])
             else:
                 t = torch.from_numpy(np.stack([images[i] for i in idx])).to(dev)
+            if self.gradability is not None:                           # the decoded pictures at their own size, every pixel in the field
+                c = GR.crop_cell(H, W)
+                self._grad_pending.append((idx, c, ops.gradability_record(t, 0, self.gradability.sat), ops.locate_cells(t, c, 0)))
             if W != S:
                 t = self._lanczos_pass(t, False)
             if H != S:
@@ -294,6 +315,20 @@ class Segmenter:
         if self.clahe is not None:
             small = ops.clahe(small, self.clahe)
         return ops.image_finish(small)
+
+    def take_gradability(self, names):
+        """What the `front` calls since the last take left on the device (one copy) -> the images' gradability.csv rows without flags
+        and rank, in the images' order; they join `self.grad_rows` with their index and name."""
+        pending, self._grad_pending = self._grad_pending, []
+        host = iter(fetch([t for _, _, rec, cells in pending for t in (rec, cells)]))
+        rows = [None] * len(names)
+        for idx, c, _, _ in pending:
+            rec, cells = next(host), next(host)
+            for j, i in enumerate(idx):
+                rows[i] = self.gradability.measures(rec[j], cells[j], c)
+        for name, row in zip(names, rows):
+            self.grad_rows.append(dict(row, index=len(self.grad_rows) + 1, name=name))
+        return rows
 
     def back(self, image, logits_od, logits_oc, sizes, spread=None):
         """image [B,3,S,S] (the network input) and the two logit maps [B,1,S,S] on the device, sizes = [(h, w)] per image ->
@@ -421,7 +456,12 @@ class Segmenter:
             summary.update(adapt=self.adapt, prior=self.prior)
         if self.morphometry:
             summary.update(M.summarise(self.morph_rows, self.eye), sectors=self.sectors)
+        if self.gradability is not None and self.write_gradability:
+            self.grad_rows = GR.finish_rows(self.grad_rows, self.gradability)
+            summary.update(gradability=GR.summarise(self.grad_rows, self.gradability))
         write_measurements(self.out_dir, self.rows, summary)
+        if self.gradability is not None and self.write_gradability:
+            GR.write_csv(self.out_dir, self.grad_rows)
         if self.n_maps:
             U.write_csv(self.out_dir, self.sample_rows)
         if self.morphometry:
@@ -436,6 +476,7 @@ class Segmenter:
         device = next(self.nets[0].parameters()).device
         self.rows, self.sample_rows, self.sample_offsets = [], [], []
         self.morph_rows, self.morph_sample_rows = [], []
+        self.grad_rows, self._grad_pending = [], []
         per_image = V.noise_share(self.samples, self.size, len(self.views) if self.views is not None else 1)
         with V.eval_mode(self.nets), A.blended(self.nets, A.make_state(self.adapt, self.prior)):
             for first in range(0, len(folder), self.batch_size):
@@ -443,6 +484,8 @@ class Segmenter:
                 images = [folder.load(i) for i in idx]
                 image = self.front(images, device)
                 names, sizes = [folder.names[i] for i in idx], [im.shape[:2] for im in images]
+                if self.gradability is not None:
+                    self.take_gradability(names)
                 if not self.n_maps:
                     pred, pred_oc = V.predict_pair(*self.nets, image)
                     r = self.back_result(image, pred, pred_oc, sizes)
@@ -480,6 +523,7 @@ def add_arguments(ap, images_help=None):
     A.add_adapt_arguments(ap)
     from .programs import add_clahe_argument
     add_clahe_argument(ap)
+    GR.add_arguments(ap)
 
 
 def segmenter_arguments(ap, args):
@@ -496,6 +540,12 @@ def segmenter_arguments(ap, args):
               morphometry=args.morphometry, sectors=args.sectors, eye=args.eye, views=views)
     if adapt is not None:                   # (off: the keywords are what they were)
         kw.update(adapt=adapt, prior=args.prior)
+    try:
+        grad = GR.from_arguments(args)
+    except ValueError as e:
+        ap.error(str(e))
+    if grad is not None:                    # (off: the keywords are what they were)
+        kw["gradability"] = grad
     return kw
 
 
